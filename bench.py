@@ -7,12 +7,20 @@ log|Psi|, sigma2 profiled out, and the gradient w.r.t. the two remaining log-par
 at fixed theta, inputs already resident in HBM. Synthetic data from the reference's
 portable LCG (gpboost_amd/synthetic.py).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: construction, the clock ramp,
+W warm-up steps, the K timed steps, the JSON line. --dump-outputs DIR writes what the last timed
+step returned (nll, grad, sigma2) as DIR/<name>.npy (float64); the inputs are the same in every
+run. --full adds every secondary measurement (row-kernel HIP-event time and roofline, CPU
+baselines, prediction, row shards, fit, dense, grouped, FITC / VIF, the latent and Laplace legs)
+to the same line; the --no-* options choose among them. --only-grouped / --only-fitc run those
+legs alone.
 
 N > 1 is launched by torch.distributed.run (one process per GPU): observations (rows in
 Vecchia order) are split into N contiguous blocks, every rank evaluates its rows, and the
 six partial sums are all-reduced over RCCL inside the library (strong scaling: the total
-problem is fixed). The secondary latent/iterative leg runs at N > 1 with its probe columns
+problem is fixed). With --full the secondary latent/iterative leg runs at N > 1 with its probe columns
 sharded over the ranks (SURVEY.md §8e Option A). Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -1123,11 +1131,26 @@ def spawn_ranks(world: int, argv: list[str]) -> int:
     return 0
 
 
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: what the caller of the timed path received in the last timed step, one
+    float64 DIR/<name>.npy per value (a few doubles here, far below any size limit)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.atleast_1d(np.asarray(a, dtype=np.float64)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (nll, grad, sigma2) as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (kernel-event roofline, CPU baselines, prediction, "
+                         "row shards, fit, dense, grouped, FITC / VIF, latent and Laplace legs); the --no-* "
+                         "options below choose among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latent", action="store_true", help="skip the secondary latent/iterative leg")
     ap.add_argument("--latent-steps", type=int, default=3)
@@ -1140,6 +1163,8 @@ def main():
                     help="skip the per-rank row-range measurements (profiling the headline kernel alone)")
     ap.add_argument("--only-fitc", action="store_true", help="run only the FITC legs (prints their JSON)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     launched = os.environ.get("WORLD_SIZE")
     if launched is not None and int(launched) != args.gpus:
         sys.stderr.write(f"bench.py: --gpus {args.gpus} disagrees with the launcher's WORLD_SIZE={launched}\n")
@@ -1205,11 +1230,14 @@ def main():
     for _ in range(args.steps):
         nll, g, s2 = gm.neg_log_likelihood_and_grad(THETA, None, profile_sigma2=True)
     elapsed = time.perf_counter() - t0   # each eval returns to the host (synchronised), so wall = device time
+    if args.dump_outputs and rank == 0:   # every rank holds the same all-reduced sums
+        dump_outputs(args.dump_outputs, {"nll": nll, "grad": g, "sigma2": s2})
     kms = []   # row-kernel HIP-event times, read outside the timed region (same evaluation, repeated)
-    gm.last_kernel_ms()   # switches the model's event recording on (off during the timed loop)
-    for _ in range(min(args.steps, 20)):
-        gm.neg_log_likelihood_and_grad(THETA, None, profile_sigma2=True)
-        kms.append(gm.last_kernel_ms())
+    if args.full:
+        gm.last_kernel_ms()   # switches the model's event recording on (off during the timed loop)
+        for _ in range(min(args.steps, 20)):
+            gm.neg_log_likelihood_and_grad(THETA, None, profile_sigma2=True)
+            kms.append(gm.last_kernel_ms())
     latent_sharded = None
     if dist is not None:
         import torch
@@ -1217,18 +1245,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         dist.barrier()
-        if not args.no_latent:   # every rank takes part (probe-sharded latent leg)
+        if args.full and not args.no_latent:   # every rank takes part (probe-sharded latent leg)
             latent_sharded = latent_leg_sharded(X, Y, args.latent_steps, rank, world, dist)
             dist.barrier()
     if rank != 0:
         dist.destroy_process_group()
         return
 
-    kms = np.array(kms)
-    kernel_ms = float(np.mean(kms[:, 0]))
-    rows_local = (N_DATA + world - 1) // world
-    flops = vecchia_flops(N_DATA, M_NEIGHBORS) * rows_local / N_DATA
-    achieved_tf = flops / (kernel_ms * 1e-3) / 1e12
     ms_per_step = elapsed / args.steps * 1e3
     value = args.steps / elapsed
     line = {
@@ -1249,13 +1272,27 @@ def main():
                    "parallelism": f"rows{world}", "construction_s": round(t_construct, 3),
                    **({"note": "RCCL row sharding at world_size > 1: first hardware run is this one"} if world > 1 else {}),
                    "nll": nll, "grad": [float(x) for x in g]},
-        "roofline": {"bound": "valu", "achieved": achieved_tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved_tf / FP64_PEAK_TFLOPS, "traffic": None,
-                     "kernel": "vecchia_rows16_kernel<matern05,2>", "kernel_ms": kernel_ms,
-                     "algorithmic_flops_per_launch": flops,
-                     "exp_per_launch": vecchia_exps(N_DATA, M_NEIGHBORS) * rows_local / N_DATA,
-                     "note": "fp64 VALU-bound (per-row k<=30 Gauss-Jordan by DPP broadcasts + exp); FP64 vector peak = FP64 matrix peak"},
+        "full": args.full,
     }
+    if not args.full:   # a plain run: the headline figure and nothing else
+        print(json.dumps(line), file=json_out)
+        json_out.flush()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    kms = np.array(kms)
+    kernel_ms = float(np.mean(kms[:, 0]))
+    rows_local = (N_DATA + world - 1) // world
+    flops = vecchia_flops(N_DATA, M_NEIGHBORS) * rows_local / N_DATA
+    achieved_tf = flops / (kernel_ms * 1e-3) / 1e12
+    line["roofline"] = {"bound": "valu", "achieved": achieved_tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": achieved_tf / FP64_PEAK_TFLOPS, "traffic": None,
+                        "kernel": "vecchia_rows16_kernel<matern05,2>", "kernel_ms": kernel_ms,
+                        "algorithmic_flops_per_launch": flops,
+                        "exp_per_launch": vecchia_exps(N_DATA, M_NEIGHBORS) * rows_local / N_DATA,
+                        "note": "fp64 VALU-bound (per-row k<=30 Gauss-Jordan by DPP broadcasts + exp); "
+                                "FP64 vector peak = FP64 matrix peak"}
     traffic = pmc_traffic(rows_local / N_DATA)
     if traffic is not None:
         line["roofline"]["traffic"] = traffic["bytes"]
@@ -1310,9 +1347,9 @@ def main():
 
 if __name__ == "__main__":
     main()
-    # the JSON line is out: end now instead of tearing down the HIP runtime and the models' device
-    # buffers at interpreter exit (a slow teardown outlived the driver's clock, procs_at_end = 1).
-    # Profiling runs set GPBOOST_AMD_BENCH_FAST_EXIT=0: a tracer writes its results at normal exit.
+    # the JSON line is out. The process ends as any Python program does, so that whatever was registered
+    # to run at exit (a tracer writing its results, a caller's hooks) runs. GPBOOST_AMD_BENCH_FAST_EXIT=1
+    # ends at once instead, without tearing down the HIP runtime and the models' device buffers.
     # no child of the bench may outlive it (the driver counts processes at the end): the reference harness runs
     # are waited for by subprocess.run; reap anything else this process started
     try:
@@ -1323,7 +1360,7 @@ if __name__ == "__main__":
         psutil.wait_procs(kids, timeout=5)
     except Exception:  # noqa: BLE001
         pass
-    if os.environ.get("GPBOOST_AMD_BENCH_FAST_EXIT", "1") != "0":
+    if os.environ.get("GPBOOST_AMD_BENCH_FAST_EXIT", "0") == "1":
         sys.stdout.flush()
         sys.stderr.flush()
         os._exit(0)

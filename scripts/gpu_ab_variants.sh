@@ -14,7 +14,7 @@ for v in ${VARIANTS:-base}; do
     echo "$v tests: $(tail -1 gpurun_out/ab_tests_$v.log)" >> "$OUT"
   fi
   for rep in 1 2; do
-    timeout -k 10 120 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-latent ${BENCH_ARGS:-} \
+    timeout -k 10 120 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-latent ${BENCH_ARGS:-} \
       > gpurun_out/ab_b_$v.log 2>&1
     python -c "import json,sys;d=json.loads(open('gpurun_out/ab_b_$v.log').read().strip().splitlines()[-1]);print('$v', round(d['value'],1), round(d['roofline']['kernel_ms'],4))" >> "$OUT"
   done

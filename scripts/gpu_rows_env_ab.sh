@@ -17,7 +17,7 @@ for cfg in ${CFGS:--}; do
     echo "$cfg tests: $(tail -1 gpurun_out/rows_env_tests.log)" >> "$OUT"
   fi
   for rep in 1 2; do
-    env "${envs[@]}" timeout -k 10 120 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-latent --no-dense \
+    env "${envs[@]}" timeout -k 10 120 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-latent --no-dense \
       --no-fit --no-grouped > gpurun_out/rows_env_b.log 2>&1 || { echo "$cfg bench FAILED" >> "$OUT"; tail -20 gpurun_out/rows_env_b.log >> "$OUT"; exit 1; }
     python -c "import json;d=json.loads(open('gpurun_out/rows_env_b.log').read().strip().splitlines()[-1]);print('$cfg', round(d['value'],1), round(d['roofline']['kernel_ms'],4), d['config'].get('nll'))" >> "$OUT"
   done

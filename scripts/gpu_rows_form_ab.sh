@@ -17,7 +17,7 @@ for rep in 1 2 3; do
       slots) export GPBOOST_AMD_ROWS_SLOTS=1 ;;
       *) export GPBOOST_AMD_VARIANT=$form ;;
     esac
-    timeout -k 10 300 python -u bench.py --steps 400 --warmup 20 --no-latent --no-dense --no-fit --no-grouped --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --steps 400 --warmup 20 --no-latent --no-dense --no-fit --no-grouped --no-cpu-baseline \
       > $O/rows_b.json 2>> $O/rows_ab.err || exit $?
     python -c "import json;d=json.loads(open('$O/rows_b.json').read().strip().splitlines()[-1]);print('$form', round(d['ms_per_step'],4), round(d['roofline']['kernel_ms'],4), d['config']['nll'])" >> $O/rows_ab.log
   done
