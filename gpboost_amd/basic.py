@@ -209,7 +209,8 @@ class GPModel:
         # reference basic.py:4510-4533 (parameters of the likelihood path only)
         self.params = {"cg_max_num_it": 1000, "cg_max_num_it_tridiag": 1000, "cg_delta_conv": 1e-2,
                        "num_rand_vec_trace": 50, "reuse_rand_vec_trace": True, "seed_rand_vec_trace": 1,
-                       "cg_preconditioner_type": None, "init_aux_pars": None, "estimate_aux_pars": True,
+                       "cg_preconditioner_type": None, "fitc_piv_chol_preconditioner_rank": -1,   # reference :4528
+                       "init_aux_pars": None, "estimate_aux_pars": True,
                        "delta_conv_mode_finding": -1.,
                        # covariance-parameter optimizer (reference basic.py:4510-4533 defaults)
                        "optimizer_cov": None, "init_cov_pars": None, "maxit": 1000, "delta_rel_conv": -1.,
@@ -283,7 +284,8 @@ class GPModel:
             int(p["cg_max_num_it"]), int(p["cg_max_num_it_tridiag"]), float(p["cg_delta_conv"]),
             int(p["num_rand_vec_trace"]), bool(p["reuse_rand_vec_trace"]),
             p["cg_preconditioner_type"].encode() if p["cg_preconditioner_type"] else None,
-            int(p["seed_rand_vec_trace"]), -1, _dp(aux) if aux is not None else None,
+            int(p["seed_rand_vec_trace"]), int(p["fitc_piv_chol_preconditioner_rank"]),
+            _dp(aux) if aux is not None else None,
             bool(p["estimate_aux_pars"]), no_index.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(p["m_lbfgs"]),
             float(p["delta_conv_mode_finding"])))
 
@@ -589,6 +591,14 @@ class GPModel:
         out = np.zeros(4)
         _safe_call(lib().GPB_BenchLatentOperators(self.handle, ctypes.c_int(t), ctypes.c_int(reps), _dp(out)))
         return out
+
+    def piv_chol_info(self):
+        """(reached rank, device ms, pivots in Vecchia order) of the pivoted-Cholesky preconditioner's
+        factorisation in the last evaluation; rank 0 before any such evaluation."""
+        out = np.zeros(2)
+        piv = np.zeros(max(int(self.params["fitc_piv_chol_preconditioner_rank"]), 50, 1), dtype=np.int32)
+        _safe_call(lib().GPB_GetPivotedCholeskyInfo(self.handle, _dp(out), piv.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return int(out[0]), float(out[1]), piv[:int(out[0])].copy()
 
     def set_prediction_data(self, vecchia_pred_type=None, num_neighbors_pred=None, cg_delta_conv_pred=None,
                             nsim_var_pred=None, rank_pred_approx_matrix_lanczos=None, group_data_pred=None,

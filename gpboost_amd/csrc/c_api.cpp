@@ -238,8 +238,9 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
   // internal optimizers ("gradient_descent", "fisher_scoring"); L-BFGS always tests the relative change of the
   // objective (optim_utils.h:656-657)
   (void)trace;
-  (void)lr_coef; (void)acc_rate_coef; (void)piv_chol_rank;
+  (void)lr_coef; (void)acc_rate_coef;
   if (GroupedModel* g = as_grouped(handle)) {   // Gaussian grouped model: no aux parameters, no coefficients
+    (void)piv_chol_rank;
     (void)num_covariates; (void)init_coef; (void)optimizer_coef; (void)init_aux_pars; (void)estimate_aux_pars;
     (void)delta_conv_mode_finding;
     g->SetOptimSettings(init_cov_pars, lr, max_iter, delta_rel_conv, optimizer, m_lbfgs);
@@ -264,18 +265,32 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
   REModelAMD* m = model(handle);
   (void)num_covariates; (void)init_coef;   // the "wls" coefficient update profiles beta out at every evaluation
   const bool iterative = m->config().matrix_inversion_method == "iterative";
+  std::string precond;   // canonical name (ParsePreconditionerAlias, re_model_template.h:6756-6787); "": unchanged
   if (iterative && cg_preconditioner_type != nullptr && std::string(cg_preconditioner_type) != "") {
-    // ParsePreconditionerAlias (re_model_template.h:6756): the VADU aliases only
     const std::string p(cg_preconditioner_type);
-    if (p != "vadu" && p != "VADU" && p != "vecchia_approximation_with_diagonal_update" && p != "Sigma_inv_plus_BtWB")
-      gpb_amd::Fatal("cg_preconditioner_type '%s' is not supported by gpboost_amd (supported: vadu)", p.c_str());
+    if (p == "vadu" || p == "VADU" || p == "vecchia_approximation_with_diagonal_update" || p == "Sigma_inv_plus_BtWB")
+      precond = "vadu";
+    else if (p == "pivoted_cholesky" || p == "piv_chol" || p == "piv_chol_on_Sigma")
+      precond = "pivoted_cholesky";
+    else
+      gpb_amd::Fatal("cg_preconditioner_type '%s' is not supported by gpboost_amd (supported: vadu, pivoted_cholesky)",
+                     p.c_str());
+    if (precond == "pivoted_cholesky" && m->world_size() > 1)
+      gpb_amd::Fatal("cg_preconditioner_type = 'pivoted_cholesky' is not supported on multi-rank (sharded) models by "
+                     "gpboost_amd (use 'vadu')");
   }
   m->SetOptimSettings(init_cov_pars, lr, max_iter, delta_rel_conv, optimizer, m_lbfgs);
   m->SetInternalOptimSettings(acc_rate_cov, use_nesterov_acc, nesterov_schedule_version, momentum_offset,
                               convergence_criterion);
-  // validated above; the preconditioner name is recorded for iterative models only (canonical "vadu")
-  m->SetOptimizerNames(optimizer, optimizer_coef, iterative ? cg_preconditioner_type : nullptr);
+  // validated above; the canonical preconditioner name is recorded for iterative models only
+  m->SetOptimizerNames(optimizer, optimizer_coef, precond.empty() ? nullptr : precond.c_str());
   if (iterative) {   // :775-801
+    if (!precond.empty()) m->iter.piv_chol = precond == "pivoted_cholesky";
+    // fitc_piv_chol_preconditioner_rank (:789-800): a value > 0, else default_piv_chol_preconditioner_rank_ = 50
+    m->iter.piv_chol_rank = piv_chol_rank > 0 ? piv_chol_rank : 50;
+    if (m->iter.piv_chol && m->iter.piv_chol_rank > m->num_latent())   // :8464-8467
+      gpb_amd::Fatal("'fitc_piv_chol_preconditioner_rank' cannot be larger than the dimension of the mode (= number of "
+                     "unique locations) ");
     m->iter.cg_max_num_it = cg_max_num_it;
     m->iter.cg_max_num_it_tridiag = cg_max_num_it_tridiag;
     m->iter.cg_delta_conv = cg_delta_conv;
@@ -630,6 +645,20 @@ int GPB_GetCGPreconditionerType(REModelHandle handle, char* out_str, int* num_ch
     return 0;
   }
   copy_name(model(handle)->cg_preconditioner_type(), out_str, num_char);
+  API_END();
+}
+
+int GPB_GetPivotedCholeskyInfo(REModelHandle handle, double* out, int* pivots) {
+  API_BEGIN();
+  model(handle)->PivCholInfo(out, pivots);
+  API_END();
+}
+
+int GPB_PivotedCholeskyHost(const double* coords, int n, int d, int cov_type, double var, double phi, int rank,
+                            double tol, double* L, int* pivots, int* out_rank) {
+  API_BEGIN();
+  if (n < 1 || d < 1 || rank < 1 || cov_type < 0 || cov_type > 3) gpb_amd::Fatal("GPB_PivotedCholeskyHost: invalid argument");
+  *out_rank = gpb_amd::pivoted_cholesky_host(cov_type, coords, n, d, var, phi, rank, tol, L, pivots);
   API_END();
 }
 

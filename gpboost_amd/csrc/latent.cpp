@@ -102,6 +102,8 @@ LatentVecchia::~LatentVecchia() {
   if (h_ctl_) (void)hipHostFree(h_ctl_);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
+  if (evp0_) (void)hipEventDestroy(evp0_);
+  if (evp1_) (void)hipEventDestroy(evp1_);
 }
 
 namespace {
@@ -572,7 +574,9 @@ void LatentVecchia::PredVarSim(int nsim, int t, double delta, int cg_max, uint64
     }
     // rhs = B^T D^-1/2 e1 + W^1/2 e2 (likelihoods.h:6711), storage order
     launch_bt_apply(sp_, d_Bv_.get(), true, d_e1.get(), t, d_sdi.get(), d_sw.get(), d_e2.get(), d_rhs.get(), s_);
-    const PcgResult pr = Pcg(b, d_rhs.get(), d_z.get(), t, true, true, cg_max, 0, delta);
+    // pivoted Cholesky: the same draws through the CG on W^-1 + Sigma (likelihoods.h:6706; d_e1 is free again)
+    const PcgResult pr = piv_ ? SolveSigmaPlusWinv(b, d_rhs.get(), d_z.get(), true, true, cg_max, delta, d_e1.get())
+                              : Pcg(b, d_rhs.get(), d_z.get(), t, true, true, cg_max, 0, delta);
     if (pr.nan) Fatal("NaN or Inf in the conjugate gradient solves of the predictive-variance simulation");
     if (acc) launch_pred_sq_acc(n_pred, mp, t, d_nb.get(), d_Bpo, d_z.get(), d_acc.get(), s_);
     if (d_V) launch_pred_samples(n_pred, mp, t, tc, d_nb.get(), d_Bpo, d_z.get(), d_V, n_pred, done, s_);
@@ -589,21 +593,26 @@ void LatentVecchia::BenchOperators(int t, int reps, double* out) {
   const size_t nt = (size_t)n_ * t;
   HIP_CHECK(hipMemsetAsync(b.R.get(), 0, sizeof(double) * nt, s_));   // finite inputs (timing only)
   HIP_CHECK(hipMemsetAsync(b.H.get(), 0, sizeof(double) * nt, s_));
-  ApplyA(b.H.get(), b.V.get(), b.G.get(), t);              // warm (and graph capture below)
-  pre_->Apply(b.R.get(), b.Z.get(), b.Xt.get(), t);
+  ApplyOp(b.H.get(), b.V.get(), b.G.get(), t);             // warm (and graph capture below)
+  Precond(b.R.get(), b.Z.get(), b.Xt.get(), t);
   float ms = 0.f;
   HIP_CHECK(hipEventRecord(ev0_, s_));
-  for (int r = 0; r < reps; ++r) ApplyA(b.H.get(), b.V.get(), b.G.get(), t);
+  for (int r = 0; r < reps; ++r) ApplyOp(b.H.get(), b.V.get(), b.G.get(), t);
   HIP_CHECK(hipEventRecord(ev1_, s_));
   HIP_CHECK(hipEventSynchronize(ev1_));
   HIP_CHECK(hipEventElapsedTime(&ms, ev0_, ev1_));
   out[0] = ms / reps;
   HIP_CHECK(hipEventRecord(ev0_, s_));
-  for (int r = 0; r < reps; ++r) pre_->Apply(b.R.get(), b.Z.get(), b.Xt.get(), t);
+  for (int r = 0; r < reps; ++r) Precond(b.R.get(), b.Z.get(), b.Xt.get(), t);
   HIP_CHECK(hipEventRecord(ev1_, s_));
   HIP_CHECK(hipEventSynchronize(ev1_));
   HIP_CHECK(hipEventElapsedTime(&ms, ev0_, ev1_));
   out[1] = ms / reps;
+  if (piv_) {   // tptr-based counts stay; the low-rank application is four launches
+    out[2] = (double)tnnz_ + n_;
+    out[3] = 4;
+    return;
+  }
   if (std::getenv("GPBOOST_AMD_PRECOND_SPLIT")) {
     pre_->TimeParts(b.R.get(), b.Z.get(), b.Xt.get(), t, reps);
     for (int part = 0; part < 2; ++part) {   // the operator's two launches
@@ -679,11 +688,25 @@ void LatentVecchia::ApplyA(const double* H, double* V, double* G, int t) {
   g_timer.end(s_, t == 1 ? 2 : 3);
 }
 
+// V = (W^-1 + Sigma) H with Sigma H = B^-1 D B^-T H from the VADU plan with the diagonal D^-1
+// (CG_utils.cpp:297-299, 410-416)
+void LatentVecchia::ApplyOp(const double* H, double* V, double* G, int t) {
+  if (!piv_) {
+    ApplyA(H, V, G, t);
+    return;
+  }
+  g_timer.begin(s_);
+  pre_->Apply(H, V, G, t);
+  launch_add_winv(n_, t, d_W_.get(), H, V, s_);
+  g_timer.end(s_, t == 1 ? 2 : 3);
+}
+
 // Z = P^-1 R, P = B^T (D^-1 + W) B (VADU, CG_utils.cpp:56-60): VaduPrecond's three-part plan,
 // replayed from a hipGraph per buffer set.
 void LatentVecchia::Precond(const double* R, double* Z, double* Xt, int t) {
   g_timer.begin(s_);
-  pre_->Apply(R, Z, Xt, t);
+  if (piv_) lr_->Apply(R, Z, t);   // P = W^-1 + L_k L_k^T (CG_utils.cpp:276-282)
+  else pre_->Apply(R, Z, Xt, t);
   g_timer.end(s_, t == 1 ? 0 : 1);
 }
 
@@ -743,7 +766,7 @@ LatentVecchia::PcgResult LatentVecchia::Pcg(Block& b, const double* RHS, double*
     }
   }
   if (t == 1 && n_single == 1 && !init_zero && !u_is_zero) {   // r = rhs - A u (warm start, CG_utils.cpp:53-55)
-    ApplyA(U, b.V.get(), b.G.get(), t);
+    ApplyOp(U, b.V.get(), b.G.get(), t);
     launch_axpby(nt, 1., RHS, -1., b.V.get(), b.R.get(), s_);
   } else {
     HIP_CHECK(hipMemsetAsync(U, 0, sizeof(double) * nt, s_));
@@ -780,7 +803,7 @@ LatentVecchia::PcgResult LatentVecchia::Pcg(Block& b, const double* RHS, double*
   }
   for (int j = 0; ctl[kCtlActS] || ctl[kCtlActB]; ++j) {
     if (j >= std::max(pmax_single, pmax_block) + 2) Fatal("PCG: stopping rule did not end the iteration");
-    ApplyA(b.H.get(), b.V.get(), b.G.get(), t);
+    ApplyOp(b.H.get(), b.V.get(), b.G.get(), t);
     {
       const double* A[1] = {b.H.get()};
       const double* Bm[1] = {b.V.get()};
@@ -820,6 +843,8 @@ LatentVecchia::PcgResult LatentVecchia::Pcg(Block& b, const double* RHS, double*
 LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, double aux, const IterativeConfig& cfg,
                                  bool want_grad, bool want_aux_grad, double* grad_f_vo, ModeStart start) {
   if (use_chol_) return EvalChol(cov_type, lik, trafo, aux, cfg, want_grad, want_aux_grad, grad_f_vo, start);
+  if (cfg.piv_chol) return EvalPivChol(cov_type, lik, trafo, aux, cfg, want_grad, want_aux_grad, grad_f_vo, start);
+  piv_ = false;
   if (!y_set_) Fatal("response variable y has not been set");
   if (!(trafo[0] > 0. && trafo[1] > 0.)) Fatal("covariance parameters must be > 0");
   if (lik == kLikGaussian && !(aux > 0.)) Fatal("the error variance (aux_pars) must be > 0");
@@ -1180,6 +1205,381 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
                  "A t=1: %d x %.3f ms, t=%d: %d x %.3f ms\n", ms, g_timer.cnt[0],
                  g_timer.cnt[0] ? g_timer.ms[0] / g_timer.cnt[0] : 0., t, g_timer.cnt[1],
                  g_timer.cnt[1] ? g_timer.ms[1] / g_timer.cnt[1] : 0., g_timer.cnt[2],
+                 g_timer.cnt[2] ? g_timer.ms[2] / g_timer.cnt[2] : 0., t, g_timer.cnt[3],
+                 g_timer.cnt[3] ? g_timer.ms[3] / g_timer.cnt[3] : 0.);
+    g_timer = PhaseTimer();
+  }
+  return res;
+}
+
+// ---------------------------------------------------------------------------------------------
+// cg_preconditioner_type = "pivoted_cholesky": the CG runs on W^-1 + Sigma with P = W^-1 + L_k L_k^T.
+
+LatentVecchia::PcgResult LatentVecchia::SolveSigmaPlusWinv(Block& b, const double* RHS, double* U, bool init_zero,
+                                                            bool u_is_zero, int pmax, double delta, double* SigRhs) {
+  const int t = b.t;
+  PcgResult res;
+  if (t == 1 && Dot1(RHS, RHS) < kZeroRhsSq) {   // CG_utils.cpp:251-255
+    HIP_CHECK(hipMemsetAsync(U, 0, sizeof(double) * n_, s_));
+    res.zero_rhs = true;
+    return res;
+  }
+  pre_->Apply(RHS, SigRhs, b.Xt.get(), t);   // Sigma rhs (:257-259)
+  // warm start: u holds the solution of (W + Sigma^-1) u = rhs, the CG's unknown is u' = W u (:267-274)
+  if (t == 1 && !init_zero && !u_is_zero) launch_row_scale(n_, 1, d_W_.get(), false, U, U, s_);
+  res = Pcg(b, SigRhs, U, t, init_zero, u_is_zero, pmax, 0, delta);
+  if (!res.nan) launch_row_scale(n_, t, d_W_.get(), true, U, U, s_);   // u = W^-1 u' (:310-312)
+  return res;
+}
+
+void LatentVecchia::EnsureProbesPivChol(const IterativeConfig& cfg, int k) {
+  const int t = cfg.num_rand_vec_trace;
+  if (probes_saved_ && probes_t_ == t && e2_k_ == k) return;
+  t_all_ = t;
+  c0_ = 0;
+  c1_ = t;
+  // likelihoods.h:3015-3037: rand_vec_trace_I2_ (k x t) is drawn first, then rand_vec_trace_I_ (n x t):
+  // two consecutive GenRandVecNormalParallel calls on the same counter
+  std::vector<double> E2((size_t)k * t, 0.), Rv((size_t)n_ * t, 0.), R((size_t)n_ * t, 0.);
+  gen_probes_normal_cols(k, 0, t, t, cfg.seed_rand_vec_trace, probe_run_id_, E2.data());
+  ++probe_run_id_;
+  gen_probes_normal_cols(n_, 0, t, t, cfg.seed_rand_vec_trace, probe_run_id_, Rv.data());
+  ++probe_run_id_;
+  for (int p = 0; p < n_; ++p)   // drawn in Vecchia order, stored in the relabelled rows
+    std::copy(Rv.begin() + (size_t)vo_[p] * t, Rv.begin() + (size_t)(vo_[p] + 1) * t, R.begin() + (size_t)p * t);
+  d_e2_.alloc((size_t)k * t);
+  d_probes_.alloc((size_t)n_ * t);
+  d_Zp_.alloc((size_t)n_ * t);
+  d_U_.alloc((size_t)n_ * t);
+  d_P_.alloc((size_t)n_ * t);
+  HIP_CHECK(hipMemcpyAsync(d_e2_.get(), E2.data(), sizeof(double) * E2.size(), hipMemcpyHostToDevice, s_));
+  HIP_CHECK(hipMemcpyAsync(d_probes_.get(), R.data(), sizeof(double) * R.size(), hipMemcpyHostToDevice, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+  probes_t_ = t;
+  e2_k_ = k;
+  probes_saved_ = cfg.reuse_rand_vec_trace;
+}
+
+int LatentVecchia::PivCholInfo(double* ms, int* piv) {
+  if (!lr_ || !piv_) return 0;
+  std::vector<int> rows;
+  const int rank = lr_->Rank(&rows);
+  if (ms) *ms = piv_ms_;
+  if (piv)
+    for (int q = 0; q < rank; ++q) piv[q] = vo_[rows[q]];
+  return rank;
+}
+
+LatentResult LatentVecchia::EvalPivChol(int cov_type, int lik, const double* trafo, double aux,
+                                        const IterativeConfig& cfg, bool want_grad, bool want_aux_grad,
+                                        double* grad_f_vo, ModeStart start) {
+  if (!y_set_) Fatal("response variable y has not been set");
+  if (!(trafo[0] > 0. && trafo[1] > 0.)) Fatal("covariance parameters must be > 0");
+  if (lik == kLikGaussian && !(aux > 0.)) Fatal("the error variance (aux_pars) must be > 0");
+  if (world_ > 1)
+    Fatal("cg_preconditioner_type = 'pivoted_cholesky' is not supported on multi-rank (sharded) models by gpboost_amd "
+          "(use 'vadu')");
+  if (has_obs_)
+    Fatal("cg_preconditioner_type = 'pivoted_cholesky' is not supported with repeated coordinates by gpboost_amd "
+          "(use 'vadu')");
+  const int n = n_;
+  const int k = cfg.piv_chol_rank;
+  if (k > n)   // re_model_template.h:8464-8467
+    Fatal("'fitc_piv_chol_preconditioner_rank' cannot be larger than the dimension of the mode (= number of unique "
+          "locations) ");
+  if (k < 1) Fatal("'fitc_piv_chol_preconditioner_rank' must be > 0");
+  const bool gauss = lik == kLikGaussian;
+  const int t = cfg.num_rand_vec_trace;
+  if (t < 1) Fatal("num_rand_vec_trace must be >= 1");
+  LatentResult res;
+  HIP_CHECK(hipEventRecord(ev0_, s_));
+  piv_ = true;
+
+  // ---- 1. latent Vecchia factor (+ range derivatives); Sigma = B^-1 D B^-T from the VADU plan with the diagonal D^-1
+  LatentFactorArgs fa{};
+  fa.X = d_Xp_.get();
+  fa.nbr = d_nbr_.get();
+  fa.n = n; fa.d = d_; fa.m = m_;
+  fa.var = trafo[0];
+  fa.phi = trafo[1];
+  fa.jitter = kJitterMultVecchia;
+  fa.Bv = d_Bv_.get();
+  fa.dBv = want_grad ? d_dBv_.get() : nullptr;
+  fa.Dinv = d_Dinv_.get();
+  fa.dD = want_grad ? d_dD_.get() : nullptr;
+  launch_latent_factor(cov_type, fa, s_);
+  pre_->Refresh(d_Bv_.get());
+  launch_gather(tnnz_, d_tslot_.get(), d_Bv_.get(), d_tval_.get(), s_);
+  if (seg2_n_ > 0) launch_gather(seg2_n_, d_seg_slot2_.get(), d_Bv_.get(), d_seg_val2_.get(), s_);
+  sp_.tval_of = d_Bv_.get();
+  launch_gather(n * m_, d_ell_slot_.get(), d_Bv_.get(), d_ell_val_.get(), s_);
+  sp_.vals_of = d_Bv_.get();
+  factor_ready_ = true;
+  pre_->SetDiag(d_Dinv_.get());
+
+  // ---- 1b. pivoted Cholesky of the exact Sigma, once per evaluation (re_model_template.h:8470-8476)
+  if (!lr_ || lr_->k() != k) {
+    lr_.reset(new LowRankPrecond(n, k, s_));
+    d_lab_.alloc(n);
+    HIP_CHECK(hipMemcpyAsync(d_lab_.get(), lab_.data(), sizeof(int) * n, hipMemcpyHostToDevice, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+    for (auto* bf : {&d_wis_, &d_rowdiag_, &d_dWloc_, &d_sig1_}) bf->alloc(n);
+  }
+  if (!evp0_) {
+    HIP_CHECK(hipEventCreate(&evp0_));
+    HIP_CHECK(hipEventCreate(&evp1_));
+  }
+  HIP_CHECK(hipEventRecord(evp0_, s_));
+  lr_->Factorize(cov_type, d_Xp_.get(), d_, trafo[0], trafo[1], d_lab_.get());
+  HIP_CHECK(hipEventRecord(evp1_, s_));
+
+  Block& b1 = GetBlock(0, 1, std::max(cfg.cg_max_num_it, 1));
+  ScalarArgs sa{};
+  sa.n = n; sa.m = m_; sa.lik = lik; sa.aux = aux;
+  sa.nbr = d_nbr_.get(); sa.Bv = d_Bv_.get(); sa.Dinv = d_Dinv_.get(); sa.y = d_y_.get();
+  sa.offset = has_off_ ? d_off_.get() : nullptr;
+  sa.obs = Obs();
+
+  // ---- 2. mode finding (likelihoods.h:2780-3000)
+  if (start == ModeStart::kZero) {
+    HIP_CHECK(hipMemsetAsync(d_mode_.get(), 0, sizeof(double) * n, s_));
+  } else if (start == ModeStart::kWarm) {
+    d_mode_prev_.alloc(n);
+    launch_copy(n, d_mode_.get(), d_mode_prev_.get(), s_);
+    mode_prev_valid_ = true;
+  }
+  HIP_CHECK(hipMemsetAsync(d_mode_upd_.get(), 0, sizeof(double) * n, s_));
+  double sc[kLatentScalars];
+  sa.mode = d_mode_.get();
+  Scalars(sa, sc);
+  if (std::isnan(sc[kSqLogDinv]) || std::isinf(sc[kSqLogDinv]))   // Vecchia_utils.cpp:1619-1630
+    Fatal("The matrix D in the Vecchia approximation contains negative or zero values. "
+          "This likely results from numerical instabilities ");
+  double mll = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
+  const int maxit = gauss ? 1 : 1000;
+  const int max_shrink = gauss ? 1 : 20;
+  const int pmax_tri = std::max(1, std::min(cfg.cg_max_num_it_tridiag, n));
+  const int cg_max = std::max(0, cfg.cg_max_num_it);
+  auto line_search_and_check = [&](int it, double gdd) -> bool {   // likelihoods.h:2967-2995, 11820-11870
+    double lr = 1., mll_new = mll;
+    for (int ih = 0; ih < max_shrink; ++ih) {
+      if (ih == 0) launch_copy(n, d_mode_upd_.get(), d_mode_new_.get(), s_);
+      else launch_axpby(n, 1. - lr, d_mode_.get(), lr, d_mode_upd_.get(), d_mode_new_.get(), s_);
+      if (lik == kLikPoisson || lik == kLikGamma) launch_cap_mode_change(n, d_mode_.get(), d_mode_new_.get(), s_);
+      sa.mode = d_mode_new_.get();
+      Scalars(sa, sc);
+      mll_new = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
+      if (mll_new < mll + kCArmijo * lr * gdd || std::isnan(mll_new) || std::isinf(mll_new)) lr *= 0.5;
+      else break;
+    }
+    std::swap(d_mode_, d_mode_new_);
+    res.newton_its = it + 1;
+    if (std::isnan(mll_new) || std::isinf(mll_new))
+      throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
+    const double dc = cfg.delta_conv_mode_finding;
+    const bool term = (it == 0) ? std::fabs(mll_new - mll) < dc * std::fabs(mll) : (mll_new - mll) < dc * std::fabs(mll);
+    mll = mll_new;
+    return term;
+  };
+  auto prep = [&](int w_update, bool want_rhs) {
+    NewtonPrepArgs np{};
+    np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
+    np.offset = has_off_ ? d_off_.get() : nullptr;
+    np.obs = Obs();
+    np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get(); np.W_update = w_update;
+    np.rhs = want_rhs ? d_rhs_.get() : nullptr;
+    np.dw = d_dw_.get();
+    launch_newton_prep(np, s_);
+  };
+  // I_k + L_k^T W L_k, its factor and inverse for the current W (likelihoods.h:11985-11990, 12099-12103)
+  double logdet_G = 0.;
+  auto gram = [&](bool in_mode_finding) {
+    lr_->SetWeights(d_W_.get());
+    int flags = 0;
+    logdet_G = lr_->LogDetG(&flags);
+    // the Woodbury inversion is unstable when the information is very large (:11977-11979)
+    if ((flags & 1) && in_mode_finding)
+      throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
+    if (flags & 2)   // :12083-12086
+      Fatal("0's or negative values found in the (diagonal) Hessian (or Fisher information) of the negative "
+            "log-likelihood. This is not permitted when using the Vecchia approximation and iterative methods with the "
+            "'pivoted_cholesky' preconditioner. Try using another preconditioner (e.g. 'vadu') or the Cholesky "
+            "decomposition ");
+    if ((flags & 4) || std::isnan(logdet_G) || std::isinf(logdet_G))
+      throw LatentNan("NaN or Inf occurred in the pivoted Cholesky preconditioner (I_k + L_k^T W L_k)");
+  };
+  if (gauss) {
+    prep(1, true);
+    gram(true);
+    const PcgResult pr = SolveSigmaPlusWinv(b1, d_rhs_.get(), d_mode_upd_.get(), true, true, cg_max, cfg.cg_delta_conv,
+                                            d_sig1_.get());
+    res.cg_its += pr.its_single;
+    if (pr.nan) throw LatentNan("NaN or Inf occurred in the conjugate gradient algorithm during mode finding");
+    line_search_and_check(0, 0.);
+    prep(0, false);   // first derivative at the mode (likelihoods.h:3008)
+  } else {
+    bool upd_zero = true;
+    const int newton_its = start == ModeStart::kKeep ? 0 : maxit;
+    for (int it = 0; it < newton_its; ++it) {
+      prep(1, true);
+      gram(true);
+      const PcgResult pr = SolveSigmaPlusWinv(b1, d_rhs_.get(), d_mode_upd_.get(), it == 0, upd_zero, cg_max,
+                                              cfg.cg_delta_conv, d_sig1_.get());
+      res.cg_its += pr.its_single;
+      upd_zero = pr.zero_rhs;
+      if (pr.nan) throw LatentNan("NaN or Inf occurred in the conjugate gradient algorithm during mode finding");
+      launch_axpby(n, 1., d_mode_upd_.get(), -1., d_mode_.get(), d_dir_.get(), s_);   // Armijo (:2957-2966)
+      ApplyA(d_dir_.get(), d_Adir_.get(), b1.G.get(), 1);
+      const double gdd = Dot1(d_dir_.get(), d_Adir_.get());
+      if (line_search_and_check(it, gdd)) break;
+    }
+    prep(1, false);   // derivative / information at the mode (:3008-3011)
+    gram(false);
+  }
+
+  // ---- 3. SLQ (likelihoods.h:12082-12162): z_i = L_k r2_i + W^-1/2 r_i ~ N(0, P), Lanczos on P^-1 (W^-1 + Sigma)
+  EnsureProbesPivChol(cfg, k);
+  launch_rsqrt_vec(n, d_W_.get(), d_wis_.get(), s_);
+  lr_->Combine(d_probes_.get(), d_wis_.get(), nullptr, 1., nullptr, d_e2_.get(), d_Zp_.get(), t);
+  Block& bt = GetBlock(1, t, pmax_tri);
+  const PcgResult slq = Pcg(bt, d_Zp_.get(), d_U_.get(), 0, true, true, 0, pmax_tri, cfg.cg_delta_conv);
+  if (slq.nan) throw LatentNan("NaN or Inf occurred in the stochastic Lanczos quadrature (log-determinant)");
+  const int L = slq.its_block;
+  res.lanczos_steps = L;
+  std::vector<double> ah((size_t)L * t), bh((size_t)L * t);
+  HIP_CHECK(hipMemcpyAsync(ah.data(), bt.a_hist.get(), sizeof(double) * ah.size(), hipMemcpyDeviceToHost, s_));
+  if (L > 1)
+    HIP_CHECK(hipMemcpyAsync(bh.data(), bt.b_hist.get(), sizeof(double) * (size_t)(L - 1) * t, hipMemcpyDeviceToHost, s_));
+  sa.mode = d_mode_.get();
+  sa.dw = d_dw_.get();
+  Scalars(sa, sc);   // synchronises the stream
+  std::vector<std::vector<double>> Td(t), Ts(t);
+  for (int c = 0; c < t; ++c) {   // CG_utils.cpp:458-464
+    Td[c].resize(L);
+    Ts[c].resize(L > 0 ? L - 1 : 0);
+    for (int j = 0; j < L; ++j) {
+      const double a = ah[(size_t)j * t + c];
+      const double a_old = j > 0 ? ah[(size_t)(j - 1) * t + c] : 1.;
+      const double b_old = j > 0 ? bh[(size_t)(j - 1) * t + c] : 0.;
+      Td[c][j] = 1. / a + b_old / a_old;
+      if (j > 0) Ts[c][j - 1] = std::sqrt(b_old) / a_old;
+    }
+  }
+  // log|Sigma W + I| = log|P^-1 (W^-1 + Sigma)| + log|W| + log|P|, log|P| = log|I_k + L_k^T W L_k| - log|W| (:12146-12150)
+  res.logdet = slq_logdet(Td, Ts, n) + logdet_G;
+  res.nll = -(mll - 0.5 * res.logdet);
+  {
+    float pm = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&pm, evp0_, evp1_));
+    piv_ms_ = pm;
+  }
+
+  if (want_grad) {
+    // ---- 4. gradient (likelihoods.h:4951-5206 with 12241-12300, 12403-12421, 12487-12506)
+    const size_t nt = (size_t)n * t;
+    for (auto* bf : {&d_wiu_, &d_wipz_, &d_sigU_, &d_sigP_, &d_sigX_}) bf->alloc(nt);
+    launch_row_scale(n, t, d_W_.get(), true, d_U_.get(), d_wiu_.get(), s_);   // W^-1 (W^-1 + Sigma)^-1 Z
+    // W^-1 P^-1 Z = Z - L_k (I_k + L_k^T W L_k)^-1 L_k^T W Z (:12253-12261)
+    lr_->Combine(d_Zp_.get(), nullptr, nullptr, -1., d_Zp_.get(), nullptr, d_wipz_.get(), t);
+    if (!gauss) {   // implicit derivative through the mode
+      launch_lik_dinfo(n, lik, aux, d_y_.get(), d_mode_.get(), has_off_ ? d_off_.get() : nullptr, d_dWloc_.get(), s_);
+      lr_->RowDiag(d_rowdiag_.get());
+      launch_lowrank_mode_deriv(n, t, d_dWloc_.get(), d_W_.get(), d_rowdiag_.get(), d_wiu_.get(), d_wipz_.get(),
+                                d_dmll_.get(), s_);
+      const PcgResult pv = SolveSigmaPlusWinv(b1, d_dmll_.get(), d_vS_.get(), true, true, cg_max, cfg.cg_delta_conv,
+                                              d_sig1_.get());   // :5029
+      res.cg_its += pv.its_single;
+      if (pv.nan) Warning("NaN or Inf occurred in the conjugate gradient algorithm of the gradient calculation");
+    }
+    // covariance parameters, no variance reduction (:12403-12421):
+    // d log|Sigma W + I| / d theta = -mean_i (Sigma u_i)^T dSigma^-1 (Sigma P^-1 z_i)
+    pre_->Apply(d_U_.get(), d_sigU_.get(), d_sigX_.get(), t);
+    launch_row_scale(n, t, d_W_.get(), false, d_wipz_.get(), d_P_.get(), s_);   // P^-1 Z
+    pre_->Apply(d_P_.get(), d_sigP_.get(), d_sigX_.get(), t);
+    GradColsArgs ga{};
+    ga.n = n; ga.m = m_; ga.t = t; ga.nbr = d_nbr_.get(); ga.Bv = d_Bv_.get(); ga.dBv = d_dBv_.get();
+    ga.Dinv = d_Dinv_.get(); ga.dD = d_dD_.get(); ga.W = d_W_.get();
+    ga.daux = 0.;
+    ga.obs_ptr = nullptr;
+    ga.U = d_sigU_.get(); ga.P = d_sigP_.get();
+    launch_grad_cols(ga, d_partials_.get(), d_out_.get(), s_);
+    std::vector<double> z((size_t)kGradCols * t);
+    HIP_CHECK(hipMemcpyAsync(z.data(), d_out_.get(), sizeof(double) * z.size(), hipMemcpyDeviceToHost, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+    ScalarArgs sg = sa;
+    sg.dBv = d_dBv_.get();
+    sg.dD = d_dD_.get();
+    sg.vS = gauss ? nullptr : d_vS_.get();
+    Scalars(sg, sc);
+    auto mean = [t](const double* v) {
+      double s = 0.;
+      for (int c = 0; c < t; ++c) s += v[c];
+      return s / t;
+    };
+    {   // marginal variance: dSigma^-1 = -Sigma^-1
+      double g = 0.5 * (-sc[kSqQuad] - mean(z.data()));
+      if (!gauss) g += sc[kSqImpVar];
+      res.grad.push_back(g);
+    }
+    {   // range
+      double g = 0.5 * (2. * sc[kSqDQuadRng] - sc[kSqDDQuad] - mean(z.data() + 2 * t));
+      if (!gauss) g -= sc[kSqImpRng];
+      res.grad.push_back(g);
+    }
+    if (grad_f_vo != nullptr) {   // wrt the fixed effects F (likelihoods.h:5337-5367)
+      d_gradf_.alloc(n);
+      launch_grad_f(n, d_d1_.get(), gauss ? nullptr : d_dmll_.get(), d_W_.get(), gauss ? nullptr : d_vS_.get(),
+                    d_gradf_.get(), s_);
+      std::vector<double> gp(n);
+      HIP_CHECK(hipMemcpyAsync(gp.data(), d_gradf_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
+      HIP_CHECK(hipStreamSynchronize(s_));
+      for (int p = 0; p < n; ++p) grad_f_vo[vo_[p]] = gp[p];
+    }
+    // gamma shape on the log scale (:5139-5202): the diagonal of (Sigma^-1 + W)^-1 comes from d_dmll_ as for vadu
+    if (lik == kLikGamma && want_aux_grad) {
+      DevBuf<double> rec((size_t)3 * n), red(3);
+      launch_gamma_aux_rec(n, aux, d_y_.get(), has_off_ ? d_off_.get() : nullptr, d_mode_.get(), d_W_.get(),
+                           d_dmll_.get(), d_d1_.get(), d_vS_.get(), rec.get(), s_);
+      launch_sum_blocks(rec.get(), n, 3, red.get(), s_);
+      double h[3];
+      HIP_CHECK(hipMemcpyAsync(h, red.get(), sizeof(h), hipMemcpyDeviceToHost, s_));
+      HIP_CHECK(hipStreamSynchronize(s_));
+      const double neg = aux * (h[0] - n * (std::log(aux) + 1. - digamma_asa103(aux)) - sum_log_y_);
+      res.grad.push_back(neg + 0.5 * h[1] + h[2]);
+    }
+    // gaussian error variance on the log scale (:12487-12506): dW / dlog aux = -W = -1 / aux on every row
+    if (gauss && want_aux_grad) {
+      const double da = -1. / aux;
+      lr_->RowDiag(d_rowdiag_.get());
+      launch_weighted_coldots(n, t, d_wiu_.get(), nullptr, d_wipz_.get(), d_partials_.get(), d_out_.get(), s_);
+      launch_weighted_coldots(n, t, d_wipz_.get(), nullptr, d_wipz_.get(), d_partials_.get(), d_out_.get() + t, s_);
+      launch_weighted_coldots(n, 1, d_rowdiag_.get(), nullptr, d_W_.get(), d_partials_.get(), d_out_.get() + 2 * t, s_);
+      std::vector<double> zz((size_t)2 * t + 1);
+      HIP_CHECK(hipMemcpyAsync(zz.data(), d_out_.get(), sizeof(double) * zz.size(), hipMemcpyDeviceToHost, s_));
+      HIP_CHECK(hipStreamSynchronize(s_));
+      std::vector<double> z1(t), zP(t);
+      for (int c = 0; c < t; ++c) {
+        z1[c] = -da * zz[c];        // -(W^-1 u)^T dW (W^-1 P^-1 z)
+        zP[c] = -da * zz[t + c];    // -(W^-1 P^-1 z)^T dW (W^-1 P^-1 z)
+      }
+      const double tr1 = mean(z1.data()), trP = mean(zP.data());
+      const double trWI = -(double)n;          // tr(W^-1 dW)
+      const double trK = -zz[2 * t];           // tr((I_k + L_k^T W L_k)^-1 L_k^T dW L_k)
+      const double c = optimal_c(z1.data(), zP.data(), t, tr1, trP);
+      const double dd = tr1 + trWI + c * (trK - trWI) - c * trP;
+      res.grad.push_back(sc[kSqRss] * (-0.5 / aux) + 0.5 * n + 0.5 * dd);
+    }
+  }
+  HIP_CHECK(hipEventRecord(ev1_, s_));
+  HIP_CHECK(hipEventSynchronize(ev1_));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, ev0_, ev1_));
+  res.ms_total = ms;
+  if (g_timer.on) {
+    std::fprintf(stderr, "[latent timing, pivoted_cholesky] total %.1f ms | factorisation %.3f ms (rank %d) | precond "
+                 "t=1: %d x %.3f ms, t=%d: %d x %.3f ms | W^-1 + Sigma t=1: %d x %.3f ms, t=%d: %d x %.3f ms\n", ms,
+                 piv_ms_, lr_->Rank(), g_timer.cnt[0], g_timer.cnt[0] ? g_timer.ms[0] / g_timer.cnt[0] : 0., t,
+                 g_timer.cnt[1], g_timer.cnt[1] ? g_timer.ms[1] / g_timer.cnt[1] : 0., g_timer.cnt[2],
                  g_timer.cnt[2] ? g_timer.ms[2] / g_timer.cnt[2] : 0., t, g_timer.cnt[3],
                  g_timer.cnt[3] ? g_timer.ms[3] / g_timer.cnt[3] : 0.);
     g_timer = PhaseTimer();

@@ -27,6 +27,7 @@
 #include "collective.h"
 #include "latent_kernels.h"
 #include "vadu_precond.h"
+#include "lowrank_precond.h"
 #include "sparse_chol.h"
 
 namespace gpb_amd {
@@ -39,6 +40,10 @@ struct IterativeConfig {
   int seed_rand_vec_trace = 1;             // :5380
   bool reuse_rand_vec_trace = true;
   double delta_conv_mode_finding = 1e-8;   // likelihoods.h:12723
+  // cg_preconditioner_type: false "vadu" (P = B^T (D^-1 + W) B, CG on Sigma^-1 + W); true
+  // "pivoted_cholesky" (P = W^-1 + L_k L_k^T, CG on W^-1 + Sigma; lowrank_precond.h)
+  bool piv_chol = false;
+  int piv_chol_rank = 50;                  // default_piv_chol_preconditioner_rank_ (re_model_template.h:789-800)
 };
 
 // NaN / Inf in the mode finding or a CG solve of an evaluation. The reference sets the approximate
@@ -139,7 +144,12 @@ class LatentVecchia : public LatentSolverBase {
   // A = B^T D^-1 B + W application, out[1] = ms per VADU preconditioner application (both on
   // t columns, averaged over reps, HIP events on the model's stream), out[2] = nnz(B) incl.
   // the unit diagonal, out[3] = dependent launches per preconditioner application.
+  // After an evaluation with the pivoted-Cholesky preconditioner the two costs are those of its CG: out[0] = ms
+  // per W^-1 + Sigma application, out[1] = ms per P^-1 = (W^-1 + L_k L_k^T)^-1 application, out[3] = 4.
   void BenchOperators(int t, int reps, double* out);
+  // Pivoted-Cholesky preconditioner of the last evaluation: reached rank, device ms of the factorisation
+  // and (piv nullable, >= rank entries) the pivots in Vecchia order. Rank 0: no such evaluation yet.
+  int PivCholInfo(double* ms, int* piv);
 
   // Predictive-variance simulation of PredictLaplaceApproxVecchia (likelihoods.h:6628-6746,
   // iterative): nsim draws z ~ N(0, (Sigma^-1 + W)^-1), each the solution of (Sigma^-1 + W) z =
@@ -220,6 +230,18 @@ class LatentVecchia : public LatentSolverBase {
   // over all ranks (> 0 with a collective: the block rule uses the all-reduced norm sum).
   PcgResult Pcg(Block& b, const double* RHS, double* U, int n_single, bool init_zero, bool u_is_zero,
                 int pmax_single, int pmax_block, double delta, int n_valid = -1, int nblock_all = 0);
+  // The operator of the PCG: A (vadu) or W^-1 + Sigma = W^-1 + B^-1 D B^-T (pivoted Cholesky; G = scratch)
+  void ApplyOp(const double* H, double* V, double* G, int t);
+  // U = (Sigma^-1 + W)^-1 RHS for b.t independent columns through the CG on W^-1 + Sigma
+  // (CGVecchiaLaplaceSigmaPlusWinvVec, CG_utils.cpp:219-344): right-hand side Sigma RHS, warm start W U,
+  // result W^-1 u. Same arguments as Pcg with n_single = b.t.
+  // SigRhs: n x b.t scratch.
+  PcgResult SolveSigmaPlusWinv(Block& b, const double* RHS, double* U, bool init_zero, bool u_is_zero, int pmax,
+                               double delta, double* SigRhs);
+  // the pivoted-Cholesky branch of Eval
+  LatentResult EvalPivChol(int cov_type, int lik, const double* trafo, double aux, const IterativeConfig& cfg,
+                           bool want_grad, bool want_aux_grad, double* grad_f_vo, ModeStart start);
+  void EnsureProbesPivChol(const IterativeConfig& cfg, int k);
   // Sum of a host vector over ranks (identity at world 1).
   void AllReduceHost(double* v, int count);
   int probe_cols() const { return world_ > 1 ? (t_all_ + world_ - 1) / world_ : t_all_; }
@@ -253,6 +275,17 @@ class LatentVecchia : public LatentSolverBase {
   DevBuf<double> d_ell_val_;
   int dense_rows_ = 0, head_rows_ = 0;   // VADU plan split (VaduPrecond)
   std::unique_ptr<VaduPrecond> pre_;
+  // pivoted-Cholesky preconditioner (built at the first evaluation that asks for it)
+  std::unique_ptr<LowRankPrecond> lr_;
+  bool piv_ = false;                 // the operator / preconditioner pair Pcg runs on (set by the last Eval)
+  DevBuf<int> d_lab_;                // storage row of Vecchia row h (the initial permutation)
+  DevBuf<double> d_wis_, d_rowdiag_, d_dWloc_, d_sig1_;   // W^-1/2, diag(L M L^T), dW / d location, Sigma rhs: n
+  DevBuf<double> d_e2_;              // rand_vec_trace_I2_: k x t
+  DevBuf<double> d_wiu_, d_wipz_;    // W^-1 (W^-1 + Sigma)^-1 Z and W^-1 P^-1 Z: n x t
+  DevBuf<double> d_sigU_, d_sigP_, d_sigX_;   // Sigma (W^-1 + Sigma)^-1 Z, Sigma P^-1 Z, scratch: n x t
+  int e2_k_ = 0;
+  float piv_ms_ = 0.f;
+  hipEvent_t evp0_ = nullptr, evp1_ = nullptr;
   DevBuf<double> d_y_, d_Bv_, d_dBv_, d_Dinv_, d_dD_, d_W_, d_dw_, d_sdw_, d_d1_;
   double sum_log_y_ = 0.;   // likelihood 'gamma
   DevBuf<double> d_mode_, d_mode_upd_, d_mode_new_, d_rhs_, d_dir_, d_Adir_, d_vS_, d_dmll_;

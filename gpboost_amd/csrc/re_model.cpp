@@ -1481,6 +1481,13 @@ void REModelAMD::BenchLatentOperators(int t, int reps, double* out) {
   latent_->BenchOperators(t, reps, out);
 }
 
+void REModelAMD::PivCholInfo(double* out, int* pivots) {
+  out[0] = out[1] = 0.;
+  if (!cfg_.latent || !latent_) return;
+  UseDevice();
+  out[0] = latent_->PivCholInfo(&out[1], pivots);
+}
+
 EvalResult REModelAMD::Eval(const double* cov_pars_orig, bool want_grad, int profile) {
   if (!y_set_) Fatal("response variable y has not been set");
   if (cfg_.latent) {

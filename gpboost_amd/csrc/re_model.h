@@ -133,6 +133,11 @@ class REModelAMD {
   void GetLastIterationInfo(double* out) const { for (int k = 0; k < 4; ++k) out[k] = last_iter_info_[k]; }
   void CholeskyPlanInfo(double* out);   // GPB_GetCholeskyPlanInfo (latent Vecchia, cholesky)
   void BenchLatentOperators(int t, int reps, double* out);
+  // Pivoted-Cholesky preconditioner of the last evaluation (LatentVecchia::PivCholInfo): out[0] = reached rank
+  // (0: none), out[1] = device ms of the factorisation; pivots (nullable): Vecchia-order indices, >= rank entries.
+  void PivCholInfo(double* out, int* pivots);
+  int world_size() const { return world_; }
+  int num_latent() const { return nu_; }
   void GetLastKernelTimes(double* ms);
   // FITC inducing points (host row-major m x d; EXTENSION: GPB_GetInducingPoints)
   const std::vector<double>& InducingPoints() const;

@@ -452,7 +452,7 @@ void REModelAMD::SetOptimizerNames(const char* optimizer_cov, const char* optimi
             o.c_str());
     optimizer_coef_ = o;
   }
-  if (preconditioner != nullptr && preconditioner[0] != '\0') cg_preconditioner_type_ = "vadu";
+  if (preconditioner != nullptr && preconditioner[0] != '\0') cg_preconditioner_type_ = preconditioner;   // canonical
 }
 
 std::string REModelAMD::cg_preconditioner_type() const {

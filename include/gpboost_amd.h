@@ -353,6 +353,21 @@ GPBOOST_AMD_EXPORT int GPB_GetLastKernelTimes(REModelHandle handle, double* kern
  * kernels). No reference counterpart (measurement only). */
 GPBOOST_AMD_EXPORT int GPB_BenchLatentOperators(REModelHandle handle, int t, int reps, double* out);
 
+/* cg_preconditioner_type = "pivoted_cholesky" (latent Vecchia, iterative): the factorisation of the last
+ * evaluation. out[0] = reached rank (0: no such evaluation yet), out[1] = its device time in ms (HIP
+ * events); pivots (nullable, >= rank entries): the pivots in Vecchia order. After such an evaluation
+ * GPB_BenchLatentOperators times the CG's operator W^-1 + Sigma (out[0]) and the preconditioner
+ * (W^-1 + L_k L_k^T)^-1 (out[1]). No reference counterpart (measurement and tests). */
+GPBOOST_AMD_EXPORT int GPB_GetPivotedCholeskyInfo(REModelHandle handle, double* out, int* pivots);
+
+/* Host restatement of the reference's PivotedCholsekyFactorizationSigma (CG_utils.h:438-488), the rules
+ * the device factorisation follows; needs no GPU. coords: row-major n x d in the order the permutation
+ * starts from; cov_type 0 / 1 / 2 Matern 0.5 / 1.5 / 2.5, 3 Gaussian; (var, phi) on the transformed
+ * scale. L: row-major n x min(rank, n), pivots: min(rank, n) entries, out_rank: the reached rank. */
+GPBOOST_AMD_EXPORT int GPB_PivotedCholeskyHost(const double* coords, int n, int d, int cov_type, double var,
+                                               double phi, int rank, double tol, double* L, int* pivots,
+                                               int* out_rank);
+
 /* ---------------------------------------------------------------- prediction */
 
 /* replaces GPB_SetPredictionData (include/LightGBM/c_api.h:1578; c_api.cpp). Only the settings
