@@ -151,7 +151,10 @@ class GPModel:
                       gp_coords=None, cov_function="matern", cov_fct_shape=1.5, gp_approx="none"):
         """Grouped random effects (reference basic.py GPModel.__init__ group_data handling): labels are
         converted to strings and passed column-major as NUL-terminated C strings. With gp_coords: the
-        combined model with one GP component (gp_approx "none")."""
+        combined model with one GP component (gp_approx "none"). likelihood "bernoulli_logit",
+        "bernoulli_probit", "poisson" or "gamma": the Laplace approximation (several grouping variables: "iterative"
+        by default, or "cholesky"); cov_pars then are the K variances without an error term and
+        gamma's shape is the auxiliary parameter."""
         g = np.asarray(group_data)
         if g.ndim == 1:
             g = g.reshape(-1, 1)
@@ -392,6 +395,8 @@ class GPModel:
     def cov_par_names(self):
         """Parameter names as the reference labels them (error term only for the Gaussian likelihood)."""
         if getattr(self, "num_group_re", 0):
+            if self.likelihood != "gaussian":   # no error term
+                return [f"Group_{k + 1}" for k in range(self.num_group_re)]
             return (["Error_term"] + [f"Group_{k + 1}" for k in range(self.num_group_re)] +
                     (["GP_var", "GP_range"] if getattr(self, "has_gp", False) else []))
         return (["Error_term"] if self.num_cov_pars == 3 else []) + ["GP_var", "GP_range"]
@@ -600,6 +605,20 @@ class GPModel:
         _safe_call(lib().GPB_GetPivotedCholeskyInfo(self.handle, _dp(out), piv.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return int(out[0]), float(out[1]), piv[:int(out[0])].copy()
 
+    def grouped_laplace_info(self):
+        """Grouped random effects with a non-Gaussian likelihood (GPB_GetGroupedLaplaceInfo): the CSR
+        (rowptr, col) of the off-diagonal part of Z^T Z over the M random effects and the diagonal / off-diagonal
+        values of Z^T W Z at the mode of the last evaluation. Returns (rowptr, col, diag, vals)."""
+        dims = np.zeros(2, dtype=np.int32)
+        _safe_call(lib().GPB_GetGroupedLaplaceInfo(self.handle, _ip(dims), None, None, None, None))
+        M, nnz = int(dims[0]), int(dims[1])
+        rowptr = np.zeros(M + 1, dtype=np.int32)
+        col = np.zeros(max(nnz, 1), dtype=np.int32)
+        diag = np.zeros(M)
+        vals = np.zeros(max(nnz, 1))
+        _safe_call(lib().GPB_GetGroupedLaplaceInfo(self.handle, _ip(dims), _ip(rowptr), _ip(col), _dp(diag), _dp(vals)))
+        return rowptr, col[:nnz], diag, vals[:nnz]
+
     def set_prediction_data(self, vecchia_pred_type=None, num_neighbors_pred=None, cg_delta_conv_pred=None,
                             nsim_var_pred=None, rank_pred_approx_matrix_lanczos=None, group_data_pred=None,
                             group_rand_coef_data_pred=None, gp_coords_pred=None, gp_rand_coef_data_pred=None,
@@ -746,7 +765,9 @@ class GPModel:
         """Predictions of a grouped random effects model at new group labels (GPB_PredictREModel
         with re_group_data_pred): means = sum over the effects of the training posterior mean of the
         label's level (0 for a level not seen in training); with predict_var / predict_cov_mat
-        (matrix_inversion_method = "cholesky") the predictive variances / covariance matrix."""
+        (matrix_inversion_method = "cholesky") the predictive variances / covariance matrix. Non-Gaussian
+        likelihoods: the means are sums of the Laplace mode's levels, predict_var gives the latent variances,
+        predict_response maps both through the likelihood (no covariance matrices)."""
         if group_data_pred is None:
             raise ValueError("'group_data_pred' is missing")
         g = np.asarray(group_data_pred)

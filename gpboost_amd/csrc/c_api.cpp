@@ -164,15 +164,20 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
     if (num_gp == 1 && str_or(gp_approx, "none") != "none")
       gpb_amd::Fatal("GP + grouped random effects models with gp_approx = '%s' are not supported (the reference "
                      "allows only 'none' there, re_model_template.h:236-239)", gp_approx);
-    if (str_or(likelihood, "gaussian") != "gaussian")
-      gpb_amd::Fatal("grouped random effects with likelihood '%s' are not supported by gpboost_amd (supported: gaussian)",
-                     likelihood);
+    // non-Gaussian likelihoods: the Laplace approximation of GroupedLaplace; names outside parse_likelihood's fail there
+    const std::string lik_name = str_or(likelihood, "gaussian");
+    if (lik_name != "gaussian") {
+      (void)gpb_amd::parse_likelihood(lik_name);
+      if (num_gp == 1)
+        gpb_amd::Fatal("a Gaussian process beside grouped random effects (gp_coords with group_data) is not supported "
+                       "for likelihood '%s' by gpboost_amd", lik_name.c_str());
+    }
     if (num_data <= 0) gpb_amd::Fatal("num_data must be > 0");
     std::vector<std::unordered_map<std::string, int>> index;
     auto levels = gpb_amd::parse_group_levels(num_data, num_re_group, re_group_data, &index);
     std::string mim = str_or(matrix_inversion_method, "default");
     if (num_gp == 1 && mim == "default") mim = "cholesky";   // a GP beside: the dense path
-    std::unique_ptr<GroupedModel> gm(new GroupedModel(num_data, levels, mim, seed, std::move(index)));
+    std::unique_ptr<GroupedModel> gm(new GroupedModel(num_data, levels, mim, seed, std::move(index), lik_name));
     if (num_gp == 1)
       gm->AttachGP(dim_gp_coords, gp_coords_data, gpb_amd::parse_cov(str_or(cov_fct, "exponential"), cov_fct_shape),
                    seed);
@@ -239,10 +244,15 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
   // objective (optim_utils.h:656-657)
   (void)trace;
   (void)lr_coef; (void)acc_rate_coef;
-  if (GroupedModel* g = as_grouped(handle)) {   // Gaussian grouped model: no aux parameters, no coefficients
+  if (GroupedModel* g = as_grouped(handle)) {   // no coefficients; aux parameters for the gamma likelihood only
     (void)piv_chol_rank;
-    (void)num_covariates; (void)init_coef; (void)optimizer_coef; (void)init_aux_pars; (void)estimate_aux_pars;
-    (void)delta_conv_mode_finding;
+    (void)num_covariates; (void)init_coef; (void)optimizer_coef;
+    if (g->laplace()) {
+      g->SetPreconditioner(cg_preconditioner_type);
+      if (delta_conv_mode_finding > 0.) g->iter.delta_conv_mode_finding = delta_conv_mode_finding;
+      if (init_aux_pars != nullptr) g->SetInitAuxPars(init_aux_pars);
+      g->estimate_aux_pars = estimate_aux_pars;
+    }
     g->SetOptimSettings(init_cov_pars, lr, max_iter, delta_rel_conv, optimizer, m_lbfgs);
     g->SetInternalOptimSettings(acc_rate_cov, use_nesterov_acc, nesterov_schedule_version, momentum_offset,
                                 convergence_criterion);
@@ -566,8 +576,8 @@ int GPB_OptimCovParBoosting(REModelHandle handle, const double* y_data, const do
   // REModel::OptimCovPar(y, F, called_in_GPBoost_algorithm, reuse) (re_model.cpp:339-401)
   API_BEGIN();
   if (as_grouped(handle) != nullptr)
-    gpb_amd::Fatal("the GPBoost-algorithm covariance update is not supported for grouped random effects models by "
-                   "gpboost_amd");
+    gpb_amd::Fatal("the GPBoost-algorithm covariance update (GPB_OptimCovParBoosting) is not supported for grouped "
+                   "random effects models by gpboost_amd");
   model(handle)->OptimCovPar(y_data, fixed_effects, called_in_GPBoost_algorithm, reuse_learning_rates_from_previous_call);
   API_END();
 }
@@ -586,6 +596,12 @@ int GPB_CalcGradientF(REModelHandle handle, double* y, const double* fixed_effec
   // REModel::CalcGradient (re_model.cpp:667-680), the call the boosting objective makes
   // (regression_objective.hpp:164-179)
   API_BEGIN();
+  if (GroupedModel* g = as_grouped(handle)) {
+    if (g->laplace()) {
+      g->CalcGradientF(y, fixed_effects, calc_cov_factor);
+      return 0;
+    }
+  }
   model(handle)->CalcGradientF(y, fixed_effects, calc_cov_factor);
   API_END();
 }
@@ -654,6 +670,15 @@ int GPB_GetPivotedCholeskyInfo(REModelHandle handle, double* out, int* pivots) {
   API_END();
 }
 
+int GPB_GetGroupedLaplaceInfo(REModelHandle handle, int32_t* dims, int32_t* rowptr, int32_t* col, double* diag,
+                              double* vals) {
+  API_BEGIN();
+  GroupedModel* g = as_grouped(handle);
+  if (g == nullptr) gpb_amd::Fatal("GPB_GetGroupedLaplaceInfo: the model has no grouped random effects");
+  g->GetLaplaceInfo(dims, rowptr, col, diag, vals);
+  API_END();
+}
+
 int GPB_PivotedCholeskyHost(const double* coords, int n, int d, int cov_type, double var, double phi, int rank,
                             double tol, double* L, int* pivots, int* out_rank) {
   API_BEGIN();
@@ -688,10 +713,10 @@ int GPB_GetNumCGStepsTridiag(REModelHandle handle, int* num_cg_steps) {
 int GPB_SetLikelihood(REModelHandle handle, const char* likelihood) {
   API_BEGIN();
   if (likelihood == nullptr) gpb_amd::Fatal("likelihood is NULL");
-  if (as_grouped(handle) != nullptr) {
-    if (std::string(likelihood) != "gaussian")
-      gpb_amd::Fatal("grouped random effects with likelihood '%s' are not supported by gpboost_amd (supported: "
-                     "gaussian)", likelihood);
+  if (GroupedModel* g = as_grouped(handle)) {
+    if (std::string(likelihood) != g->likelihood())
+      gpb_amd::Fatal("changing the likelihood of a grouped random effects model ('%s' to '%s') is not supported by "
+                     "gpboost_amd (create a new model)", g->likelihood().c_str(), likelihood);
     return 0;
   }
   model(handle)->SetLikelihood(std::string(likelihood));
@@ -728,13 +753,18 @@ int GPB_SetOffsetData(REModelHandle handle, const double* fixed_effects) {
 
 int GPB_GetInitAuxPars(REModelHandle handle, double* aux_pars) {
   API_BEGIN();
+  if (GroupedModel* g = as_grouped(handle)) {
+    g->GetInitAuxPars(aux_pars);
+    return 0;
+  }
   model(handle)->GetInitAuxPars(aux_pars);
   API_END();
 }
 
 int GPB_GetLikelihoodName(REModelHandle handle, char* out_str, int* num_char) {
   API_BEGIN();
-  const std::string s = as_grouped(handle) != nullptr ? std::string("gaussian") : model(handle)->config().likelihood;
+  GroupedModel* g = as_grouped(handle);
+  const std::string s = g != nullptr ? g->likelihood() : model(handle)->config().likelihood;
   std::memcpy(out_str, s.c_str(), s.size() + 1);
   num_char[0] = (int)s.size() + 1;
   API_END();
@@ -742,15 +772,18 @@ int GPB_GetLikelihoodName(REModelHandle handle, char* out_str, int* num_char) {
 
 int GPB_GetNumAuxPars(REModelHandle handle, int* num_aux_pars) {
   API_BEGIN();
-  num_aux_pars[0] = as_grouped(handle) != nullptr ? 0 : model(handle)->num_aux_pars();
+  GroupedModel* g = as_grouped(handle);
+  num_aux_pars[0] = g != nullptr ? g->num_aux_pars() : model(handle)->num_aux_pars();
   API_END();
 }
 
 int GPB_GetAuxPars(REModelHandle handle, double* aux_pars, char* out_str) {
   API_BEGIN();
-  if (as_grouped(handle) != nullptr) {
-    (void)aux_pars;
-    if (out_str != nullptr) out_str[0] = '\0';
+  if (GroupedModel* g = as_grouped(handle)) {
+    const auto& a = g->aux_pars();
+    for (size_t k = 0; k < a.size(); ++k) aux_pars[k] = a[k];
+    const std::string name = g->aux_par_name();
+    if (out_str != nullptr) std::memcpy(out_str, name.c_str(), name.size() + 1);
     return 0;
   }
   REModelAMD* m = model(handle);

@@ -181,7 +181,7 @@ GroupedOp GroupedRE::Op(int t) {
   op.rowptr = d_rowptr_.get();
   op.split = d_split_.get();
   op.col = d_col_.get();
-  op.val = d_val_.get();
+  op.val = op_val_ != nullptr ? op_val_ : d_val_.get();
   op.tc = gre_tc(t);
   const ChunkPlan& pl = Plan(op.tc);
   GreChunks* ch[3] = {&op.full, &op.lower, &op.upper};
@@ -203,13 +203,13 @@ void GroupedRE::Diag(const double* tau) {
 }
 
 void GroupedRE::ApplyA(const double* X, double* Y, int t, bool with_sigma_inv) {
-  launch_gre_apply(Op(t), with_sigma_inv ? d_D_.get() : d_cnt_.get(), X, Y, t, s_);
+  launch_gre_apply(Op(t), with_sigma_inv ? OpD() : (op_cnt_ != nullptr ? op_cnt_ : d_cnt_.get()), X, Y, t, s_);
 }
 
 void GroupedRE::Precond(const double* R, double* Z, double* S, int t) {
   const GroupedOp op = Op(t);
   const ChunkPlan& pl = Plan(op.tc);
-  launch_gre_ssor(op, cum_, pl.lower_q, pl.upper_q, d_D_.get(), d_sqrtD_.get(), R, S, Z, t, s_);
+  launch_gre_ssor(op, cum_, pl.lower_q, pl.upper_q, OpD(), OpDis(), R, S, Z, t, s_);
 }
 
 // CGRandomEffectsVec (block = false; CG_utils.cpp:1100-1230) and CGTridiagRandomEffects (block =
@@ -299,6 +299,12 @@ void GroupedRE::CheckMethod(const double* tau, bool iterative) const {
 
 void GroupedRE::DenseFactor() {
   // A = Sigma^-1 + Z^T Z dense (diag(A) = D from Diag), in-place Cholesky, log|A|, the inverse factor
+  if (!DenseFactorOf(d_D_.get(), d_val_.get())) Fatal("the matrix Sigma^-1 + Z^T Z is not positive definite");
+  DenseSolve(d_zty_.get(), d_u_.get());
+  HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+bool GroupedRE::DenseFactorOf(const double* D, const double* val) {
   const int M = M_;
   if (ldM_ == 0) {
     ldM_ = (M + 63) / 64 * 64;
@@ -315,19 +321,48 @@ void GroupedRE::DenseFactor() {
   const int ld = ldM_;
   HIP_CHECK(hipMemsetAsync(dA_.get(), 0, sizeof(double) * (size_t)ld * ld, s_));
   HIP_CHECK(hipMemsetAsync(d_info_.get(), 0, sizeof(int), s_));
-  launch_gre_dense_build(M, ld, d_rowptr_.get(), d_col_.get(), d_val_.get(), d_D_.get(), dA_.get(), s_);
+  launch_gre_dense_build(M, ld, d_rowptr_.get(), d_col_.get(), val, D, dA_.get(), s_);
   chol_lower(s_, dA_.get(), dW_.get(), M, ld, d_info_.get());
   launch_logdet_chol(s_, dA_.get(), ld, M, d_out_.get() + kOut - 3);
   trtri_lower(s_, dA_.get(), dW_.get(), dX_.get(), 0, M, ld);
   fitc_lower_t(s_, dW_.get(), M, ld, dLiT_.get());
   launch_gre_inv_diag(M, ld, dW_.get(), d_invdiag_.get(), s_);
-  fitc_chol_solve(s_, dW_.get(), dLiT_.get(), d_zty_.get(), M, ld, d_tmpM_.get(), d_u_.get());
   int info = 0;
   HIP_CHECK(hipMemcpyAsync(&info, d_info_.get(), sizeof(int), hipMemcpyDeviceToHost, s_));
   HIP_CHECK(hipMemcpyAsync(h_out_ + kOut - 3, d_out_.get() + kOut - 3, sizeof(double), hipMemcpyDeviceToHost, s_));
   HIP_CHECK(hipStreamSynchronize(s_));
-  if (info != 0) Fatal("the matrix Sigma^-1 + Z^T Z is not positive definite");
   dense_logdet_ = h_out_[kOut - 3];
+  return info == 0;
+}
+
+void GroupedRE::DenseSolve(const double* rhs, double* sol) {
+  fitc_chol_solve(s_, dW_.get(), dLiT_.get(), rhs, M_, ldM_, d_tmpM_.get(), sol);
+}
+
+const double* GroupedRE::DenseInverse() {
+  // A^-1 = L^-T L^-1 = LiT LiT^T (L itself is not needed any more)
+  gemm_f64(s_, M_, M_, M_, 1., dLiT_.get(), ldM_, 0, dLiT_.get(), ldM_, 1, 0., dA_.get(), ldM_);
+  return dA_.get();
+}
+
+GroupedRE::View GroupedRE::view() const {
+  View v;
+  v.n = n_;
+  v.K = K_;
+  v.M = M_;
+  v.nnz = rowptr_h_[M_];
+  v.cum = &cum_;
+  v.rowptr_h = &rowptr_h_;
+  v.d_rowptr = d_rowptr_.get();
+  v.d_col = d_col_.get();
+  v.s = s_;
+  return v;
+}
+
+void GroupedRE::CheckDenseSize() const {
+  if (K_ > 1 && M_ > kDenseMaxM)
+    Fatal("matrix_inversion_method 'cholesky' with several grouped random effects: %d random effects exceed the "
+          "dense factor's limit of %d in gpboost_amd (use 'iterative')", M_, kDenseMaxM);
 }
 
 // u = A^-1 Z^T y (CalcYAux, re_model_template.h:8965-9003): K == 1 closed form (single_sums: the
@@ -383,11 +418,11 @@ void GroupedRE::Blup(const double* tau, bool iterative, bool warm, const Iterati
     }
 }
 
-void GroupedRE::PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out) {
+void GroupedRE::PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out, const double* D_k1) {
   if (np <= 0) return;
   if (K_ == 1) {   // A^-1 = diag(1/D)
     std::vector<double> D(M_);
-    HIP_CHECK(hipMemcpyAsync(D.data(), d_D_.get(), sizeof(double) * M_, hipMemcpyDeviceToHost, s_));
+    HIP_CHECK(hipMemcpyAsync(D.data(), D_k1 != nullptr ? D_k1 : d_D_.get(), sizeof(double) * M_, hipMemcpyDeviceToHost, s_));
     HIP_CHECK(hipStreamSynchronize(s_));
     if (want_cov) {
       for (int q = 0; q < np; ++q)
@@ -502,44 +537,8 @@ void GroupedRE::Eval(const double* tau, bool want_grad, bool iterative, bool war
   } else if (!iterative) {
     for (int k = 0; k < K_; ++k) logdet += sum_logD[k];   // 2 sum log sqrt(D) (re_model_template.h:2780)
   } else {
-    // ---- SLQ: probes r ~ N(0, I) (GenRandVecNormalParallel), P-distributed L D^-1/2 r, block PCG
     t = cfg.num_rand_vec_trace;
-    if (t < 1 || t > 1024) Fatal("num_rand_vec_trace = %d outside [1, 1024]", t);
-    if (!(probes_saved_ && probes_t_ == t)) {
-      std::vector<double> R((size_t)M_ * t);
-      gen_probes_normal(M_, t, cfg.seed_rand_vec_trace, probe_run_id_, R.data());
-      ++probe_run_id_;
-      d_probes_.alloc(R.size());
-      HIP_CHECK(hipMemcpyAsync(d_probes_.get(), R.data(), sizeof(double) * R.size(), hipMemcpyHostToDevice, s_));
-      HIP_CHECK(hipStreamSynchronize(s_));   // R is pageable and goes out of scope
-      probes_t_ = t;
-      probes_saved_ = cfg.reuse_rand_vec_trace;
-    }
-    d_probesP_.alloc((size_t)M_ * t);
-    launch_gre_lds_mult(Op(t), d_D_.get(), d_sqrtD_.get(), d_probes_.get(), d_probesP_.get(), t, s_);
-    const int pmax = std::max(1, std::min(cfg.cg_max_num_it_tridiag, M_));
-    Block& bt = GetBlock(1, t, pmax);
-    const int L = Pcg(bt, d_probesP_.get(), bt.U.get(), true, pmax, cfg.cg_delta_conv);
-    out.lanczos_steps = L;
-    std::vector<double> ah((size_t)L * t), bh((size_t)std::max(L - 1, 1) * t);
-    HIP_CHECK(hipMemcpyAsync(ah.data(), bt.a_hist.get(), sizeof(double) * ah.size(), hipMemcpyDeviceToHost, s_));
-    if (L > 1)
-      HIP_CHECK(hipMemcpyAsync(bh.data(), bt.b_hist.get(), sizeof(double) * (size_t)(L - 1) * t, hipMemcpyDeviceToHost,
-                               s_));
-    HIP_CHECK(hipStreamSynchronize(s_));
-    std::vector<std::vector<double>> Td(t), Ts(t);
-    for (int c = 0; c < t; ++c) {   // CG_utils.cpp:1383-1388 (a_old = 1, b_old = 0 before the first step)
-      Td[c].resize(L);
-      Ts[c].resize(L > 0 ? L - 1 : 0);
-      for (int j = 0; j < L; ++j) {
-        const double aj = ah[(size_t)j * t + c];
-        const double a_old = j > 0 ? ah[(size_t)(j - 1) * t + c] : 1.;
-        const double b_old = j > 0 ? bh[(size_t)(j - 1) * t + c] : 0.;
-        Td[c][j] = 1. / aj + b_old / a_old;
-        if (j > 0) Ts[c][j - 1] = std::sqrt(b_old) / a_old;
-      }
-    }
-    logdet = slq_logdet(Td, Ts, M_);
+    logdet = SlqLogdet(cfg, &out.lanczos_steps);
     for (int k = 0; k < K_; ++k) logdet += sum_logD[k];   // log|P| = 2 sum log(D sqrt(1/D)) (:2848-2851)
   }
   for (int k = 0; k < K_; ++k) logdet += m_[k] * std::log(tau[k]);   // log|Sigma| (:2868-2871)
@@ -573,11 +572,60 @@ void GroupedRE::Eval(const double* tau, bool want_grad, bool iterative, bool war
     out.trace[0] = (single_sums[0] - single_sums[1]) * tau[0];
     return;
   }
+  StochTraces(tau, sum_Dinv.data(), t, out.trace.data());
+}
+
+// SLQ of log|P^-1 A| (CGTridiagRandomEffects / LogDetStochTridiag): probes r ~ N(0, I), P-distributed L D^-1/2 r,
+// block PCG; leaves A^-1 z in the block's U and z in d_probesP_. log|P| = sum log D is added by the caller.
+double GroupedRE::SlqLogdet(const IterativeConfig& cfg, int* steps) {
+  // ---- SLQ: probes r ~ N(0, I) (GenRandVecNormalParallel), P-distributed L D^-1/2 r, block PCG
+  const int t = cfg.num_rand_vec_trace;
+  if (t < 1 || t > 1024) Fatal("num_rand_vec_trace = %d outside [1, 1024]", t);
+  if (!(probes_saved_ && probes_t_ == t)) {
+    std::vector<double> R((size_t)M_ * t);
+    gen_probes_normal(M_, t, cfg.seed_rand_vec_trace, probe_run_id_, R.data());
+    ++probe_run_id_;
+    d_probes_.alloc(R.size());
+    HIP_CHECK(hipMemcpyAsync(d_probes_.get(), R.data(), sizeof(double) * R.size(), hipMemcpyHostToDevice, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));   // R is pageable and goes out of scope
+    probes_t_ = t;
+    probes_saved_ = cfg.reuse_rand_vec_trace;
+  }
+  d_probesP_.alloc((size_t)M_ * t);
+  launch_gre_lds_mult(Op(t), OpD(), OpDis(), d_probes_.get(), d_probesP_.get(), t, s_);
+  const int pmax = std::max(1, std::min(cfg.cg_max_num_it_tridiag, M_));
+  Block& bt = GetBlock(1, t, pmax);
+  const int L = Pcg(bt, d_probesP_.get(), bt.U.get(), true, pmax, cfg.cg_delta_conv);
+  if (steps != nullptr) *steps = L;
+  std::vector<double> ah((size_t)L * t), bh((size_t)std::max(L - 1, 1) * t);
+  HIP_CHECK(hipMemcpyAsync(ah.data(), bt.a_hist.get(), sizeof(double) * ah.size(), hipMemcpyDeviceToHost, s_));
+  if (L > 1)
+    HIP_CHECK(hipMemcpyAsync(bh.data(), bt.b_hist.get(), sizeof(double) * (size_t)(L - 1) * t, hipMemcpyDeviceToHost,
+                             s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+  std::vector<std::vector<double>> Td(t), Ts(t);
+  for (int c = 0; c < t; ++c) {   // CG_utils.cpp:1383-1388 (a_old = 1, b_old = 0 before the first step)
+    Td[c].resize(L);
+    Ts[c].resize(L > 0 ? L - 1 : 0);
+    for (int j = 0; j < L; ++j) {
+      const double aj = ah[(size_t)j * t + c];
+      const double a_old = j > 0 ? ah[(size_t)(j - 1) * t + c] : 1.;
+      const double b_old = j > 0 ? bh[(size_t)(j - 1) * t + c] : 0.;
+      Td[c][j] = 1. / aj + b_old / a_old;
+      if (j > 0) Ts[c][j - 1] = std::sqrt(b_old) / a_old;
+    }
+  }
+  return slq_logdet(Td, Ts, M_);
+}
+
+// Stochastic tr(A^-1 dSigma^-1/dlog tau_k) + m_k per effect with the SSOR variance reduction (CalcOptimalC), on
+// the block solution and probes of the preceding SlqLogdet; leaves P^-1 z in d_PI_ and D^-1 (upper A) P^-1 z in d_DI_
+void GroupedRE::StochTraces(const double* tau, const double* sum_Dinv, int t, double* trace) {
   Block& bt = GetBlock(1, t, 1);
   d_PI_.alloc((size_t)M_ * t);
   d_DI_.alloc((size_t)M_ * t);
   Precond(d_probesP_.get(), d_PI_.get(), bt.S.get(), t);               // PI_RV = P^-1 z
-  launch_gre_upper(Op(t), d_D_.get(), d_PI_.get(), d_DI_.get(), t, s_);  // DI_L_plus_D_t_PI_RV
+  launch_gre_upper(Op(t), OpD(), d_PI_.get(), d_DI_.get(), t, s_);  // DI_L_plus_D_t_PI_RV
   std::vector<double> sums((size_t)3 * t * K_);
   d_sums3_.alloc((size_t)3 * t * K_);   // own scratch: M x t blocks can be smaller than 3 t (M < 3)
   for (int k = 0; k < K_; ++k) {
@@ -603,8 +651,33 @@ void GroupedRE::Eval(const double* tau, bool want_grad, bool iterative, bool war
     trP /= t;
     const double trD = -(sum_Dinv[k] * inv);
     const double copt = optimal_c(z1.data(), zP.data(), t, tr1, trP);
-    out.trace[k] = tr1 + copt * (trD - trP) + m_[k];
+    trace[k] = tr1 + copt * (trD - trP) + m_[k];
   }
+}
+
+void GroupedRE::SetOperator(const double* val, const double* cnt, const double* D, const double* dis) {
+  op_val_ = val;
+  op_cnt_ = cnt;
+  op_D_ = D;
+  op_dis_ = dis;
+}
+
+int GroupedRE::SolveVec(const double* rhs, double* U, int pmax, double delta, bool warm) {
+  Block& b1 = GetBlock(0, 1, std::max(pmax, 1));
+  return Pcg(b1, rhs, U, false, std::max(pmax, 1), delta, warm);
+}
+
+void GroupedRE::ApplyLower(const double* dg, const double* X, double* Y, int t) {
+  launch_gre_apply_lower(Op(t), dg, X, Y, t, s_);
+}
+
+void GroupedRE::ColDots(const double* A, const double* B, int t, double* host_out) {
+  const double* a[1] = {A};
+  const double* b[1] = {B};
+  d_sums3_.alloc((size_t)3 * t * K_);
+  launch_coldots(M_, t, 1, a, b, d_partials_.get(), d_sums3_.get(), s_);
+  HIP_CHECK(hipMemcpyAsync(host_out, d_sums3_.get(), sizeof(double) * t, hipMemcpyDeviceToHost, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
 }
 
 }  // namespace gpb_amd

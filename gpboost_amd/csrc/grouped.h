@@ -76,7 +76,8 @@ class GroupedRE {
   // (re_model_template.h:10350-10358, 10510-10522) with Z^T Z = A - Sigma^-1 collapses to
   // U - sum_k tau_k [same seen level] + e_p^T A^-1 e_q. K >= 2: E = Li [e_p] on the device (one wave per
   // point), variances ||E_p||^2, covariances E^T E on the MFMA GEMM; K == 1: A^-1 = diag(1/D).
-  void PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out);
+  // D_k1 (nullable, device, M): the diagonal of A for K == 1 when it is not the Gaussian model's own
+  void PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out, const double* D_k1 = nullptr);
   // Fisher information of the original-scale parameters [sigma^2, sigma_1^2 .. sigma_K^2] (cholesky;
   // CalcFisherInformation_Only_Grouped_REs_Woodbury re_model_template.h:9559-9651 with transf_scale =
   // false): with B = S^1/2 A^-1 S^1/2 (S = Sigma^-1 on the transformed scale), F_jk = ||B_jk||_F^2 and
@@ -87,6 +88,39 @@ class GroupedRE {
   void Fisher(const double* tau, double sigma2, double* FI);
   // the pieces of both forms: F (K x K, F_jk = ||B_jk||_F^2) and t_j = tr(B_jj)
   void FisherParts(const double* tau, std::vector<double>& F, std::vector<double>& tr);
+
+  // What the Laplace model of non-Gaussian likelihoods (grouped_laplace.h) borrows: the structure of Z^T Z and
+  // the dense factor, here for A = diag(D) + the off-diagonal values val in the CSR's entry order.
+  struct View {
+    int n = 0, K = 0, M = 0, nnz = 0;
+    const std::vector<int>* cum = nullptr;
+    const std::vector<int>* rowptr_h = nullptr;
+    const int* d_rowptr = nullptr;
+    const int* d_col = nullptr;
+    hipStream_t s = nullptr;
+  };
+  View view() const;
+  void CheckDenseSize() const;
+  // Cholesky factor, log|A|, the inverse factor and diag(A^-1) of the dense A; false: A not positive definite
+  bool DenseFactorOf(const double* D, const double* val);
+  void DenseSolve(const double* rhs, double* sol);   // sol = A^-1 rhs on the last factor
+  const double* DenseInverse();                      // A^-1 (column-major M x M, leading dimension dense_ld())
+  int dense_ld() const { return ldM_; }
+  double dense_logdet() const { return dense_logdet_; }
+  // Iterative pieces on a caller's operator A = diag(D) + offdiag(val) (dis = sqrt(1 / D), cnt = the diagonal of
+  // A - Sigma^-1; all null: the model's own Z^T Z): the SSOR-PCG solve of one vector (returns the iterations), the
+  // SLQ log-determinant and the stochastic traces (see their definitions), products with the lower triangle of
+  // diag(dg) + offdiag(val), and column dot products of two M x t blocks (host_out: t sums).
+  void SetOperator(const double* val, const double* cnt, const double* D, const double* dis);
+  int SolveVec(const double* rhs, double* U, int pmax, double delta, bool warm);
+  double SlqLogdet(const IterativeConfig& cfg, int* steps);
+  void StochTraces(const double* tau, const double* sum_Dinv, int t, double* trace);
+  void ApplyLower(const double* dg, const double* X, double* Y, int t);
+  void ApplyOffDiagPlus(const double* X, double* Y, int t) { ApplyA(X, Y, t, false); }   // (A - Sigma^-1) X
+  void ColDots(const double* A, const double* B, int t, double* host_out);
+  const double* slq_solution() { return bt_->U.get(); }   // A^-1 z (M x t) after SlqLogdet
+  const double* probes_pinv() const { return d_PI_.get(); }   // P^-1 z after StochTraces
+  const double* probes_dinv_upper() const { return d_DI_.get(); }
 
  private:
   struct Block {   // work space of a t-column PCG
@@ -121,6 +155,12 @@ class GroupedRE {
   // warm (single column only): U holds the initial guess, R = RHS - A U.
   int Pcg(Block& b, const double* RHS, double* U, bool block, int pmax, double delta, bool warm = false);
 
+  const double* op_val_ = nullptr;   // SetOperator
+  const double* op_cnt_ = nullptr;
+  const double* op_D_ = nullptr;
+  const double* op_dis_ = nullptr;
+  const double* OpD() const { return op_D_ != nullptr ? op_D_ : d_D_.get(); }
+  const double* OpDis() const { return op_dis_ != nullptr ? op_dis_ : d_sqrtD_.get(); }
   DevBuf<double> d_sums3_;   // 3 t K column sums of the trace terms
   int n_, K_, M_;
   hipStream_t s_;

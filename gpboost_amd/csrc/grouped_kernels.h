@@ -40,6 +40,8 @@ void launch_gre_diag(int K, const int* cum, const double* cnt, const double* tau
                      hipStream_t s);
 // Y = (diag(dg) + offdiag(Z^T Z)) X, t columns
 void launch_gre_apply(const GroupedOp& op, const double* dg, const double* X, double* Y, int t, hipStream_t s);
+// Y = (diag(dg) + strictly lower part of offdiag) X
+void launch_gre_apply_lower(const GroupedOp& op, const double* dg, const double* X, double* Y, int t, hipStream_t s);
 // Y = (L D^-1/2) R
 void launch_gre_lds_mult(const GroupedOp& op, const double* D, const double* dis, const double* R, double* Y, int t,
                          hipStream_t s);

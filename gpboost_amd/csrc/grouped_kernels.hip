@@ -233,6 +233,11 @@ void launch_gre_apply(const GroupedOp& op, const double* dg, const double* X, do
   combine_pass<kCombApply>(op.full, op.P, 0, op.M, t, dg, nullptr, X, Y, s);
 }
 
+void launch_gre_apply_lower(const GroupedOp& op, const double* dg, const double* X, double* Y, int t, hipStream_t s) {
+  chunk_pass<false>(op, op.lower, 0, op.lower.n, nullptr, X, t, s);
+  combine_pass<kCombApply>(op.lower, op.P, 0, op.M, t, dg, nullptr, X, Y, s);
+}
+
 void launch_gre_lds_mult(const GroupedOp& op, const double* D, const double* dis, const double* R, double* Y, int t,
                          hipStream_t s) {
   chunk_pass<true>(op, op.lower, 0, op.lower.n, dis, R, t, s);

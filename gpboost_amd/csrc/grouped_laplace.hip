@@ -1,0 +1,665 @@
+// GroupedLaplace: kernels and host driver (grouped_laplace.h).
+#include "grouped_laplace.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <utility>
+
+#include "lik_device.h"
+#include "slq_host.h"
+#include "wave_ops.h"
+
+namespace gpb_amd {
+
+namespace {
+
+constexpr int kMaxBlocks = 1024;      // blocks of an observation pass (grid-stride; fixed by n -> fixed sum order)
+constexpr int kShortLen = 32;         // destinations of at most this many observations: one thread each
+constexpr int kChunkLen = 512;        // chunk of a longer list: one wave, 8 observations per lane
+constexpr double kCArmijo = 1e-4;     // c_armijo_ (likelihoods.h:12737)
+constexpr int kMaxItNewton = 1000;    // maxit_mode_newton_ (:12721)
+constexpr int kMaxShrink = 20;        // max_number_lr_shrinkage_steps_newton_ (:12725)
+constexpr int kRed = 64;              // scalar slots
+
+struct EffArgs {   // per-effect constants, by value
+  int K;
+  int cum[kGlpMaxK + 1];
+  double sigi[kGlpMaxK];   // 1 / sigma_k^2
+};
+
+__device__ __forceinline__ int effect_of(const EffArgs& a, int r) {
+  int k = 0;
+  while (k + 1 < a.K && r >= a.cum[k + 1]) ++k;
+  return k;
+}
+
+// sum over the 256 threads of a block, in every thread (fixed order)
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+  v = lane_group_sum<64>(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __syncthreads();
+  return r;
+}
+
+// Observation pass: eta_i = F_i + sum_k b[lev_k(i)] (K gathers), the log-likelihood summed per block, and
+// (DERIV) d1, W and, when asked, dW / deta from the same read of y.
+template <bool DERIV>
+__global__ void __launch_bounds__(256) glp_obs_kernel(int n, int K, const int* __restrict__ glev,
+                                                      const double* __restrict__ y, const double* __restrict__ F,
+                                                      const double* __restrict__ b, int lik, double aux,
+                                                      double* __restrict__ d1, double* __restrict__ W,
+                                                      double* __restrict__ dW, double* __restrict__ partial) {
+  __shared__ double sh[4];
+  double ll = 0.;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    double eta = F != nullptr ? F[i] : 0.;
+    for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+    const double yi = y[i];
+    ll += lik_loglik(lik, aux, yi, eta);
+    if (DERIV) {
+      d1[i] = lik_d1(lik, aux, yi, eta);
+      W[i] = lik_info(lik, aux, yi, eta);
+      if (dW != nullptr) dW[i] = lik_dinfo(lik, aux, yi, eta);
+    }
+  }
+  ll = block_sum(ll, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = ll;
+}
+
+// out[c] = sum_j partial[c nb + j], one block per column
+__global__ void __launch_bounds__(256) glp_finish_kernel(int nb, const double* __restrict__ partial,
+                                                         double* __restrict__ out) {
+  __shared__ double sh[4];
+  double s = 0.;
+  for (int j = threadIdx.x; j < nb; j += 256) s += partial[(size_t)blockIdx.x * nb + j];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+// Segmented sums, short destinations: out[d] = sum of w over d's observations, in list order
+__global__ void __launch_bounds__(256) glp_seg_short_kernel(int ndst, const int* __restrict__ ptr,
+                                                            const int* __restrict__ obs, const double* __restrict__ w,
+                                                            double* __restrict__ out) {
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndst) return;
+  const int e0 = ptr[d], e1 = ptr[d + 1];
+  if (e1 - e0 > kShortLen) return;   // chunked
+  double s = 0.;
+  for (int e = e0; e < e1; ++e) s += w[obs[e]];
+  out[d] = s;
+}
+
+// long destinations, stage 1: one wave per chunk
+__global__ void __launch_bounds__(256) glp_seg_chunk_kernel(int nchunks, const int* __restrict__ c0,
+                                                            const int* __restrict__ c1, const int* __restrict__ obs,
+                                                            const double* __restrict__ w, double* __restrict__ P) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nchunks) return;   // wave-uniform
+  const int lane = threadIdx.x & 63;
+  double s = 0.;
+  const int e1 = c1[q];
+  for (int e = c0[q] + lane; e < e1; e += 64) s += w[obs[e]];
+  s = lane_group_sum<64>(s);
+  if (lane == 0) P[q] = s;
+}
+
+// stage 2: the chunk partials of a destination in chunk order
+__global__ void __launch_bounds__(256) glp_seg_long_kernel(int nlong, const int* __restrict__ dst,
+                                                           const int* __restrict__ cptr, const double* __restrict__ P,
+                                                           double* __restrict__ out) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= nlong) return;
+  double s = 0.;
+  for (int q = cptr[j]; q < cptr[j + 1]; ++q) s += P[q];
+  out[dst[j]] = s;
+}
+
+enum VecOp : int {
+  kVecDiag = 0,   // out = sigi + x                  (diag(A) from diag(Z^T W Z))
+  kVecRhs,        // out = x - sigi y                (Z^T d1 - Sigma^-1 b)
+  kVecDiv,        // out = x / y
+  kVecAxpy,       // out = x + alpha y
+  kVecInvSqrt,    // out = sqrt(1 / x)
+};
+template <int OP>
+__global__ void __launch_bounds__(256) glp_vec_kernel(int M, EffArgs a, double alpha, const double* __restrict__ x,
+                                                      const double* __restrict__ y, double* __restrict__ out) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= M) return;
+  if (OP == kVecDiag) out[r] = a.sigi[effect_of(a, r)] + x[r];
+  if (OP == kVecRhs) out[r] = x[r] - a.sigi[effect_of(a, r)] * y[r];
+  if (OP == kVecDiv) out[r] = x[r] / y[r];
+  if (OP == kVecAxpy) out[r] = x[r] + alpha * y[r];
+  if (OP == kVecInvSqrt) out[r] = sqrt(1. / x[r]);
+}
+
+// out[k] = sum over the rows of effect k of x y (MODE 1: of log x, 2: of 1 / x, 3: of x / y); one block per effect
+template <int MODE>
+__global__ void __launch_bounds__(256) glp_effect_dots_kernel(EffArgs a, const double* __restrict__ x,
+                                                              const double* __restrict__ y, double* __restrict__ out) {
+  __shared__ double sh[4];
+  const int k = blockIdx.x;
+  double s = 0.;
+  for (int r = a.cum[k] + threadIdx.x; r < a.cum[k + 1]; r += 256)
+    s += MODE == 1 ? log(x[r]) : MODE == 2 ? 1. / x[r] : MODE == 3 ? x[r] / y[r] : x[r] * y[r];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) out[k] = s;
+}
+
+// q_ij = sum_k A^-1[lev_j(i), lev_k(i)] (K^2 gathers from the dense inverse; K == 1: 1 / D), q_i = sum_j q_ij;
+// written: dwq_i = dW_i q_i / 2 and per block the sums of W_i q_ij (column j)
+__global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __restrict__ glev,
+                                                    const double* __restrict__ Ainv, int ld,
+                                                    const double* __restrict__ D, const double* __restrict__ W,
+                                                    const double* __restrict__ dW, double* __restrict__ dwq,
+                                                    double* __restrict__ partial) {
+  __shared__ double sh[4];
+  double tr[kGlpMaxK];
+#pragma unroll
+  for (int j = 0; j < kGlpMaxK; ++j) tr[j] = 0.;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    int g[kGlpMaxK];
+#pragma unroll
+    for (int k = 0; k < kGlpMaxK; ++k) g[k] = k < K ? glev[(size_t)k * n + i] : 0;
+    const double wi = W[i];
+    double qi = 0.;
+#pragma unroll
+    for (int j = 0; j < kGlpMaxK; ++j) {
+      if (j < K) {
+        double qj = 0.;
+        if (Ainv == nullptr) {
+          qj = 1. / D[g[0]];
+        } else {
+          for (int k = 0; k < K; ++k) qj += Ainv[(size_t)g[k] * ld + g[j]];
+        }
+        qi += qj;
+        tr[j] += wi * qj;
+      }
+    }
+    dwq[i] = 0.5 * dW[i] * qi;
+  }
+#pragma unroll
+  for (int j = 0; j < kGlpMaxK; ++j) {
+    if (j < K) {   // block-uniform
+      const double s = block_sum(tr[j], sh);
+      if (threadIdx.x == 0) partial[(size_t)j * gridDim.x + blockIdx.x] = s;
+    }
+  }
+}
+
+// iterative: dwq_i = dW_i mean_c[(Z U)_ic (Z V)_ic] / 2 from the M x t blocks U = A^-1 z and V = P^-1 z (row-major:
+// K gathered rows of t doubles per observation; no n x t matrix is formed)
+__global__ void __launch_bounds__(256) glp_row_trace_kernel(int n, int K, int t, const int* __restrict__ glev,
+                                                            const double* __restrict__ U, const double* __restrict__ V,
+                                                            const double* __restrict__ dW, double* __restrict__ dwq) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  size_t g[kGlpMaxK];
+#pragma unroll
+  for (int k = 0; k < kGlpMaxK; ++k) g[k] = k < K ? (size_t)glev[(size_t)k * n + i] * t : 0;
+  double acc = 0.;
+  for (int c = 0; c < t; ++c) {
+    double a = 0., p = 0.;
+#pragma unroll
+    for (int k = 0; k < kGlpMaxK; ++k) {
+      if (k < K) {
+        a += U[g[k] + c];
+        p += V[g[k] + c];
+      }
+    }
+    acc += a * p;
+  }
+  dwq[i] = 0.5 * dW[i] * (acc / t);
+}
+
+// gradient wrt the fixed effects: -d1_i + dW_i q_i / 2 - W_i (Z v)_i
+__global__ void __launch_bounds__(256) glp_grad_f_kernel(int n, int K, const int* __restrict__ glev,
+                                                         const double* __restrict__ d1, const double* __restrict__ dwq,
+                                                         const double* __restrict__ W, const double* __restrict__ v,
+                                                         double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double zv = 0.;
+  for (int k = 0; k < K; ++k) zv += v[glev[(size_t)k * n + i]];
+  out[i] = -d1[i] + dwq[i] - W[i] * zv;
+}
+
+inline int blocks_of(int count) { return (count + 255) / 256; }
+
+}  // namespace
+
+GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>>& levels, int lik)
+    : re_(re), v_(re->view()), lik_(lik), s_(v_.s) {
+  const int n = v_.n, K = v_.K, M = v_.M;
+  if (K > kGlpMaxK)
+    Fatal("non-Gaussian likelihoods with grouped random effects: at most %d grouping variables are supported by "
+          "gpboost_amd", kGlpMaxK);
+  const std::vector<int>& cum = *v_.cum;
+  nb_ = std::max(1, std::min(blocks_of(n), kMaxBlocks));
+  std::vector<int> glev((size_t)K * n);
+  for (int k = 0; k < K; ++k)
+    for (int i = 0; i < n; ++i) glev[(size_t)k * n + i] = cum[k] + levels[k][i];
+  // inverted index: the M levels (observations ascending), then the CSR slots of Z^T Z. The CSR holds the
+  // distinct (row, column) pairs in ascending order, so slot e is the e-th distinct key of the sorted pairs.
+  const int ND = M + v_.nnz;
+  std::vector<int> ptr(ND + 1, 0), obs;
+  obs.reserve((size_t)n * K * K);
+  {
+    std::vector<int> cnt(M, 0);
+    for (size_t e = 0; e < glev.size(); ++e) ++cnt[glev[e]];
+    for (int r = 0; r < M; ++r) ptr[r + 1] = ptr[r] + cnt[r];
+    obs.resize((size_t)n * K);
+    std::vector<int> fill(ptr.begin(), ptr.begin() + M);
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < n; ++i) obs[fill[glev[(size_t)k * n + i]]++] = i;
+  }
+  if (K > 1) {
+    std::vector<std::pair<int64_t, int>> pairs;
+    pairs.reserve((size_t)n * K * (K - 1));
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < K; ++k)
+        for (int l = 0; l < K; ++l)
+          if (k != l)
+            pairs.emplace_back((int64_t)glev[(size_t)k * n + i] * M + glev[(size_t)l * n + i], i);
+    std::sort(pairs.begin(), pairs.end());
+    int slot = 0;
+    for (size_t a = 0; a < pairs.size();) {
+      size_t b = a;
+      while (b < pairs.size() && pairs[b].first == pairs[a].first) obs.push_back(pairs[b++].second);
+      if (slot >= v_.nnz) Fatal("internal error: the inverted index does not match the CSR of Z^T Z");
+      ptr[M + slot + 1] = (int)obs.size();
+      ++slot;
+      a = b;
+    }
+    if (slot != v_.nnz) Fatal("internal error: the inverted index does not match the CSR of Z^T Z");
+  }
+  std::vector<int> c0, c1, long_dst, long_cptr(1, 0);
+  for (int d = 0; d < ND; ++d) {
+    if (d == M) {
+      n_long_diag_ = (int)long_dst.size();
+      n_chunks_diag_ = (int)c0.size();
+    }
+    if (ptr[d + 1] - ptr[d] <= kShortLen) continue;
+    for (int e = ptr[d]; e < ptr[d + 1]; e += kChunkLen) {
+      c0.push_back(e);
+      c1.push_back(std::min(e + kChunkLen, ptr[d + 1]));
+    }
+    long_dst.push_back(d);
+    long_cptr.push_back((int)c0.size());
+  }
+  if (ND == M) {
+    n_long_diag_ = (int)long_dst.size();
+    n_chunks_diag_ = (int)c0.size();
+  }
+  n_long_ = (int)long_dst.size();
+  n_chunks_ = (int)c0.size();
+  auto upload = [&](DevBuf<int>& dst, const std::vector<int>& src) {
+    dst.alloc(std::max<size_t>(src.size(), 1));
+    if (!src.empty())
+      HIP_CHECK(hipMemcpyAsync(dst.get(), src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice, s_));
+  };
+  upload(d_glev_, glev);
+  upload(d_seg_ptr_, ptr);
+  upload(d_seg_obs_, obs);
+  upload(d_c0_, c0);
+  upload(d_c1_, c1);
+  upload(d_long_dst_, long_dst);
+  upload(d_long_cptr_, long_cptr);
+  d_chunk_P_.alloc(std::max(n_chunks_, 1));
+  for (auto* b : {&d_y_, &d_d1_, &d_W_, &d_dW_, &d_dwq_}) b->alloc(n);
+  for (auto* b : {&d_mode_, &d_mode_new_, &d_mode_prev_, &d_upd_, &d_rhs_, &d_ztd1_, &d_D_, &d_dmll_, &d_vS_, &d_dis_})
+    b->alloc(M);
+  d_ztwz_.alloc(ND);
+  d_partial_.alloc((size_t)kMaxBlocks * kGlpMaxK);
+  d_red_.alloc(kRed);
+  HIP_CHECK(hipMemsetAsync(d_mode_.get(), 0, sizeof(double) * M, s_));
+  HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_red_), kRed * sizeof(double), hipHostMallocDefault));
+  for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
+  HIP_CHECK(hipStreamSynchronize(s_));   // the host vectors go out of scope
+}
+
+GroupedLaplace::~GroupedLaplace() {
+  if (h_red_) (void)hipHostFree(h_red_);
+  for (auto& e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+void GroupedLaplace::SetY(const double* y) {
+  const int n = v_.n;
+  // CheckY (likelihoods.h:637-737), CalculateLogNormalizingConstant (:8290-8310)
+  lognorm_ = 0.;
+  sum_log_y_ = 0.;
+  if (lik_ == kLikBernoulliLogit || lik_ == kLikBernoulliProbit) {
+    for (int i = 0; i < n; ++i)
+      if (y[i] != 0. && y[i] != 1.)
+        Fatal("The response variable ('y') needs to be 0 or 1 for likelihood = '%s' ",
+              lik_ == kLikBernoulliLogit ? "bernoulli_logit" : "bernoulli_probit");
+  } else if (lik_ == kLikGamma) {
+    for (int i = 0; i < n; ++i) {
+      if (y[i] <= 0.)
+        Fatal(" Must have y > 0 for the response variable ('y') for likelihood = 'gamma', found %g ", y[i]);
+      sum_log_y_ += std::log(y[i]);
+    }
+  } else if (lik_ == kLikPoisson) {
+    for (int i = 0; i < n; ++i) {
+      if (y[i] < 0.) Fatal(" Must have y >= 0 for the response variable ('y') for likelihood = 'poisson', found %g ", y[i]);
+      double ip;
+      if (std::modf(y[i], &ip) != 0.)
+        Fatal("Found non-integer response variable ('y'). Response variable can only be integer valued for likelihood = "
+              "'poisson' ");
+      for (int k = 2; k <= (int)y[i]; ++k) lognorm_ -= std::log((double)k);
+    }
+  }
+  HIP_CHECK(hipMemcpyAsync(d_y_.get(), y, sizeof(double) * n, hipMemcpyHostToDevice, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+  y_set_ = true;
+}
+
+void GroupedLaplace::SetOffset(const double* offset) {
+  has_off_ = offset != nullptr;
+  if (!has_off_) return;
+  d_off_.alloc(v_.n);
+  HIP_CHECK(hipMemcpyAsync(d_off_.get(), offset, sizeof(double) * v_.n, hipMemcpyHostToDevice, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+double GroupedLaplace::LogLikConst(double aux) const {
+  if (lik_ == kLikPoisson) return lognorm_;
+  if (lik_ == kLikGamma)   // likelihoods.h:8181-8191
+    return (aux - 1.) * sum_log_y_ + v_.n * (aux * std::log(aux) - std::lgamma(aux));
+  return 0.;
+}
+
+void GroupedLaplace::Assemble(const double* w, double* out, bool diag_only) {
+  const int ndst = diag_only ? v_.M : v_.M + v_.nnz;
+  const int nchunks = diag_only ? n_chunks_diag_ : n_chunks_;
+  const int nlong = diag_only ? n_long_diag_ : n_long_;
+  glp_seg_short_kernel<<<blocks_of(ndst), 256, 0, s_>>>(ndst, d_seg_ptr_.get(), d_seg_obs_.get(), w, out);
+  if (nchunks > 0) {
+    glp_seg_chunk_kernel<<<(nchunks + 3) / 4, 256, 0, s_>>>(nchunks, d_c0_.get(), d_c1_.get(), d_seg_obs_.get(), w,
+                                                            d_chunk_P_.get());
+    glp_seg_long_kernel<<<blocks_of(nlong), 256, 0, s_>>>(nlong, d_long_dst_.get(), d_long_cptr_.get(),
+                                                          d_chunk_P_.get(), out);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+namespace {
+EffArgs make_eff(const GroupedRE::View& v, const double* sigma2) {
+  EffArgs a{};
+  a.K = v.K;
+  for (int k = 0; k <= v.K; ++k) a.cum[k] = (*v.cum)[k];
+  for (int k = 0; k < v.K; ++k) a.sigi[k] = 1. / sigma2[k];
+  return a;
+}
+}  // namespace
+
+double GroupedLaplace::Objective(const double* mode, double aux, const double* sigi) {
+  const int n = v_.n, K = v_.K;
+  glp_obs_kernel<false><<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr, mode,
+                                             lik_, aux, nullptr, nullptr, nullptr, d_partial_.get());
+  glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get());
+  EffArgs a{};
+  a.K = K;
+  for (int k = 0; k <= K; ++k) a.cum[k] = (*v_.cum)[k];
+  glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(a, mode, mode, d_red_.get() + 1);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h_red_, d_red_.get(), sizeof(double) * (1 + K), hipMemcpyDeviceToHost, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+  double quad = 0.;
+  for (int k = 0; k < K; ++k) quad += sigi[k] * h_red_[1 + k];
+  return h_red_[0] + LogLikConst(aux) - 0.5 * quad;
+}
+
+void GroupedLaplace::Deriv(const double* mode, double aux, bool want_dw) {
+  glp_obs_kernel<true><<<nb_, 256, 0, s_>>>(v_.n, v_.K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr,
+                                            mode, lik_, aux, d_d1_.get(), d_W_.get(), want_dw ? d_dW_.get() : nullptr,
+                                            d_partial_.get());
+  HIP_CHECK(hipGetLastError());
+}
+
+GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, const IterativeConfig& cfg, bool iterative,
+                                          bool want_grad, bool want_aux_grad, double* grad_f, Start start) {
+  const double delta_conv = cfg.delta_conv_mode_finding;
+  constexpr double kCgDeltaConvPred = 1e-3;   // cg_delta_conv_pred_ (re_model_template.h:5370)
+  if (!y_set_) Fatal("response variable y has not been set");
+  const int n = v_.n, K = v_.K, M = v_.M;
+  const std::vector<int>& cum = *v_.cum;
+  for (int k = 0; k < K; ++k)
+    if (!(sigma2[k] > 0.)) Fatal("covariance parameters must be > 0");
+  if (lik_ == kLikGamma && !(aux > 0.)) Fatal("the shape parameter of the gamma likelihood must be > 0");
+  if (iterative && K < 2) Fatal("iterative methods need several grouped random effects");
+  if (K > 1 && !iterative) re_->CheckDenseSize();
+  const EffArgs ea = make_eff(v_, sigma2);
+  GroupedLaplaceResult res;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  auto fail = [&]() {
+    res.nan = true;
+    res.nll = nan;
+    evaluated_ = false;
+    return res;
+  };
+
+  if (start == Start::kZero) {
+    HIP_CHECK(hipMemsetAsync(d_mode_.get(), 0, sizeof(double) * M, s_));
+  } else if (start == Start::kWarm) {
+    HIP_CHECK(hipMemcpyAsync(d_mode_prev_.get(), d_mode_.get(), sizeof(double) * M, hipMemcpyDeviceToDevice, s_));
+    mode_prev_valid_ = true;
+  }
+  // diag(A), the weighted off-diagonal values and (K >= 2) the dense factor at the current mode's W
+  static const bool timing = std::getenv("GPBOOST_AMD_TIMING") != nullptr;   // HIP events around the last steps
+  auto factor = [&]() -> bool {
+    if (timing) HIP_CHECK(hipEventRecord(ev_[0], s_));
+    Assemble(d_W_.get(), d_ztwz_.get(), false);
+    if (timing) HIP_CHECK(hipEventRecord(ev_[1], s_));
+    glp_vec_kernel<kVecDiag><<<blocks_of(M), 256, 0, s_>>>(M, ea, 0., d_ztwz_.get(), nullptr, d_D_.get());
+    HIP_CHECK(hipGetLastError());
+    if (iterative) {   // the SSOR preconditioner's D^-1/2 and the weighted operator of GroupedRE's PCG
+      glp_vec_kernel<kVecInvSqrt><<<blocks_of(M), 256, 0, s_>>>(M, ea, 0., d_D_.get(), nullptr, d_dis_.get());
+      HIP_CHECK(hipGetLastError());
+      re_->SetOperator(d_ztwz_.get() + M, d_ztwz_.get(), d_D_.get(), d_dis_.get());
+      return true;
+    }
+    if (K > 1) return re_->DenseFactorOf(d_D_.get(), d_ztwz_.get() + M);
+    return true;
+  };
+  struct OperatorGuard {   // GroupedRE's own Z^T Z back when the evaluation ends
+    GroupedRE* re;
+    ~OperatorGuard() { re->SetOperator(nullptr, nullptr, nullptr, nullptr); }
+  } guard{re_};
+  // warm (iterative): out holds the initial guess
+  auto solve = [&](const double* rhs, double* out, bool warm, double delta) -> int {
+    if (iterative) return re_->SolveVec(rhs, out, cfg.cg_max_num_it, delta, warm);
+    if (K > 1) {
+      re_->DenseSolve(rhs, out);
+    } else {
+      glp_vec_kernel<kVecDiv><<<blocks_of(M), 256, 0, s_>>>(M, ea, 0., rhs, d_D_.get(), out);
+      HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+  };
+
+  // ---- mode finding (likelihoods.h:1995-2088 / 2224-2274)
+  double mll = Objective(d_mode_.get(), aux, ea.sigi);
+  const int newton_its = start == Start::kKeep ? 0 : kMaxItNewton;
+  for (int it = 0; it < newton_its; ++it) {
+    if (timing) HIP_CHECK(hipEventRecord(ev_[2], s_));
+    Deriv(d_mode_.get(), aux, false);
+    Assemble(d_d1_.get(), d_ztd1_.get(), true);
+    glp_vec_kernel<kVecRhs><<<blocks_of(M), 256, 0, s_>>>(M, ea, 0., d_ztd1_.get(), d_mode_.get(), d_rhs_.get());
+    if (!factor()) return fail();
+    const int its = solve(d_rhs_.get(), d_upd_.get(), it > 0, cfg.cg_delta_conv);
+    if (it == 0) res.cg_its = its;
+    glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_upd_.get(), d_rhs_.get(), d_red_.get() + 16);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_ + 16, d_red_.get() + 16, sizeof(double) * K, hipMemcpyDeviceToHost, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+    double gdd = 0.;   // grad_dot_direction (rhs = gradient of the objective)
+    for (int k = 0; k < K; ++k) gdd += h_red_[16 + k];
+    double lr = 1., mll_new = mll;
+    for (int ih = 0; ih < kMaxShrink; ++ih) {
+      glp_vec_kernel<kVecAxpy><<<blocks_of(M), 256, 0, s_>>>(M, ea, lr, d_mode_.get(), d_upd_.get(), d_mode_new_.get());
+      mll_new = Objective(d_mode_new_.get(), aux, ea.sigi);
+      if (mll_new < mll + kCArmijo * lr * gdd || std::isnan(mll_new) || std::isinf(mll_new)) lr *= 0.5;
+      else break;
+    }
+    std::swap(d_mode_, d_mode_new_);
+    if (timing) HIP_CHECK(hipEventRecord(ev_[3], s_));
+    res.newton_its = it + 1;
+    if (std::isnan(mll_new) || std::isinf(mll_new)) return fail();
+    // CheckConvergenceModeFinding (:11820-11870)
+    const bool term = it == 0 ? std::fabs(mll_new - mll) < delta_conv * std::fabs(mll)
+                              : (mll_new - mll) < delta_conv * std::fabs(mll);
+    mll = mll_new;
+    if (term) break;
+  }
+  // ---- derivatives, information and factor at the mode; the determinant (:2089-2193 / 2275-2289)
+  Deriv(d_mode_.get(), aux, want_grad);
+  glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get() + 32);   // ll at the mode (aux gradient)
+  if (!factor()) return fail();
+  double logdet = 0.;
+  if (iterative) {   // SLQ of log|P^-1 A| + log|P|, log|P| = sum log D (:2155-2169)
+    logdet = re_->SlqLogdet(cfg, &res.lanczos_steps);
+    glp_effect_dots_kernel<1><<<K, 256, 0, s_>>>(ea, d_D_.get(), nullptr, d_red_.get() + 33);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_ + 32, d_red_.get() + 32, sizeof(double) * (1 + K), hipMemcpyDeviceToHost, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+    for (int k = 0; k < K; ++k) logdet += h_red_[33 + k];
+  } else if (K > 1) {
+    logdet = re_->dense_logdet();
+    HIP_CHECK(hipMemcpyAsync(h_red_ + 32, d_red_.get() + 32, sizeof(double), hipMemcpyDeviceToHost, s_));
+  } else {
+    glp_effect_dots_kernel<1><<<1, 256, 0, s_>>>(ea, d_D_.get(), nullptr, d_red_.get() + 33);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_ + 32, d_red_.get() + 32, sizeof(double) * 2, hipMemcpyDeviceToHost, s_));
+  }
+  HIP_CHECK(hipStreamSynchronize(s_));
+  if (K == 1) logdet = h_red_[33];
+  if (!std::isfinite(logdet)) return fail();
+  const double ll_mode = h_red_[32];
+  double sum_log_sigi = 0.;
+  for (int k = 0; k < K; ++k) sum_log_sigi += (cum[k + 1] - cum[k]) * std::log(ea.sigi[k]);
+  res.nll = -(mll - 0.5 * logdet + 0.5 * sum_log_sigi);
+  if (timing && newton_its > 0 && res.newton_its > 0) {
+    HIP_CHECK(hipEventElapsedTime(&res.ms_assembly, ev_[0], ev_[1]));
+    HIP_CHECK(hipEventElapsedTime(&res.ms_newton_step, ev_[2], ev_[3]));
+    std::fprintf(stderr, "[grouped laplace] %d Newton steps, %d CG its in the first, %d Lanczos steps; last weighted "
+                 "assembly %.3f ms, last Newton step %.3f ms\n", res.newton_its, res.cg_its, res.lanczos_steps,
+                 res.ms_assembly, res.ms_newton_step);
+  }
+  if (!std::isfinite(res.nll)) return fail();
+  evaluated_ = true;
+  if (!want_grad) return res;
+
+  // ---- gradient (:3634-3740 / 3791-3853)
+  std::vector<double> tr_iter(K, 0.);
+  double aux_det = 0.;   // iterative: d log|A| / dlog shape
+  if (iterative) {
+    const int t = cfg.num_rand_vec_trace;
+    glp_effect_dots_kernel<2><<<K, 256, 0, s_>>>(ea, d_D_.get(), nullptr, d_red_.get() + 40);
+    glp_effect_dots_kernel<3><<<K, 256, 0, s_>>>(ea, d_ztwz_.get(), d_D_.get(), d_red_.get() + 48);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_ + 40, d_red_.get() + 40, sizeof(double) * 16, hipMemcpyDeviceToHost, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+    std::vector<double> sum_Dinv(h_red_ + 40, h_red_ + 40 + K);
+    double tr_dinv_w = 0.;   // tr(D^-1 diag(Z^T W Z))
+    for (int k = 0; k < K; ++k) tr_dinv_w += h_red_[48 + k];
+    // m_j + tr(A^-1 dSigma^-1/dlog sigma_j^2) = tr(A^-1 I_j Z^T W Z) (:3565-3582)
+    re_->StochTraces(sigma2, sum_Dinv.data(), t, tr_iter.data());
+    const double* U = re_->slq_solution();
+    const double* PI = re_->probes_pinv();
+    const double* DI = re_->probes_dinv_upper();
+    glp_row_trace_kernel<<<blocks_of(n), 256, 0, s_>>>(n, K, t, d_glev_.get(), U, PI, d_dW_.get(), d_dwq_.get());
+    HIP_CHECK(hipGetLastError());
+    if (lik_ == kLikGamma && want_aux_grad) {
+      // dW/dlog shape = W: tr(A^-1 Z^T W Z) by the probes, its SSOR control variate with the lower triangle of
+      // Z^T W Z (:3607-3625)
+      const size_t mt = (size_t)M * t;
+      d_blkA_.alloc(mt);
+      d_blkB_.alloc(mt);
+      std::vector<double> z1(t), zP(t), tmp(t);
+      re_->ApplyOffDiagPlus(PI, d_blkA_.get(), t);
+      re_->ColDots(U, d_blkA_.get(), t, z1.data());
+      re_->ApplyLower(d_ztwz_.get(), DI, d_blkB_.get(), t);
+      re_->ColDots(PI, d_blkB_.get(), t, zP.data());
+      re_->ColDots(DI, d_blkB_.get(), t, tmp.data());
+      double tr1 = 0., trP = 0.;
+      for (int c = 0; c < t; ++c) {
+        zP[c] = 2. * zP[c] - tmp[c];
+        tr1 += z1[c];
+        trP += zP[c];
+      }
+      tr1 /= t;
+      trP /= t;
+      aux_det = tr1 + optimal_c(z1.data(), zP.data(), t, tr1, trP) * (tr_dinv_w - trP);
+    }
+  } else {
+    const double* Ainv = K > 1 ? re_->DenseInverse() : nullptr;
+    glp_q_kernel<<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(), d_dW_.get(),
+                                      d_dwq_.get(), d_partial_.get());
+    glp_finish_kernel<<<K, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get());   // sum_i W_i q_ij
+    HIP_CHECK(hipGetLastError());
+  }
+  Assemble(d_dwq_.get(), d_dmll_.get(), true);                                 // d_mll_d_mode
+  solve(d_dmll_.get(), d_vS_.get(), false, kCgDeltaConvPred);                  // v = A^-1 d_mll_d_mode
+  Assemble(d_d1_.get(), d_ztd1_.get(), true);
+  glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_vS_.get(), d_ztd1_.get(), d_red_.get() + kGlpMaxK);
+  glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_mode_.get(), d_mode_.get(), d_red_.get() + 2 * kGlpMaxK);
+  HIP_CHECK(hipGetLastError());
+  if (grad_f != nullptr) {
+    d_gradf_.alloc(n);
+    glp_grad_f_kernel<<<blocks_of(n), 256, 0, s_>>>(n, K, d_glev_.get(), d_d1_.get(), d_dwq_.get(), d_W_.get(),
+                                                    d_vS_.get(), d_gradf_.get());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(grad_f, d_gradf_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
+  }
+  HIP_CHECK(hipMemcpyAsync(h_red_, d_red_.get(), sizeof(double) * 3 * kGlpMaxK, hipMemcpyDeviceToHost, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+  double tr_all = 0., imp_all = 0.;
+  for (int j = 0; j < K; ++j) {
+    const double tr = iterative ? tr_iter[j] : h_red_[j], imp = h_red_[kGlpMaxK + j], bb = h_red_[2 * kGlpMaxK + j];
+    res.grad.push_back(-0.5 * bb * ea.sigi[j] + 0.5 * tr + imp);
+    tr_all += tr;
+    imp_all += imp;
+  }
+  if (lik_ == kLikGamma && want_aux_grad) {
+    // shape on the log scale (:3720-3739, 10508-10524): -dll/dlog a = -ll - a n (log a + 1 - digamma(a)) - a sum log y
+    // with ll = -a sum (eta + y e^-eta); dW/dlog a = W and dd1/dlog a = d1
+    const double neg = -ll_mode - aux * (n * (std::log(aux) + 1. - digamma_asa103(aux)) + sum_log_y_);
+    res.grad.push_back(neg + 0.5 * (iterative ? aux_det : tr_all) + imp_all);
+  }
+  for (double g : res.grad)
+    if (!std::isfinite(g)) res.nan = true;
+  return res;
+}
+
+void GroupedLaplace::ResetModeToPrevious() {
+  if (!mode_prev_valid_) return;
+  HIP_CHECK(hipMemcpyAsync(d_mode_.get(), d_mode_prev_.get(), sizeof(double) * v_.M, hipMemcpyDeviceToDevice, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+void GroupedLaplace::GetMode(double* b) {
+  HIP_CHECK(hipMemcpyAsync(b, d_mode_.get(), sizeof(double) * v_.M, hipMemcpyDeviceToHost, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+void GroupedLaplace::PredVar(int np, const std::vector<int>& idx, double* out) {
+  if (!evaluated_) Fatal("predictive variances need an evaluation of the Laplace approximation first");
+  re_->PredCov(np, idx, false, out, v_.K == 1 ? d_D_.get() : nullptr);
+}
+
+void GroupedLaplace::GetZtWZ(double* diag, double* vals) {
+  if (!evaluated_) Fatal("Z^T W Z is available after an evaluation of the Laplace approximation");
+  HIP_CHECK(hipMemcpyAsync(diag, d_ztwz_.get(), sizeof(double) * v_.M, hipMemcpyDeviceToHost, s_));
+  if (v_.nnz > 0)
+    HIP_CHECK(hipMemcpyAsync(vals, d_ztwz_.get() + v_.M, sizeof(double) * v_.nnz, hipMemcpyDeviceToHost, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+}  // namespace gpb_amd

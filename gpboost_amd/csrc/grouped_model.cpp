@@ -2,7 +2,9 @@
 // device sums into the negative log-likelihood and its gradient, and the L-BFGS fit.
 #include "grouped_model.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <limits>
 #include <unordered_map>
@@ -31,12 +33,13 @@ std::vector<std::vector<int>> parse_group_levels(int n, int K, const char* re_gr
 }
 
 GroupedModel::GroupedModel(int n, const std::vector<std::vector<int>>& levels, const std::string& mim, int seed,
-                           std::vector<std::unordered_map<std::string, int>> label_index)
-    : n_(n), mim_(mim), levels_(levels), label_index_(std::move(label_index)) {
+                           std::vector<std::unordered_map<std::string, int>> label_index, const std::string& likelihood)
+    : n_(n), mim_(mim), likelihood_(likelihood), levels_(levels), label_index_(std::move(label_index)) {
   (void)seed;   // grouped models draw no random numbers at construction (probes use seed_rand_vec_trace)
   if (n <= 0) Fatal("num_data must be > 0");
   const int K = (int)levels.size();
   if (K < 1) Fatal("num_re_group must be > 0");
+  lik_ = parse_likelihood(likelihood_);
   if (mim_ == "default") mim_ = K > 1 ? "iterative" : "cholesky";
   if (mim_ != "iterative" && mim_ != "cholesky")
     Fatal("Matrix inversion method '%s' is not supported.", mim_.c_str());
@@ -56,9 +59,17 @@ GroupedModel::GroupedModel(int n, const std::vector<std::vector<int>>& levels, c
   UseDevice();
   HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   re_.reset(new GroupedRE(n, levels, stream_));
+  if (lik_ != kLikGaussian) {
+    lap_.reset(new GroupedLaplace(re_.get(), levels, lik_));
+    if (lik_ == kLikGamma) {
+      aux_pars_ = {1.};   // aux_pars_ = {1.} until set or estimated (likelihoods.h:219-222)
+      init_aux_pars_ = {-1.};
+    }
+  }
 }
 
 GroupedModel::~GroupedModel() {
+  lap_.reset();
   re_.reset();
   if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -66,6 +77,9 @@ GroupedModel::~GroupedModel() {
 void GroupedModel::UseDevice() const { HIP_CHECK(hipSetDevice(device_)); }
 
 void GroupedModel::AttachGP(int d, const double* coords_colmajor, int cov_type, int seed) {
+  if (laplace())
+    Fatal("a Gaussian process beside grouped random effects (gp_coords with group_data) is not supported for "
+          "likelihood '%s' by gpboost_amd", likelihood_.c_str());
   if (d < 1 || d > 3) Fatal("dim_gp_coords = %d is not supported by gpboost_amd's dense path (1..3)", d);
   if (coords_colmajor == nullptr) Fatal("gp_coords_data is NULL");
   if (re_->K() > 8) Fatal("GP + grouped random effects: at most 8 grouped effects are supported by gpboost_amd");
@@ -119,6 +133,15 @@ void GroupedModel::SetResponseAndOffset(const double* y, const double* fixed_eff
   }
   if (y != nullptr) y_raw_.assign(y, y + n_);
   if (y_raw_.empty()) Fatal("response variable y has not been set");
+  if (laplace()) {   // F is the offset of the location parameter, not a shift of y
+    for (int i = 0; i < n_; ++i)
+      if (std::isnan(y_raw_[i]) || std::isinf(y_raw_[i])) Fatal("NaN or Inf in response variable / label ");
+    UseDevice();
+    if (y != nullptr) lap_->SetY(y_raw_.data());
+    lap_->SetOffset(fixed_effects);
+    y_set_ = true;
+    return;
+  }
   y_ = y_raw_;
   if (fixed_effects != nullptr)
     for (int i = 0; i < n_; ++i) y_[i] -= fixed_effects[i];
@@ -142,6 +165,14 @@ EvalResult GroupedModel::Eval(const double* cov_pars_orig, bool want_grad, int p
   const int P = num_cov_pars();
   for (int k = 0; k < P; ++k)
     if (!(cov_pars_orig[k] > 0.)) Fatal("covariance parameters must be > 0");
+  if (laplace()) {   // an explicit evaluation starts the mode finding from zero (InitializeModeAvec)
+    if (profile)
+      Fatal("profile_sigma2 is not available for likelihood '%s': there is no error variance to profile out",
+            likelihood_.c_str());
+    EvalResult r = EvalLaplace(cov_pars_orig, want_grad, GroupedLaplace::Start::kZero, /*fatal_on_nan=*/true);
+    last_cov_pars_.assign(cov_pars_orig, cov_pars_orig + P);
+    return r;
+  }
   std::vector<double> trafo(P);   // TransformCovPars (re_comp.h: sigma_k^2 / sigma^2; the GP range transform)
   ToTrafo(cov_pars_orig, trafo.data());
   EvalResult r = EvalTrafo(trafo.data(), want_grad, profile);
@@ -226,6 +257,9 @@ void GroupedModel::SetOptimSettings(const double* init_cov_pars, double lr, int 
                                     const char* optimizer, int m_lbfgs) {
   if (optimizer != nullptr && optimizer[0] != '\0') {
     const std::string o(optimizer);
+    if (laplace() && o != "lbfgs")
+      Fatal("Optimizer option '%s' is not supported for covariance parameters of grouped random effects with "
+            "likelihood '%s' by gpboost_amd (supported: lbfgs)", optimizer, likelihood_.c_str());
     if (o != "lbfgs" && o != "nelder_mead" && !is_internal_optimizer(o))
       Fatal("Optimizer option '%s' is not supported for covariance parameters by gpboost_amd (supported: lbfgs, "
             "gradient_descent, fisher_scoring, nelder_mead)", optimizer);
@@ -354,6 +388,10 @@ std::vector<double> GroupedModel::FisherTrafo(const double* trafo) {
 
 void GroupedModel::OptimCovPar(const double* y, const double* fixed_effects) {
   UseDevice();
+  if (laplace()) {
+    OptimCovParLaplace(y, fixed_effects);
+    return;
+  }
   if (y == nullptr && y_raw_.empty()) Fatal("response variable y has not been set");
   SetResponseAndOffset(y != nullptr ? y : y_raw_.data(), fixed_effects);
   const int P = num_cov_pars();
@@ -459,6 +497,22 @@ void GroupedModel::PredictTrainingDataRandomEffects(const double* cov_pars, cons
   if (calc_var && iterative())
     Fatal("PredictTrainingDataRandomEffects() is currently not implemented for matrix_inversion_method_ == '%s' and "
           "likelihood == 'Gaussian'. Call the predict() function instead.", mim_.c_str());
+  if (laplace()) {   // the mode at the parameters, found from zero; means only
+    if (calc_var)
+      Fatal("variances (predict_var / calc_var) of the training-data random effects are not supported for likelihood "
+            "'%s' with grouped random effects by gpboost_amd (call predict() with predict_var)", likelihood_.c_str());
+    const std::vector<double> cp = LaplaceCovPars(cov_pars);
+    if (y != nullptr || fixed_effects != nullptr) SetResponseAndOffset(y, fixed_effects);
+    EvalLaplace(cp.data(), false, GroupedLaplace::Start::kZero, true);
+    std::vector<double> b(re_->M());
+    lap_->GetMode(b.data());
+    int off = 0;
+    for (int k = 0; k < K; ++k) {
+      for (int i = 0; i < n_; ++i) out[(size_t)k * n_ + i] = b[off + levels_[k][i]];
+      off += re_->levels_per_effect()[k];
+    }
+    return;
+  }
   std::vector<double> var;
   const std::vector<double> b = Blup(cov_pars, y, fixed_effects, calc_var ? &var : nullptr);
   const std::vector<int>& cum_m = re_->levels_per_effect();
@@ -481,6 +535,14 @@ void GroupedModel::Predict(const double* y, int n_pred, const char* re_group_dat
     return;
   }
   if (gp_coords_pred != nullptr) Fatal("gp_coords_pred given for a model without a Gaussian process");
+  if (laplace()) {
+    if (predict_cov_mat)
+      Fatal("predictive covariance matrices (predict_cov_mat) are not supported for likelihood '%s' with grouped "
+            "random effects by gpboost_amd (use predict_var)", likelihood_.c_str());
+    PredictLaplace(y, n_pred, re_group_data_pred, cov_pars, predict_var, predict_response, fixed_effects,
+                   fixed_effects_pred, out);
+    return;
+  }
   if ((predict_cov_mat || predict_var) && iterative())
     Fatal("predictive (co)variances for grouped random effects with matrix_inversion_method = 'iterative' (the "
           "reference's simulation-based estimate) are not supported by gpboost_amd (use 'cholesky')");
@@ -618,6 +680,9 @@ void GroupedModel::PredictCombined(const double* y, int n_pred, const char* re_g
 }
 
 void GroupedModel::StdDevCovPars(const double* cov_pars, double* sd) {
+  if (laplace())
+    Fatal("standard deviations of covariance parameters (std_err) are not supported for likelihood '%s' with "
+          "grouped random effects by gpboost_amd", likelihood_.c_str());
   if (has_gp())
     Fatal("standard deviations of covariance parameters for GP + grouped random effects models are not "
           "supported by gpboost_amd");
@@ -659,6 +724,234 @@ void GroupedModel::StdDevCovPars(const double* cov_pars, double* sd) {
     }
   }
   for (int k = 0; k < P; ++k) sd[k] = std::sqrt(inv[(size_t)k * P + k]);
+}
+
+// ---- non-Gaussian likelihoods (GroupedLaplace)
+
+std::vector<double> GroupedModel::LaplaceCovPars(const double* cov_pars) const {
+  const int K = re_->K();
+  std::vector<double> cp;
+  if (cov_pars != nullptr) cp.assign(cov_pars, cov_pars + K);
+  else if (!last_cov_pars_.empty()) cp = last_cov_pars_;
+  else Fatal("Covariance parameters have not been estimated or correctly set ");
+  for (double v : cp)
+    if (!(v > 0.)) Fatal("covariance parameters must be > 0");
+  return cp;
+}
+
+void GroupedModel::SetInitAuxPars(const double* aux) {
+  if (aux_pars_.empty() || aux == nullptr) return;
+  if (!(aux[0] > 0.)) Fatal("init_aux_pars must be > 0");
+  aux_pars_[0] = aux[0];
+  init_aux_pars_[0] = aux[0];
+  aux_pars_set_ = true;
+}
+
+void GroupedModel::GetInitAuxPars(double* aux) const {
+  for (size_t k = 0; k < init_aux_pars_.size(); ++k) aux[k] = init_aux_pars_[k];
+}
+
+EvalResult GroupedModel::EvalLaplace(const double* sigma2, bool want_grad, GroupedLaplace::Start start,
+                                     bool fatal_on_nan, double* grad_f) {
+  if (!y_set_) Fatal("response variable y has not been set");
+  UseDevice();
+  const bool with_aux = !aux_pars_.empty() && estimate_aux_pars;
+  const double aux = aux_pars_.empty() ? 1. : aux_pars_[0];
+  GroupedLaplaceResult r = lap_->Eval(sigma2, aux, iter, iterative(), want_grad, with_aux, grad_f, start);
+  last_cg_its_ = r.cg_its;
+  last_lanczos_ = r.lanczos_steps;
+  if (r.nan && fatal_on_nan)
+    Fatal("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
+  EvalResult res;
+  res.nll = r.nll;
+  res.sigma2 = 1.;
+  res.grad = r.grad;
+  last_nll_ = res.nll;
+  return res;
+}
+
+namespace {
+
+// EvalLLforLBFGSpp for the Laplace model: x = log(sigma_1^2 .. sigma_K^2 [, shape]). Every likelihood evaluation
+// continues from the previous mode (mode_initialized_, likelihoods.h:1985-1991) and computes the gradient only when the
+// caller asks for or announces it; a gradient-only call at the point just evaluated uses that evaluation's mode as it
+// stands (eval_likelihood = false, optim_utils.h:314-330), as LatentObjective (optim.cpp) does.
+class GroupedLaplaceObjective : public LbfgsObjective {
+ public:
+  GroupedLaplaceObjective(GroupedModel* m, int K, bool with_aux) : m_(m), K_(K), with_aux_(with_aux) {}
+  double Eval(const std::vector<double>& x, std::vector<double>& grad, bool eval_ll, bool calc_grad,
+              bool hint_grad) override {
+    if (eval_ll || !(has_grad_ && x == x_)) {
+      std::vector<double> s2(K_);
+      for (int k = 0; k < K_; ++k) s2[k] = std::exp(x[k]);
+      if (with_aux_) {
+        const double aux = std::exp(x[K_]);
+        m_->SetAuxPars(&aux);
+      }
+      const bool grad_only = !eval_ll && has_x_ && x == x_;
+      EvalResult r = m_->EvalLaplace(s2.data(), calc_grad || hint_grad,
+                                     grad_only ? GroupedLaplace::Start::kKeep : GroupedLaplace::Start::kWarm,
+                                     /*fatal_on_nan=*/false);
+      has_x_ = true;
+      bool bad = !std::isfinite(r.nll);
+      for (double g : r.grad) bad = bad || !std::isfinite(g);
+      if (bad) m_->ResetLaplaceModeToPrevious();   // EvalLLforLBFGSpp, optim_utils.h:349-360
+      x_ = x;
+      nll_ = r.nll;
+      has_grad_ = calc_grad || hint_grad;
+      if (has_grad_) {
+        grad_ = r.grad;
+        grad_.resize(x.size(), std::numeric_limits<double>::quiet_NaN());
+      }
+    }
+    if (calc_grad) grad = grad_;
+    return nll_;
+  }
+
+ private:
+  GroupedModel* m_;
+  int K_;
+  bool with_aux_;
+  std::vector<double> x_, grad_;
+  double nll_ = 0.;
+  bool has_grad_ = false, has_x_ = false;
+};
+
+}  // namespace
+
+void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effects) {
+  if (y == nullptr && y_raw_.empty()) Fatal("response variable y has not been set");
+  const std::vector<double> yraw(y != nullptr ? y : y_raw_.data(), (y != nullptr ? y : y_raw_.data()) + n_);
+  SetResponseAndOffset(yraw.data(), fixed_effects);
+  const int K = re_->K();
+  num_iter_ = 0;
+  // FindInitCovPar for non-Gaussian data (re_model_template.h:4440-4451): marginal variance 1 / num_comps each
+  std::vector<double> s2(K, 1. / K);
+  if (cov_pars_initialized_) s2 = cov_pars_orig_;
+  else init_used_ = s2;
+  const bool with_aux = !aux_pars_.empty() && estimate_aux_pars;
+  if (with_aux && !aux_pars_set_) {
+    // FindInitialAuxPars, gamma (likelihoods.h:1116-1145): approximate MLE of the shape ignoring the random
+    // effects, s = log(mean y e^-F) - mean(log y - F), k = (3 - s + sqrt((s - 3)^2 + 24 s)) / (12 s)
+    double log_avg = 0., avg_log = 0.;
+    for (int i = 0; i < n_; ++i) {
+      const double f = fixed_effects != nullptr ? fixed_effects[i] : 0.;
+      log_avg += fixed_effects != nullptr ? yraw[i] / std::exp(f) : yraw[i];
+      avg_log += fixed_effects != nullptr ? std::log(yraw[i]) - f : std::log(yraw[i]);
+    }
+    log_avg = std::log(log_avg / n_);
+    avg_log /= n_;
+    const double sv = log_avg - avg_log;
+    aux_pars_[0] = (3. - sv + std::sqrt((sv - 3.) * (sv - 3.) + 24. * sv)) / (12. * sv);
+    aux_pars_set_ = true;
+  }
+  if (optim_.max_iterations <= 0) {
+    num_it_ = 0;
+    cov_pars_orig_ = s2;
+    cov_pars_initialized_ = true;
+    last_cov_pars_ = cov_pars_orig_;
+    return;
+  }
+  std::vector<double> x(K);
+  for (int k = 0; k < K; ++k) x[k] = std::log(s2[k]);
+  if (with_aux) x.push_back(std::log(aux_pars_[0]));
+  double fx = 0.;
+  lap_->ClearModePrevious();
+  GroupedLaplaceObjective obj(this, K, with_aux);
+  num_it_ = lbfgs_minimize(obj, x, fx, optim_);
+  for (double v : x)
+    if (std::isnan(v) || std::isinf(v))
+      Fatal("NaN or Inf occurred in covariance parameter optimization using 'lbfgs' (the reference's nelder_mead "
+            "restart is not supported by gpboost_amd)");
+  cov_pars_orig_.assign(K, 0.);
+  for (int k = 0; k < K; ++k) cov_pars_orig_[k] = std::exp(x[k]);
+  if (with_aux) aux_pars_[0] = std::exp(x[K]);
+  cov_pars_initialized_ = true;
+  last_nll_ = fx;
+  last_cov_pars_ = cov_pars_orig_;
+}
+
+void GroupedModel::CalcGradientF(double* y, const double* fixed_effects, bool calc_cov_factor) {
+  if (y == nullptr) Fatal("the output array 'y' is NULL");
+  if (!y_set_) Fatal("Response variable data has not been set");
+  const int K = re_->K();
+  if (last_cov_pars_.empty()) {   // InitializeCovParsIfNotDefined (re_model.cpp:1142-1164)
+    last_cov_pars_ = cov_pars_initialized_ ? cov_pars_orig_ : std::vector<double>(K, 1. / K);
+  }
+  SetResponseAndOffset(nullptr, fixed_effects);   // null: the offset stays as it is, as in Predict
+  std::vector<double> g(n_);
+  const std::vector<double> cp = last_cov_pars_;
+  EvalLaplace(cp.data(), true, calc_cov_factor ? GroupedLaplace::Start::kWarm : GroupedLaplace::Start::kKeep, true,
+              g.data());
+  std::copy(g.begin(), g.end(), y);
+}
+
+void GroupedModel::GetLaplaceInfo(int* dims, int* rowptr, int* col, double* diag, double* vals) {
+  if (!laplace()) Fatal("GPB_GetGroupedLaplaceInfo: the model has a Gaussian likelihood");
+  UseDevice();
+  const GroupedRE::View v = re_->view();
+  if (dims != nullptr) {
+    dims[0] = v.M;
+    dims[1] = v.nnz;
+  }
+  if (rowptr != nullptr) std::copy(v.rowptr_h->begin(), v.rowptr_h->end(), rowptr);
+  if (col != nullptr && v.nnz > 0) {
+    HIP_CHECK(hipMemcpy(col, v.d_col, sizeof(int) * v.nnz, hipMemcpyDeviceToHost));
+  }
+  if (diag != nullptr && vals != nullptr) lap_->GetZtWZ(diag, vals);
+}
+
+void GroupedModel::PredictLaplace(const double* y, int n_pred, const char* re_group_data_pred, const double* cov_pars,
+                                  bool predict_var, bool predict_response, const double* fixed_effects,
+                                  const double* fixed_effects_pred, double* out) {
+  // PredictLaplaceApproxGroupedRE (likelihoods.h:5696-5953) / ...OnlyOneGroupedRECalculationsOnREScale (:5973-6032):
+  // latent mean = sum_k mode_k[level] (0 for a level not in the training data); latent variance = sum_k sigma_k^2
+  // [level not seen] + e_p^T A^-1 e_p, e_p the indicator of p's seen levels (the posterior covariance of the
+  // random effects is A^-1 at the mode); then the likelihood's response moments
+  if (n_pred <= 0) Fatal("num_data_pred must be > 0");
+  if (re_group_data_pred == nullptr) Fatal("re_group_data_pred must be provided for grouped random effects");
+  const int K = re_->K();
+  if ((int)label_index_.size() != K) Fatal("the model has no label index (created without re_group_data)");
+  const std::vector<double> cp = LaplaceCovPars(cov_pars);
+  if (y != nullptr || fixed_effects != nullptr) SetResponseAndOffset(y, fixed_effects);
+  if (!y_set_) Fatal("Response variable data is not provided and has not been set before");
+  EvalLaplace(cp.data(), false, GroupedLaplace::Start::kZero, true);
+  std::vector<double> b(re_->M());
+  lap_->GetMode(b.data());
+  std::vector<int> idx((size_t)n_pred * K, -1);
+  std::vector<double> mu(n_pred, 0.);
+  const char* p = re_group_data_pred;
+  int off = 0;
+  for (int k = 0; k < K; ++k) {
+    for (int i = 0; i < n_pred; ++i) {
+      std::string label(p);
+      p += label.size() + 1;
+      auto it = label_index_[k].find(label);
+      if (it != label_index_[k].end()) {
+        mu[i] += b[off + it->second];
+        idx[(size_t)i * K + k] = off + it->second;
+      }
+    }
+    off += re_->levels_per_effect()[k];
+  }
+  for (int i = 0; i < n_pred; ++i) mu[i] += fixed_effects_pred ? fixed_effects_pred[i] : 0.;
+  const bool want_var = predict_var || predict_response;
+  if (want_var && iterative())
+    Fatal("predict_response needs the predictive variances, which for grouped random effects with "
+          "matrix_inversion_method = 'iterative' (the reference's simulation-based estimate) are not supported by "
+          "gpboost_amd (use 'cholesky' or predict_response = false)");
+  std::vector<double> var(n_pred, 0.);
+  if (want_var) {
+    lap_->PredVar(n_pred, idx, var.data());
+    for (int i = 0; i < n_pred; ++i)
+      for (int k = 0; k < K; ++k)
+        if (idx[(size_t)i * K + k] < 0) var[i] += cp[k];
+  }
+  if (predict_response)
+    response_transform(lik_, aux_pars_.empty() ? 1. : aux_pars_[0], 0., iter.delta_conv_mode_finding, stream_, n_pred,
+                       mu.data(), var.data(), nullptr);
+  std::copy(mu.begin(), mu.end(), out);
+  if (predict_var) std::copy(var.begin(), var.end(), out + n_pred);
 }
 
 }  // namespace gpb_amd

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "grouped.h"
+#include "grouped_laplace.h"
 #include "optim.h"
 #include "re_model.h"
 
@@ -25,8 +26,13 @@ class GroupedModel {
   // levels: K x n level indices (order of first appearance, as RECompGroup numbers its labels,
   // re_comp.h:245-264). matrix_inversion_method: "default" -> "iterative" for K >= 2, "cholesky"
   // for K == 1 (UseIterativeByDefault, re_model_template.h:6719-6724).
+  // likelihood other than "gaussian" (bernoulli_logit, bernoulli_probit, poisson, gamma): the Laplace
+  // approximation of GroupedLaplace (grouped_laplace.h) for K == 1 and for K >= 2 with "cholesky"; there is no
+  // error term then, the parameters are [sigma_1^2 .. sigma_K^2] on both scales, and gamma's shape is the
+  // auxiliary parameter.
   GroupedModel(int n, const std::vector<std::vector<int>>& levels, const std::string& matrix_inversion_method,
-               int seed, std::vector<std::unordered_map<std::string, int>> label_index = {});
+               int seed, std::vector<std::unordered_map<std::string, int>> label_index = {},
+               const std::string& likelihood = "gaussian");
   ~GroupedModel();
   // Combined model (re_model_template.h:236-239 allows grouped random effects beside a GP for
   // gp_approx = "none"): one dense GP component on coords (host column-major n x d, as GPB_CreateREModel passes
@@ -38,7 +44,28 @@ class GroupedModel {
 
   int n() const { return n_; }
   int K() const { return re_->K(); }
-  int num_cov_pars() const { return 1 + re_->K() + (has_gp() ? 2 : 0); }
+  int num_cov_pars() const { return laplace() ? re_->K() : 1 + re_->K() + (has_gp() ? 2 : 0); }
+  bool laplace() const { return lap_ != nullptr; }
+  const std::string& likelihood() const { return likelihood_; }
+  int num_aux_pars() const { return (int)aux_pars_.size(); }
+  const std::vector<double>& aux_pars() const { return aux_pars_; }
+  std::string aux_par_name() const { return aux_pars_.empty() ? "" : "shape"; }
+  void SetInitAuxPars(const double* aux);
+  void GetInitAuxPars(double* aux) const;
+  bool estimate_aux_pars = true;
+  // GPB_CalcGradientF for non-Gaussian likelihoods (re_model_template.h:3021-3043): the gradient of the
+  // Laplace-approximated nll wrt the fixed effects F at the current covariance parameters, written to y.
+  // calc_cov_factor = false keeps the mode of the last evaluation. fixed_effects null keeps the offset of the last call
+  // that gave y or an offset (the rule of every call without y and offset, Predict included). Laplace models only.
+  void CalcGradientF(double* y, const double* fixed_effects, bool calc_cov_factor);
+  // test hook (GPB_GetGroupedLaplaceInfo): dims = [M, nnz]; the CSR of the off-diagonal part of Z^T Z and the
+  // diagonal / off-diagonal values of Z^T W Z of the last evaluation (each nullable)
+  void GetLaplaceInfo(int* dims, int* rowptr, int* col, double* diag, double* vals);
+  // the objective of the L-BFGS fit: x = log(sigma_1^2 .. sigma_K^2 [, shape])
+  EvalResult EvalLaplace(const double* sigma2, bool want_grad, GroupedLaplace::Start start, bool fatal_on_nan,
+                         double* grad_f = nullptr);
+  void SetAuxPars(const double* aux) { aux_pars_[0] = aux[0]; aux_pars_set_ = true; }
+  void ResetLaplaceModeToPrevious() { lap_->ResetModeToPrevious(); }
   const std::string& matrix_inversion_method() const { return mim_; }
   bool iterative() const { return mim_ == "iterative"; }
   std::string cg_preconditioner_type() const { return iterative() ? "ssor" : ""; }
@@ -99,7 +126,7 @@ class GroupedModel {
   // CalcFisherInformation_Only_Grouped_REs_Woodbury :9559-9651): sqrt(diag(FI^-1)) at the original-scale
   // cov_pars; cholesky only (the iterative branch is a stochastic estimate: refused)
   void StdDevCovPars(const double* cov_pars, double* sd);
-  bool CanCalculateStandardErrorsCovPars() const { return !iterative() && !has_gp(); }
+  bool CanCalculateStandardErrorsCovPars() const { return !iterative() && !has_gp() && !laplace(); }
   IterativeConfig iter;
 
  private:
@@ -123,6 +150,17 @@ class GroupedModel {
   std::string mim_;
   hipStream_t stream_ = nullptr;
   std::unique_ptr<GroupedRE> re_;
+  // non-Gaussian likelihood
+  std::unique_ptr<GroupedLaplace> lap_;
+  std::string likelihood_ = "gaussian";
+  int lik_ = 0;
+  std::vector<double> aux_pars_, init_aux_pars_;
+  bool aux_pars_set_ = false;
+  void OptimCovParLaplace(const double* y, const double* fixed_effects);
+  void PredictLaplace(const double* y, int n_pred, const char* re_group_data_pred, const double* cov_pars,
+                      bool predict_var, bool predict_response, const double* fixed_effects,
+                      const double* fixed_effects_pred, double* out);
+  std::vector<double> LaplaceCovPars(const double* cov_pars) const;
   std::vector<std::vector<int>> levels_;                       // K x n
   std::vector<std::unordered_map<std::string, int>> label_index_;   // label -> level, per effect
   std::vector<double> y_raw_, y_;

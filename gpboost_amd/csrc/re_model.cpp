@@ -877,42 +877,48 @@ void REModelAMD::PredictFitc(const double* y, int n_pred, const double* coords_p
 // PredictResponse (likelihoods.h:7526-7580) on the latent predictive mean / variance (n_pred each, in place):
 // bernoulli_logit by the adaptive Gauss-Hermite rule on the GPU, bernoulli_probit / poisson in closed form,
 // gaussian (vecchia_latent) + the error variance (also on the covariance diagonal, cov nullable).
-void REModelAMD::ResponseTransform(int n_pred, double* mean, double* var, double* cov) {
-  if (cfg_.lik == kLikBernoulliLogit) {
+void response_transform(int lik, double aux_shape, double aux_gauss, double delta_conv, hipStream_t stream, int n_pred,
+                        double* mean, double* var, double* cov) {
+  if (lik == kLikBernoulliLogit) {
     static const std::vector<double> gh = gauss_hermite_adaptive(30);   // order_GH_ = 30 (likelihoods.h:12877)
     DevBuf<double> dmv((size_t)2 * n_pred), dgh(gh.size()), dout((size_t)2 * n_pred);
-    HIP_CHECK(hipMemcpyAsync(dmv.get(), mean, sizeof(double) * n_pred, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipMemcpyAsync(dmv.get() + n_pred, var, sizeof(double) * n_pred, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipMemcpyAsync(dgh.get(), gh.data(), sizeof(double) * gh.size(), hipMemcpyHostToDevice, stream_));
-    launch_resp_logit(n_pred, dmv.get(), dmv.get() + n_pred, dgh.get(), dgh.get() + 30, 30, iter.delta_conv_mode_finding,
-                      dout.get(), dout.get() + n_pred, stream_);
-    HIP_CHECK(hipMemcpyAsync(mean, dout.get(), sizeof(double) * n_pred, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(var, dout.get() + n_pred, sizeof(double) * n_pred, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-  } else if (cfg_.lik == kLikBernoulliProbit) {   // :7531-7543
+    HIP_CHECK(hipMemcpyAsync(dmv.get(), mean, sizeof(double) * n_pred, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(dmv.get() + n_pred, var, sizeof(double) * n_pred, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(dgh.get(), gh.data(), sizeof(double) * gh.size(), hipMemcpyHostToDevice, stream));
+    launch_resp_logit(n_pred, dmv.get(), dmv.get() + n_pred, dgh.get(), dgh.get() + 30, 30, delta_conv,
+                      dout.get(), dout.get() + n_pred, stream);
+    HIP_CHECK(hipMemcpyAsync(mean, dout.get(), sizeof(double) * n_pred, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(var, dout.get() + n_pred, sizeof(double) * n_pred, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  } else if (lik == kLikBernoulliProbit) {   // :7531-7543
     for (int p = 0; p < n_pred; ++p) {
       mean[p] = 0.5 * std::erfc(-(mean[p] / std::sqrt(1. + var[p])) * M_SQRT1_2);
       var[p] = mean[p] * (1. - mean[p]);
     }
-  } else if (cfg_.lik == kLikGamma) {   // :7571-7584
-    const double a = aux_pars_.empty() ? 1. : aux_pars_[0];
+  } else if (lik == kLikGamma) {   // :7571-7584
+    const double a = aux_shape;
     for (int p = 0; p < n_pred; ++p) {
       const double pm = std::exp(mean[p] + 0.5 * var[p]);
       var[p] = (std::exp(var[p]) - 1.) * pm * pm + std::exp(2 * mean[p] + 2 * var[p]) / a;
       mean[p] = pm;
     }
-  } else if (cfg_.lik == kLikPoisson) {   // :7557-7569
+  } else if (lik == kLikPoisson) {   // :7557-7569
     for (int p = 0; p < n_pred; ++p) {
       const double pm = std::exp(mean[p] + 0.5 * var[p]);
       var[p] = pm * ((std::exp(var[p]) - 1.) * pm + 1.);
       mean[p] = pm;
     }
   } else {   // gaussian vecchia_latent: + the error variance
-    const double aux = aux_pars_.empty() ? 0. : aux_pars_[0];
+    const double aux = aux_gauss;
     for (int p = 0; p < n_pred; ++p) var[p] += aux;
     if (cov != nullptr)
       for (int p = 0; p < n_pred; ++p) cov[(size_t)p * n_pred + p] += aux;
   }
+}
+
+void REModelAMD::ResponseTransform(int n_pred, double* mean, double* var, double* cov) {
+  response_transform(cfg_.lik, aux_pars_.empty() ? 1. : aux_pars_[0], aux_pars_.empty() ? 0. : aux_pars_[0],
+                     iter.delta_conv_mode_finding, stream_, n_pred, mean, var, cov);
 }
 
 // FITC with a Laplace likelihood (CalcPredFITC_FSA, re_model_template.h:10600-10760, then

@@ -52,6 +52,10 @@ struct ModelConfig {
 };
 
 int parse_likelihood(const std::string& name);   // LatentLik code
+// PredictResponse (likelihoods.h:7526-7580) on latent predictive means / variances (host, n_pred each, in place);
+// aux_shape: gamma's shape, aux_gauss: the error variance of the latent Gaussian likelihood (cov nullable)
+void response_transform(int lik, double aux_shape, double aux_gauss, double delta_conv, hipStream_t stream, int n_pred,
+                        double* mean, double* var, double* cov);
 // cov_fcts.h:438-460: range rho -> phi on the transformed scale
 // cov_fcts.h:2753-2770 ParseCovFunctionAlias (+ shape) -> kMatern05 / kMatern15 / kMatern25 / kGaussian
 int parse_cov(const std::string& name, double shape);

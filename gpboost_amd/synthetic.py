@@ -245,3 +245,47 @@ def bench_grouped_y(groups: np.ndarray, sd=(1.0, 0.5), noise_sd: float = 1.0) ->
         b = sd[k % len(sd)] * _normal(m, 0.31 + 0.1 * k, 0.57 + 0.1 * k)
         y = y + b[groups[:, k]]
     return y
+
+
+def _grouped_eta(groups: np.ndarray, sd=(1.0, 0.5)) -> np.ndarray:
+    """eta = sum_k b_k[g_k], b_k ~ N(0, sd_k^2) per level (the level effects of bench_grouped_y)."""
+    n, K = groups.shape
+    eta = np.zeros(n)
+    for k in range(K):
+        m = int(groups[:, k].max()) + 1
+        b = sd[k % len(sd)] * _normal(m, 0.31 + 0.1 * k, 0.57 + 0.1 * k)
+        eta = eta + b[groups[:, k]]
+    return eta
+
+
+def bench_grouped_bernoulli_y(groups: np.ndarray, sd=(1.0, 0.5)) -> np.ndarray:
+    """y = 1[u < 1 / (1 + exp(-eta))], eta the grouped level effects, u from LCG c=0.19341."""
+    eta = _grouped_eta(groups, sd)
+    return (lcg_unif(groups.shape[0], 0.19341) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+
+
+def bench_grouped_poisson_y(groups: np.ndarray, sd=(1.0, 0.5)) -> np.ndarray:
+    """Counts with log-rate 0.5 + eta, drawn by inversion of the Poisson CDF at u from LCG c=0.27183."""
+    n = groups.shape[0]
+    lam = np.exp(0.5 + _grouped_eta(groups, sd))
+    u = lcg_unif(n, 0.27183)
+    k = np.zeros(n)
+    p = np.exp(-lam)
+    cdf = p.copy()
+    active = u > cdf
+    while active.any():
+        k[active] += 1.0
+        p[active] *= lam[active] / k[active]
+        cdf[active] += p[active]
+        active &= (u > cdf) & (k < 1000.0)
+    return k
+
+
+def bench_grouped_gamma_y(groups: np.ndarray, shape: int = 2, sd=(1.0, 0.5)) -> np.ndarray:
+    """Gamma responses with integer shape and mean exp(eta): exp(eta) / shape times a sum of `shape`
+    exponentials -log u_j, u_j from LCG streams c = 0.31415 + 0.1 j."""
+    n = groups.shape[0]
+    g = np.zeros(n)
+    for j in range(int(shape)):
+        g -= np.log(np.maximum(lcg_unif(n, 0.31415 + 0.1 * j), 1e-300))
+    return np.exp(_grouped_eta(groups, sd)) * g / int(shape)

@@ -23,7 +23,17 @@
  * "vecchia_latent" with "gaussian" (Laplace approximation, iterative methods); linear regression
  * covariates for the Gaussian likelihood (GLS, optimizer_coef "wls"); OR grouped random effects
  * (num_gp = 0, re_group_data with num_re_group >= 1 grouping variables, Gaussian likelihood; K = 1
- * closed form, K >= 2 iterative SSOR-PCG + SLQ as the reference's default). Latent models accept
+ * closed form, K >= 2 iterative SSOR-PCG + SLQ as the reference's default). Grouped handles also accept
+ * likelihood "bernoulli_logit", "bernoulli_probit", "poisson" and "gamma" (Laplace approximation on
+ * A = Sigma^-1 + Z^T W Z: K = 1 closed form per level, K >= 2 "iterative" (the default: SSOR-PCG Newton solves,
+ * SLQ, stochastic traces; cg_* / num_rand_vec_trace / seed_rand_vec_trace / reuse_rand_vec_trace honoured) or
+ * "cholesky" (dense factor). Such a model has no error term: cov_pars =
+ * [sigma_1^2 .. sigma_K^2]; gamma's shape is its auxiliary parameter (init_aux_pars / estimate_aux_pars of
+ * GPB_SetOptimConfig, GPB_GetAuxPars). GPB_EvalNegLogLikelihood[Grad], GPB_OptimCovPar (optimizer "lbfgs"),
+ * GPB_CalcGradientF, GPB_PredictREModel (latent and response means and variances, unseen labels) and
+ * GPB_PredictREModelTrainingDataRandomEffects (means) serve them; fixed_effects is the offset of the location
+ * parameter. Refused: a GP beside the grouped effects, profile_sigma2, standard deviations of the covariance
+ * parameters, predictive covariance matrices, predictive variances with "iterative", GPB_OptimCovParBoosting. Latent models accept
  * repeated coordinates (the reference's unique-location form). Anything else fails with -1 and a
  * message naming the unsupported option.
  * The compute path is HIP on gfx950; there is no CPU fallback: if no GPU is
@@ -359,6 +369,14 @@ GPBOOST_AMD_EXPORT int GPB_BenchLatentOperators(REModelHandle handle, int t, int
  * GPB_BenchLatentOperators times the CG's operator W^-1 + Sigma (out[0]) and the preconditioner
  * (W^-1 + L_k L_k^T)^-1 (out[1]). No reference counterpart (measurement and tests). */
 GPBOOST_AMD_EXPORT int GPB_GetPivotedCholeskyInfo(REModelHandle handle, double* out, int* pivots);
+
+/* Grouped random effects with a non-Gaussian likelihood: the structure and the weighted values of
+ * A - Sigma^-1 = Z^T W Z of the last evaluation. dims[0] = M (number of random effects), dims[1] = nnz of the
+ * off-diagonal part; rowptr (M + 1) and col (nnz): its CSR over the random effects (effect-major, columns
+ * ascending); diag (M) and vals (nnz): the values at the mode. Every array is nullable (diag and vals are
+ * filled together). No reference counterpart (tests). */
+GPBOOST_AMD_EXPORT int GPB_GetGroupedLaplaceInfo(REModelHandle handle, int32_t* dims, int32_t* rowptr, int32_t* col,
+                                                 double* diag, double* vals);
 
 /* Host restatement of the reference's PivotedCholsekyFactorizationSigma (CG_utils.h:438-488), the rules
  * the device factorisation follows; needs no GPU. coords: row-major n x d in the order the permutation
