@@ -687,6 +687,40 @@ int GPB_PivotedCholeskyHost(const double* coords, int n, int d, int cov_type, do
   API_END();
 }
 
+int GPB_TestDenseGemm(int variant, int M, int N, int K, double alpha, const double* A, int64_t a_len, int lda,
+                      int transA, const double* B, int64_t b_len, int ldb, int transB, double beta, double* C,
+                      int64_t c_len, int ldc, int lower_out, int a_lower, int a_upper, int b_lower, int c_alias_a) {
+  API_BEGIN();
+  if (a_len < 0 || b_len < 0 || c_len < 0) gpb_amd::Fatal("GPB_TestDenseGemm: negative extent");
+  gpb_amd::test_dense_gemm(variant, M, N, K, alpha, A, (long)a_len, lda, transA, B, (long)b_len, ldb, transB, beta, C,
+                           (long)c_len, ldc, lower_out, a_lower, a_upper, b_lower, c_alias_a);
+  API_END();
+}
+
+int GPB_TestDenseGemmSplitK(int variant, int M, int N, int K, const double* A, int64_t a_len, int lda, int transA,
+                            const double* B, int64_t b_len, int ldb, int transB, double* C, int64_t c_len, int ldc,
+                            int64_t cstride, int nslabs, int target_blocks, int max_chunks, int* out_chunks) {
+  API_BEGIN();
+  if (a_len < 0 || b_len < 0 || c_len < 0 || cstride < 0) gpb_amd::Fatal("GPB_TestDenseGemmSplitK: negative extent");
+  if (out_chunks == nullptr) gpb_amd::Fatal("GPB_TestDenseGemmSplitK: out_chunks is NULL");
+  *out_chunks = gpb_amd::test_dense_splitk(variant, M, N, K, A, (long)a_len, lda, transA, B, (long)b_len, ldb, transB,
+                                           C, (long)c_len, ldc, (long)cstride, nslabs, target_blocks, max_chunks);
+  API_END();
+}
+
+int GPB_TestDenseChol(int n, int ld, double* A, double* W, int want_inverse, double* logdet, int* out_info) {
+  API_BEGIN();
+  if (out_info == nullptr) gpb_amd::Fatal("GPB_TestDenseChol: out_info is NULL");
+  *out_info = gpb_amd::test_dense_chol(n, ld, A, W, want_inverse, logdet);
+  API_END();
+}
+
+int GPB_TestDenseSpdSolveInverse(int n, const double* A, const double* b, double* x, double* diag, double* inv) {
+  API_BEGIN();
+  gpb_amd::test_dense_spd_solve_inverse(n, A, b, x, diag, inv);
+  API_END();
+}
+
 int GPB_GetNumCGSteps(REModelHandle handle, int* num_cg_steps) {
   // re_model_template.h:527-537: defined for models of several grouped random effects only
   API_BEGIN();

@@ -94,6 +94,24 @@ void launch_logdet_chol(hipStream_t s, const double* L, int ld, int n, double* o
 // diag(A^-1) (nullable), the full A^-1 column-major (nullable). Fails if A is not positive definite.
 void spd_solve_inverse(hipStream_t s, int n, const double* A, const double* b, double* x, double* diag, double* inv);
 
+// Test entries into the primitives above (GPB_TestDense*, include/gpboost_amd.h): host arrays in and out with
+// their extents in doubles (*_len), checked against the sizes, transposes and leading dimensions before
+// anything runs; the default stream, synchronised. variant forces the kernel whatever the size and the
+// environment switches: gemm 0 = production dispatch, 1 = unpipelined 64-tile, 2 = pipelined 64-tile, 3 =
+// 128-tile; split-K 0 = production rule, 1 = 64-tile, 2 = 128-tile. c_alias_a: the product overwrites A's
+// device copy (chol_lower's in-place TRSM form) and comes back in C.
+void test_dense_gemm(int variant, int M, int N, int K, double alpha, const double* A, long a_len, int lda, int transA,
+                     const double* B, long b_len, int ldb, int transB, double beta, double* C, long c_len, int ldc,
+                     int lower_out, int a_lower, int a_upper, int b_lower, int c_alias_a);
+// C: nslabs >= max_chunks slabs of cstride doubles each (in / out); returns the number of chunks
+int test_dense_splitk(int variant, int M, int N, int K, const double* A, long a_len, int lda, int transA,
+                      const double* B, long b_len, int ldb, int transB, double* C, long c_len, int ldc, long cstride,
+                      int nslabs, int target_blocks, int max_chunks);
+// chol_lower on A and W (ld x ld each, in / out), then trtri_lower(0, n) (want_inverse) and launch_logdet_chol
+// (logdet non-null); returns info (non-zero exactly when a pivot was not positive and finite)
+int test_dense_chol(int n, int ld, double* A, double* W, int want_inverse, double* logdet);
+void test_dense_spd_solve_inverse(int n, const double* A, const double* b, double* x, double* diag, double* inv);
+
 // Gaussian prediction through a dense Vecchia approximation of the latent process over N points
 // (observed first: n, then np = N - n prediction points): B (host column-major N x N, unit lower),
 // D (N) -> Sigma = B^-1 diag(D) B^-T; mean = Sigma_po (Sigma_oo + I)^-1 y, cov = Sigma_pp -

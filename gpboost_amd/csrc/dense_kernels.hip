@@ -316,7 +316,8 @@ __global__ void __launch_bounds__(256) potrf_diag_kernel(double* A, int lda, int
   for (int j = 0; j < ib; ++j) {
     if (tid == 0) {
       const double p = L[j][j];
-      if (!(p > 0.)) { atomicAdd(info, 1); L[j][j] = 1.; }   // not positive definite
+      // not positive definite / not finite
+      if (!(p > 0.) || !(p < __builtin_inf())) { atomicAdd(info, 1); L[j][j] = 1.; }
       else L[j][j] = sqrt(p);
     }
     __syncthreads();
@@ -371,7 +372,7 @@ __global__ void __launch_bounds__(64) potrf_diag_wave_kernel(double* A, int lda,
     if (j < ib) {
       const double p = __shfl(row[j], j, 64);
       double d;
-      if (!(p > 0.)) {   // not positive definite
+      if (!(p > 0.) || !(p < __builtin_inf())) {   // not positive definite / not finite
         if (r == 0) atomicAdd(info, 1);
         d = 1.;
       } else {
@@ -421,11 +422,11 @@ __global__ void __launch_bounds__(64) potrf_diag_wave_kernel(double* A, int lda,
 // owner wave (j & 3) takes the pivot by v_readlane, scales its column (by 1 / sqrt(p) from the rsqrt estimate) and
 // publishes L[:, j] (zero for rows <= j) to LDS; after ONE barrier every wave updates its columns c > j
 // (registers whose columns are all <= j skipped at compile time, the published zeros make the rest
-// branch-free). A partial block (ib < 64) is padded with the identity. Every element sees the same
-// operations in the same order as in the one-wave kernel except the pivot scaling (multiplies by the Newton-refined
-// 1 / sqrt(p) instead of the one-wave form's sqrt + division: within an ulp per entry); L^-1 by its code on
-// wave 0 (a four-wave split of that substitution changed the rounding enough to move an ill-conditioned
-// Gaussian-kernel FITC case past its 1e-9 reference bound).
+// branch-free). A partial block (ib < 64) is padded with the identity. The updates are the one-wave kernel's
+// fmas in the same order, but the pivot scaling differs (multiplies by the Newton-refined 1 / sqrt(p) instead of
+// the one-wave and 256-thread forms' sqrt + division: within an ulp per entry), so L and L^-1 agree with those
+// forms to rounding only: GPBOOST_AMD_DIAG_FORM = quad vs wave / old is not a bitwise A/B. L^-1 by the four
+// waves below. A pivot that is not positive or not finite counts in info and is replaced by 1 in all three forms.
 __global__ void __launch_bounds__(256) potrf_diag_quad_kernel(double* A, int lda, int j0, int ib, double* Winv,
                                                               int ldw, int* info) {
   __shared__ double colb[2][64];
@@ -447,10 +448,13 @@ __global__ void __launch_bounds__(256) potrf_diag_quad_kernel(double* A, int lda
       const int lo = __builtin_amdgcn_readlane(__double2loint(col[j >> 2]), j);
       const int hi = __builtin_amdgcn_readlane(__double2hiint(col[j >> 2]), j);
       const double p = __hiloint2double(hi, lo);
-      bad = bad || !(p > 0.);   // not positive definite
+      // not positive definite, or not finite (rsq(+inf) = 0 would turn the Newton step into 0 * inf = NaN with
+      // info untouched): counted in info, the pivot replaced by 1
+      const bool ok = p > 0. && p < __builtin_inf();
+      bad = bad || !ok;
       // y = 1 / sqrt(p) by the hardware estimate and two Newton steps, L_jj = p y, the column scaled by y
       // (multiplies instead of a square root and a division on the pivot chain)
-      const double ps = p > 0. ? p : 1., h = 0.5 * ps;
+      const double ps = ok ? p : 1., h = 0.5 * ps;
       double y = __builtin_amdgcn_rsq(ps);
       y = y * fma(-h * y, y, 1.5);
       y = y * fma(-h * y, y, 1.5);
@@ -478,8 +482,9 @@ __global__ void __launch_bounds__(256) potrf_diag_quad_kernel(double* A, int lda
   // four waves: wave w keeps the partial sums acc_i of its rows i = 4k + w; step p: the owner of row p forms
   // x_p = acc_p / L_pp (its final entry) and publishes it, one barrier, every wave updates acc_i -= L_ip x_p for
   // its rows i > p. Each acc_i sees the same fmas in the same order (p ascending from delta_ir) as the one-wave
-  // kernel's dot products, so the inverse is bit-identical, at one division + one fma of latency per step instead
-  // of a dependent LDS-load + fma chain of length i per row on one wave.
+  // kernel's dot products, so for the same L the inverse would be bit-identical (the L above differs from the
+  // one-wave kernel's by the pivot scaling, so the two kernels' inverses differ by rounding), at one division +
+  // one fma of latency per step instead of a dependent LDS-load + fma chain of length i per row on one wave.
   double acc[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) acc[k] = (4 * k + w == r) ? 1. : 0.;
@@ -893,13 +898,16 @@ __global__ void dot_kernel(const double* a, const double* b, int n, double* out)
 
 void gemm(hipStream_t s, int M, int N, int K, double alpha, const double* A, int lda, int transA, const double* B,
           int ldb, int transB, double beta, double* C, int ldc, int lower_out = 0, int a_lower = 0, int a_upper = 0,
-          int b_lower = 0) {
+          int b_lower = 0, int variant = 0) {
+  // variant (tests): 0 = the dispatch below; 1 / 2 / 3 force the unpipelined 64-tile, the pipelined 64-tile and
+  // the 128-tile kernel at any size, whatever the environment switches say
   if (M <= 0 || N <= 0) return;
   GemmArgs g{M, N, K, alpha, beta, A, lda, transA, B, ldb, transB, C, ldc, lower_out, a_lower, a_upper, b_lower};
   static const bool small_only = std::getenv("GPBOOST_AMD_GEMM64") != nullptr;   // A/B: 64 x 64 tiles only
   // large tiles only where they still give every CU two tiles (small problems keep the 64 x 64
   // form's parallelism: n = 2000 measured 7.6 ms vs 8.6 ms per evaluation with 128 x 128 tiles)
-  if ((long)((M + TB - 1) / TB) * ((N + TB - 1) / TB) >= 512 && !small_only) {
+  const bool many = (long)((M + TB - 1) / TB) * ((N + TB - 1) / TB) >= 512;
+  if (variant == 0 ? many && !small_only : variant == 3) {
     dim3 grid((N + TB - 1) / TB, (M + TB - 1) / TB);
     hipLaunchKernelGGL(gemm_f64_big_kernel, grid, dim3(256), 0, s, g);
     HIP_CHECK(hipGetLastError());
@@ -907,7 +915,7 @@ void gemm(hipStream_t s, int M, int N, int K, double alpha, const double* A, int
   }
   dim3 grid((N + TN - 1) / TN, (M + TM - 1) / TM);
   static const bool unpiped = std::getenv("GPBOOST_AMD_GEMM_UNPIPED") != nullptr;   // A/B: round-1 64-tile form
-  if (unpiped)
+  if (variant == 0 ? unpiped : variant == 1)
     hipLaunchKernelGGL(gemm_f64_kernel, grid, dim3(256), 0, s, g);
   else
     hipLaunchKernelGGL(gemm_f64_pipe_kernel, grid, dim3(256), 0, s, g);
@@ -933,8 +941,9 @@ void gemm_f64(hipStream_t s, int M, int N, int K, double alpha, const double* A,
   gemm(s, M, N, K, alpha, A, lda, transA, B, ldb, transB, beta, C, ldc, lower_out, a_lower, a_upper, b_lower);
 }
 
-int gemm_f64_splitk(hipStream_t s, int M, int N, int K, const double* A, int lda, int transA, const double* B, int ldb,
-                    int transB, double* C, int ldc, long cstride, int target_blocks, int max_chunks) {
+// variant (tests): 0 = the tile rule below; 1 / 2 force the 64-tile / 128-tile kernel
+static int splitk(hipStream_t s, int M, int N, int K, const double* A, int lda, int transA, const double* B, int ldb,
+                  int transB, double* C, int ldc, long cstride, int target_blocks, int max_chunks, int variant) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   const long tiles = (long)((M + TN - 1) / TN) * ((N + TN - 1) / TN);
   int chunks = (int)std::max<long>(1, std::min<long>((target_blocks + tiles - 1) / tiles, (K + 255) / 256));
@@ -948,7 +957,7 @@ int gemm_f64_splitk(hipStream_t s, int M, int N, int K, const double* A, int lda
     const char* e = std::getenv("GPBOOST_AMD_SPLITK_TILE");
     return e != nullptr && std::string(e) == "64";
   }();
-  if (!tile64 && M >= TB && N >= TB) {
+  if (variant == 0 ? !tile64 && M >= TB && N >= TB : variant == 2) {
     dim3 grid((N + TB - 1) / TB, (M + TB - 1) / TB, chunks);
     hipLaunchKernelGGL(gemm_f64_splitk_big_kernel, grid, dim3(256), 0, s, g, kchunk, cstride);
   } else {
@@ -957,6 +966,11 @@ int gemm_f64_splitk(hipStream_t s, int M, int N, int K, const double* A, int lda
   }
   HIP_CHECK(hipGetLastError());
   return chunks;
+}
+
+int gemm_f64_splitk(hipStream_t s, int M, int N, int K, const double* A, int lda, int transA, const double* B, int ldb,
+                    int transB, double* C, int ldc, long cstride, int target_blocks, int max_chunks) {
+  return splitk(s, M, N, K, A, lda, transA, B, ldb, transB, C, ldc, cstride, target_blocks, max_chunks, 0);
 }
 
 DenseSolver::DenseSolver(int n, int d, const double* d_X, hipStream_t stream)
@@ -1498,6 +1512,123 @@ void DenseSolver::PsiInvDiag(int cov_type, double var, double phi, const double*
   HIP_CHECK(hipMemcpyAsync(yaux, ya, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipMemcpyAsync(diag, dg.get(), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
   CheckInfo();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Test entries into the primitives above (GPB_TestDense*, c_api.cpp): host arrays in and out, the default
+// stream, synchronised before returning. Every argument is checked first, so that a mistake in a test is an
+// error return and never an out-of-bounds access on the device.
+namespace {
+
+// extent of a column-major rows x cols operand with leading dimension ld inside an array of len doubles
+void check_operand(const char* fn, const char* name, long rows, long cols, long ld, long len, const void* p) {
+  if (ld < std::max(1L, rows)) Fatal("%s: ld of %s (%ld) is below its row count (%ld)", fn, name, ld, rows);
+  if (len < ld * cols) Fatal("%s: %s holds %ld doubles, ld x columns needs %ld", fn, name, len, ld * cols);
+  if (len > 0 && p == nullptr) Fatal("%s: %s is NULL", fn, name);
+}
+
+bool is_flag(int v) { return v == 0 || v == 1; }
+
+void upload(DevBuf<double>& d, const double* h, long len, hipStream_t s) {
+  d.alloc((size_t)std::max(1L, len));
+  if (len > 0) HIP_CHECK(hipMemcpyAsync(d.get(), h, sizeof(double) * len, hipMemcpyHostToDevice, s));
+}
+
+}  // namespace
+
+void test_dense_gemm(int variant, int M, int N, int K, double alpha, const double* A, long a_len, int lda, int transA,
+                     const double* B, long b_len, int ldb, int transB, double beta, double* C, long c_len, int ldc,
+                     int lower_out, int a_lower, int a_upper, int b_lower, int c_alias_a) {
+  const char* fn = "GPB_TestDenseGemm";
+  if (variant < 0 || variant > 3) Fatal("%s: variant must be 0 (dispatch), 1, 2 or 3 (got %d)", fn, variant);
+  if (M < 0 || N < 0 || K < 0) Fatal("%s: negative size", fn);
+  if (!is_flag(transA) || !is_flag(transB) || !is_flag(lower_out) || !is_flag(a_lower) || !is_flag(a_upper) ||
+      !is_flag(b_lower) || !is_flag(c_alias_a))
+    Fatal("%s: flags must be 0 or 1", fn);
+  check_operand(fn, "A", transA ? K : M, transA ? M : K, lda, a_len, A);
+  check_operand(fn, "B", transB ? N : K, transB ? K : N, ldb, b_len, B);
+  check_operand(fn, "C", M, N, ldc, c_len, C);
+  if (c_alias_a) {
+    // the in-place form C = A op(B) over A's storage (chol_lower's TRSM): every workgroup reads its rows' whole K
+    // range before it stores, which needs one tile column and rows that are A's rows
+    if (transA || N > 64 || ldc != lda || c_len != a_len)
+      Fatal("%s: c_alias_a needs transA = 0, N <= 64, ldc = lda and C of A's extent", fn);
+  }
+  hipStream_t s = nullptr;
+  DevBuf<double> dA, dB, dC;
+  upload(dA, A, a_len, s);
+  upload(dB, B, b_len, s);
+  if (!c_alias_a) upload(dC, C, c_len, s);
+  double* c = c_alias_a ? dA.get() : dC.get();
+  gemm(s, M, N, K, alpha, dA.get(), lda, transA, dB.get(), ldb, transB, beta, c, ldc, lower_out, a_lower, a_upper,
+       b_lower, variant);
+  if (c_len > 0) HIP_CHECK(hipMemcpyAsync(C, c, sizeof(double) * c_len, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+int test_dense_splitk(int variant, int M, int N, int K, const double* A, long a_len, int lda, int transA,
+                      const double* B, long b_len, int ldb, int transB, double* C, long c_len, int ldc, long cstride,
+                      int nslabs, int target_blocks, int max_chunks) {
+  const char* fn = "GPB_TestDenseGemmSplitK";
+  if (variant < 0 || variant > 2) Fatal("%s: variant must be 0 (tile rule), 1 or 2 (got %d)", fn, variant);
+  if (M < 0 || N < 0 || K < 0) Fatal("%s: negative size", fn);
+  if (!is_flag(transA) || !is_flag(transB)) Fatal("%s: flags must be 0 or 1", fn);
+  if (target_blocks < 1 || max_chunks < 1 || max_chunks > 65535) Fatal("%s: target_blocks / max_chunks out of range", fn);
+  if (nslabs < max_chunks) Fatal("%s: nslabs (%d) is below max_chunks (%d)", fn, nslabs, max_chunks);
+  check_operand(fn, "A", transA ? K : M, transA ? M : K, lda, a_len, A);
+  check_operand(fn, "B", transB ? N : K, transB ? K : N, ldb, b_len, B);
+  if (ldc < std::max(1, M)) Fatal("%s: ldc (%d) is below M (%d)", fn, ldc, M);
+  if (cstride < (long)ldc * N) Fatal("%s: cstride (%ld) is below ldc x N (%ld)", fn, cstride, (long)ldc * N);
+  if (c_len != cstride * nslabs) Fatal("%s: C holds %ld doubles, nslabs x cstride is %ld", fn, c_len, cstride * nslabs);
+  if (c_len > 0 && C == nullptr) Fatal("%s: C is NULL", fn);
+  hipStream_t s = nullptr;
+  DevBuf<double> dA, dB, dC;
+  upload(dA, A, a_len, s);
+  upload(dB, B, b_len, s);
+  upload(dC, C, c_len, s);
+  const int chunks = splitk(s, M, N, K, dA.get(), lda, transA, dB.get(), ldb, transB, dC.get(), ldc, cstride,
+                            target_blocks, max_chunks, variant);
+  if (c_len > 0) HIP_CHECK(hipMemcpyAsync(C, dC.get(), sizeof(double) * c_len, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return chunks;
+}
+
+int test_dense_chol(int n, int ld, double* A, double* W, int want_inverse, double* logdet) {
+  const char* fn = "GPB_TestDenseChol";
+  if (n < 1) Fatal("%s: n must be positive", fn);
+  if (ld < n || ld % 64 != 0) Fatal("%s: ld (%d) must be a multiple of 64 and >= n (%d)", fn, ld, n);
+  if (A == nullptr || W == nullptr) Fatal("%s: A or W is NULL", fn);
+  if (!is_flag(want_inverse)) Fatal("%s: flags must be 0 or 1", fn);
+  const long nn = (long)ld * ld;
+  hipStream_t s = nullptr;
+  DevBuf<double> dA, dW, T, ldet(1);
+  DevBuf<int> info(1);
+  upload(dA, A, nn, s);
+  upload(dW, W, nn, s);
+  HIP_CHECK(hipMemsetAsync(info.get(), 0, sizeof(int), s));
+  chol_lower(s, dA.get(), dW.get(), n, ld, info.get());
+  if (want_inverse) {
+    T.alloc((size_t)ld * (ld / 2 + 64));
+    trtri_lower(s, dA.get(), dW.get(), T.get(), 0, n, ld);
+  }
+  if (logdet != nullptr) {
+    launch_logdet_chol(s, dA.get(), ld, n, ldet.get());
+    HIP_CHECK(hipMemcpyAsync(logdet, ldet.get(), sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  int h_info = 0;
+  HIP_CHECK(hipMemcpyAsync(A, dA.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(W, dW.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&h_info, info.get(), sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return h_info;
+}
+
+void test_dense_spd_solve_inverse(int n, const double* A, const double* b, double* x, double* diag, double* inv) {
+  const char* fn = "GPB_TestDenseSpdSolveInverse";
+  if (n < 1) Fatal("%s: n must be positive", fn);
+  if (A == nullptr) Fatal("%s: A is NULL", fn);
+  if ((b == nullptr) != (x == nullptr)) Fatal("%s: b and x must be given together", fn);
+  spd_solve_inverse(nullptr, n, A, b, x, diag, inv);
 }
 
 }  // namespace gpb_amd

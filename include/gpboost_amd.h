@@ -386,6 +386,38 @@ GPBOOST_AMD_EXPORT int GPB_PivotedCholeskyHost(const double* coords, int n, int 
                                                double phi, int rank, double tol, double* L, int* pivots,
                                                int* out_rank);
 
+/* The dense fp64 building blocks (C = alpha op(A) op(B) + beta C on MFMA tiles with triangle masks, its
+ * split-K form, the blocked Cholesky with the triangular inverse and the log-determinant, the SPD solve /
+ * inverse) on host arrays, one call each: column-major, copied to the device and back, synchronised. Extents
+ * (*_len, in doubles) are checked against the sizes, transposes and leading dimensions; a violation is an
+ * error return. No reference counterpart (tests).
+ * GPB_TestDenseGemm: variant 0 = the production dispatch, 1 = unpipelined 64 x 64 tiles, 2 = pipelined 64 x 64
+ * tiles, 3 = 128 x 128 tiles, forced at any size. C (c_len >= ldc * N doubles, all copied both ways) is in /
+ * out. lower_out: elements above the diagonal are not written; a_lower / a_upper: op(A)[i][k] is taken as 0
+ * for k > i / k < i; b_lower: op(B)[k][j] is taken as 0 for k < j (never read). c_alias_a = 1: the product
+ * overwrites A on the device (transA = 0, N <= 64, ldc = lda, c_len = a_len) and is returned in C. */
+GPBOOST_AMD_EXPORT int GPB_TestDenseGemm(int variant, int M, int N, int K, double alpha, const double* A,
+                                         int64_t a_len, int lda, int transA, const double* B, int64_t b_len,
+                                         int ldb, int transB, double beta, double* C, int64_t c_len, int ldc,
+                                         int lower_out, int a_lower, int a_upper, int b_lower, int c_alias_a);
+/* Chunk z of K writes op(A) op(B) over its K range to C + z * cstride (M x N, ldc); C holds nslabs >=
+ * max_chunks slabs (c_len = nslabs * cstride, cstride >= ldc * N), all copied both ways. variant 0 = the
+ * production tile rule, 1 = 64 x 64 tiles, 2 = 128 x 128 tiles. out_chunks: the number of chunks. */
+GPBOOST_AMD_EXPORT int GPB_TestDenseGemmSplitK(int variant, int M, int N, int K, const double* A, int64_t a_len,
+                                               int lda, int transA, const double* B, int64_t b_len, int ldb,
+                                               int transB, double* C, int64_t c_len, int ldc, int64_t cstride,
+                                               int nslabs, int target_blocks, int max_chunks, int* out_chunks);
+/* Cholesky of the lower triangle of A (order n, ld x ld doubles, ld a multiple of 64, in / out: L); W (ld x ld,
+ * in / out): the inverses of L's 64 x 64 diagonal blocks and, with want_inverse = 1, all of L^-1. logdet
+ * (nullable): 2 sum log L_ii. out_info: non-zero exactly when some pivot was not positive and finite (not the
+ * number of such pivots: the default kernel adds to it at most once per wave and diagonal block). */
+GPBOOST_AMD_EXPORT int GPB_TestDenseChol(int n, int ld, double* A, double* W, int want_inverse, double* logdet,
+                                         int* out_info);
+/* A: n x n (ld = n). x = A^-1 b (b and x nullable together), diag = diag(A^-1) (nullable), inv = A^-1
+ * (n x n, nullable). Fails if A is not positive definite. */
+GPBOOST_AMD_EXPORT int GPB_TestDenseSpdSolveInverse(int n, const double* A, const double* b, double* x,
+                                                    double* diag, double* inv);
+
 /* ---------------------------------------------------------------- prediction */
 
 /* replaces GPB_SetPredictionData (include/LightGBM/c_api.h:1578; c_api.cpp). Only the settings
