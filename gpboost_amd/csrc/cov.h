@@ -54,20 +54,31 @@ __device__ __forceinline__ double sqrt_nonneg(double s) {
   return fma(e, h, g);
 }
 
-__device__ __forceinline__ double exp_nonpos(double x) {
+// exp's constants that no instruction can take as an inline operand: log2(e), ln 2 (high, low) and the
+// polynomial's coefficients. A kernel short of VGPRs passes a copy it holds in scalar registers
+// (ExpCoef::scalar()), so they are not re-materialised by 64-bit VALU moves at every evaluation.
+struct ExpCoef {
+  double log2e = 0x1.71547652b82fep+0, ln2hi = -0x1.62e42fefa39efp-1, ln2lo = -0x1.abc9e3b39803fp-56;
+  double c[10] = {0x1.ade156a5dcb37p-26, 0x1.28af3fca7ab0cp-22, 0x1.71dee623fde64p-19, 0x1.a01997c89e6b0p-16,
+                  0x1.a01a014761f6ep-13, 0x1.6c16c1852b7b0p-10, 0x1.1111111122322p-7,  0x1.55555555502a1p-5,
+                  0x1.5555555555511p-3,  0x1.000000000000bp-1};
+  __device__ __forceinline__ static ExpCoef scalar() {
+    ExpCoef k;
+    asm volatile("" : "+s"(k.log2e), "+s"(k.ln2hi), "+s"(k.ln2lo));
+#pragma unroll
+    for (int q = 0; q < 10; ++q) asm volatile("" : "+s"(k.c[q]));
+    return k;
+  }
+};
+
+__device__ __forceinline__ double exp_nonpos(double x, const ExpCoef& k = ExpCoef{}) {
   x = fmax(x, -1075.);
-  const double n = __builtin_rint(x * 0x1.71547652b82fep+0);
-  double t = fma(-0x1.62e42fefa39efp-1, n, x);
-  t = fma(-0x1.abc9e3b39803fp-56, n, t);
-  double p = fma(0x1.ade156a5dcb37p-26, t, 0x1.28af3fca7ab0cp-22);
-  p = fma(t, p, 0x1.71dee623fde64p-19);
-  p = fma(t, p, 0x1.a01997c89e6b0p-16);
-  p = fma(t, p, 0x1.a01a014761f6ep-13);
-  p = fma(t, p, 0x1.6c16c1852b7b0p-10);
-  p = fma(t, p, 0x1.1111111122322p-7);
-  p = fma(t, p, 0x1.55555555502a1p-5);
-  p = fma(t, p, 0x1.5555555555511p-3);
-  p = fma(t, p, 0x1.000000000000bp-1);
+  const double n = __builtin_rint(x * k.log2e);
+  double t = fma(k.ln2hi, n, x);
+  t = fma(k.ln2lo, n, t);
+  double p = fma(k.c[0], t, k.c[1]);
+#pragma unroll
+  for (int q = 2; q < 10; ++q) p = fma(t, p, k.c[q]);
   p = fma(t, p, 1.);
   p = fma(t, p, 1.);
   return __builtin_amdgcn_ldexp(p, (int)n);
@@ -75,24 +86,25 @@ __device__ __forceinline__ double exp_nonpos(double x) {
 
 // cov_dcov on the squared distance with the device forms above (identical formulas)
 template <int COV>
-__device__ __forceinline__ void cov_dcov_sq(double s, double var, double phi, double& c, double& dc) {
+__device__ __forceinline__ void cov_dcov_sq(double s, double var, double phi, double& c, double& dc,
+                                            const ExpCoef& k = ExpCoef{}) {
   const double r = sqrt_nonneg(s);
   if constexpr (COV == kMatern05) {
-    const double e = exp_nonpos(-phi * r);
+    const double e = exp_nonpos(-phi * r, k);
     c = var * e;
     dc = -phi * r * c;
   } else if constexpr (COV == kMatern15) {
     const double x = phi * r;
-    const double e = exp_nonpos(-x);
+    const double e = exp_nonpos(-x, k);
     c = var * (1. + x) * e;
     dc = -var * x * x * e;
   } else if constexpr (COV == kMatern25) {
     const double x = phi * r;
-    const double e = exp_nonpos(-x);
+    const double e = exp_nonpos(-x, k);
     c = var * (1. + x + x * x / 3.) * e;
     dc = -var * x * x / 3. * (1. + x) * e;
   } else {
-    const double e = exp_nonpos(-phi * r * r);
+    const double e = exp_nonpos(-phi * r * r, k);
     c = var * e;
     dc = -phi * r * r * c;
   }

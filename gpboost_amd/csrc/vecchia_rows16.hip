@@ -16,10 +16,19 @@
 //      LDS with copies of slots 0..15 at 31..46 (partner v + delta is an immediate-offset read). C to
 //      the packed lower triangle, dC/dlog(phi) in registers until the rows are loaded, then over the
 //      packed C in the circulant layout W[(delta - 1) 32 + v];
-//   2. rows h and h + 16 of the bordered matrix into registers; 30 Gauss-Jordan steps by DPP
-//      broadcasts (pivots 16..29 on the B rows only, the A rows finished by one block
-//      back-substitution); a_v = M[v][30] / M[v][v], w_v = M[v][31] / M[v][v] (the pivots are captured
-//      when broadcast);
+//   2. rows h and h + 16 of the bordered matrix into registers (lane address + immediate; the columns
+//      that cross the packed triangle's diagonal by two reads under compile-time lane masks); 30
+//      Gauss-Jordan steps by DPP broadcasts, each broadcast folded into its FMAs (v_fmac_f64_dpp):
+//        pivots 0..15  update the B rows (h + 16) in all columns j + 1..31, the A rows (h) only in
+//                      columns j + 1..15; the A rows' multipliers stay in the dead column registers r0[j];
+//        pivots 16..29 update the B rows only;
+//        A rows        M[h][30..31] -= sum_{c = 16..29} M[h][c] x_c with their original columns 16..29
+//                      (block back-substitution), then the 16 stored row operations replayed on these
+//                      two right-hand sides in pivot order (by linearity the same solution);
+//      675 DPP fmacs per problem set: 376 + 119 on the B rows, 120 + 28 + 32 on the A rows (899 with
+//      the A rows' columns 16..31 carried through pivots 0..15: 376 + 119 and 376 + 28; 990 for the
+//      plain 30-pivot Gauss-Jordan on both rows).
+//      a_v = M[v][30] / M[v][v], w_v = M[v][31] / M[v][v] (the pivots are captured when broadcast);
 //   3. a^T dC a and w^T dC a over each lane's circulant pairs ([a, w] pairs with the same wrap copies);
 //   4. the eight group sums by DPP within the 16-lane row, then the six row partials.
 #include <hip/hip_runtime.h>
@@ -35,21 +44,24 @@ namespace gpb_amd {
 namespace {
 
 constexpr int kD3 = 3;   // coordinate dimension bound (VecchiaRowsArgs.d <= 3)
-// broadcasts in flight per elimination step (1, 2 or 4): 1 / 2 / 4 measured 0.2193 / 0.2176 / 0.2162 ms
-// per launch (profiles/r03/rows_ab_r03o.log, rows_ab_r03p.log)
-#ifndef GPB_ROWS16_BCG
-#define GPB_ROWS16_BCG 4
-#endif
-// broadcasts folded into v_fmac_f64_dpp (1, default) vs separate DPP moves + FMAs (0): 0.1968 vs
-// 0.2140 ms per launch, 4835 vs 4483 evals/s (profiles/r04/round_r04c.log)
-#ifndef GPB_ROWS16_FMAC
-#define GPB_ROWS16_FMAC 1
-#endif
-// pivots 16..29 eliminate only the B rows (h + 16); the A rows' solution is completed by one block
-// back-substitution x_A -= M_AB x_B afterwards (28 instead of 119 fused broadcasts per problem)
-#ifndef GPB_ROWS16_BACKSUB
-#define GPB_ROWS16_BACKSUB 1
-#endif
+// Measured choices (MI355X, n = 100k, m = 30, exponential; evals/s of the headline bench, medians of 5
+// alternated runs, the parent's own min-max spread 30; profiles/rows16_issue/RESULTS.md). Each was an
+// A/B macro of this file (GPBOOST_AMD_VARIANT / GPBOOST_AMD_DEFS builds); the losing branches are gone.
+//   - every broadcast folded into its FMAs as one v_fmac_f64_dpp: 0.1968 vs 0.2140 ms per launch against
+//     separate DPP moves + FMAs (profiles/r04/round_r04c.log);
+//   - pivots 16..29 eliminate only the B rows (h + 16), the A rows' solution completed by one block
+//     back-substitution x_A -= M_AB x_B (28 instead of 119 broadcasts per problem; 4950 vs 4780);
+//   - the A rows' columns 16..31 stay out of pivots 0..15, the multipliers kept in the dead column
+//     registers and the 16 row operations replayed on the two right-hand sides after the
+//     back-substitution (120 + 32 instead of 376 A-row fmacs per problem): 5616 vs 5299 with it off;
+//   - the matrix rows read from the packed triangle at lane address + immediate, the columns that cross
+//     the diagonal by two reads under compile-time lane masks, instead of a per-lane address select per
+//     entry (about 290 VALU ops per problem set): 5616 vs 5458;
+//   - exp's constants held in scalar registers across the loop (ExpCoef::scalar(), cov.h) instead of
+//     64-bit VALU moves at each use (63 per problem set): 5616 vs 5500.
+// Rejected: the next pivot's broadcast, reciprocal and multipliers issued after the step's first three
+// columns and left to the compiler to schedule under the rest of the step's fmacs (it did interleave
+// them): 5616 with vs 5628 without, inside the noise; round 4 had measured the hand-pinned form slower.
 
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void cfence() { asm volatile("" ::: "memory"); }
@@ -82,6 +94,39 @@ __device__ __forceinline__ void fmac_bcast16(double& acc, double src, double mul
     asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
                  : "+v"(acc)
                  : "v"(src), "v"(mul), "n"(L));
+}
+
+__device__ __forceinline__ unsigned lds_addr(const double* p) {   // the 32-bit LDS byte address of a __shared__ pointer
+  return (unsigned)(size_t)(const __attribute__((address_space(3))) double*)p;
+}
+
+// Rows h and h + 16, columns C and C + 16 (C = 1..15), of a packed lower triangle: every lane reads
+// the entry past the diagonal at `up + tri(column)`, then the lanes with h >= C (the same compile-time
+// lane mask for both rows) read theirs at `lo + column` over it; LDS returns in order, so the second
+// read wins. No address select, no VALU op. The exec mask is saved and restored inside the statement
+// (no compiler-scheduled instruction runs under the narrowed mask); the results are in flight when it
+// ends: the caller waits (s_waitcnt lgkmcnt(0)) before it uses them, and tests/test_isa_rows16_loads.py
+// checks in the built code that nothing names their registers before that wait.
+template <int C>
+__device__ __forceinline__ void lds_read_split2(double& a, double& b, unsigned up_a, unsigned up_b, unsigned lo_a,
+                                                unsigned lo_b) {
+  constexpr unsigned m16 = (0xFFFFu << C) & 0xFFFFu;
+  constexpr unsigned long mask = m16 | m16 << 16;   // both halves of exec
+  constexpr int CB = C + 16;
+  unsigned long saved;
+  asm volatile(
+      "ds_read_b64 %0, %3 offset:%7\n\t"
+      "ds_read_b64 %1, %4 offset:%8\n\t"
+      "s_mov_b64 %2, exec\n\t"
+      "s_and_b32 exec_lo, exec_lo, %11\n\t"
+      "s_and_b32 exec_hi, exec_hi, %11\n\t"
+      "ds_read_b64 %0, %5 offset:%9\n\t"
+      "ds_read_b64 %1, %6 offset:%10\n\t"
+      "s_mov_b64 exec, %2"
+      : "=&v"(a), "=&v"(b), "=&s"(saved)
+      : "v"(up_a), "v"(up_b), "v"(lo_a), "v"(lo_b), "n"(C * (C + 1) / 2 * 8), "n"(CB * (CB + 1) / 2 * 8), "n"(C * 8),
+        "n"(CB * 8), "n"(mask)
+      : "memory", "scc");
 }
 
 __device__ __forceinline__ double sum16(double v) {   // fixed-order sum over the 16-lane row
@@ -137,6 +182,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   double* acc = smem + 4 * PD + g * kVecchiaSums;
   if ((lane & 15) < kVecchiaSums) acc[lane & 15] = 0.;
   const int total = a.r1 - a.r0;
+  const ExpCoef ek = ExpCoef::scalar();
   // problem sets (4 rows) over the G waves: full rounds w + it G; the last round's E sets either on
   // waves 0..E-1 (sched 0/2) or spread evenly over the grid (sched 1), so its waves do not crowd the
   // first SIMDs the dispatcher fills
@@ -205,7 +251,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
           s += t * t;
         }
         double cv, dcv;
-        cov_dcov_sq<COV>(s, var, phi, cv, dcv);
+        cov_dcov_sq<COV>(s, var, phi, cv, dcv, ek);
         Cp[b0 + h * dl + dl * (dl + 1) / 2] = cv;   // packed(h + dl, h)
         w0[dl - 1] = dcv;
       }
@@ -219,7 +265,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
           s += t * t;
         }
         double cv, dcv;
-        cov_dcov_sq<COV>(s, var, phi, cv, dcv);
+        cov_dcov_sq<COV>(s, var, phi, cv, dcv, ek);
         // packed(v1 + dl, v1), or past slot 30 packed(v1, v1 + dl - 31) (slot 31: row 31, overwritten below)
         const int pos = (v1 + dl <= kMK) ? b1 + v1 * dl + dl * (dl + 1) / 2 : b1 + dl - 31;
         Cp[pos] = cv;
@@ -236,10 +282,34 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // ---- 2. rows h and h + 16 into registers; c and y_nbr (their columns 30, 31) wait out the
     // elimination in the coordinate area; dC over the packed C (circulant layout W[(delta - 1) 32 + v])
     double r0[kK], r1[kK];
+    {
+      // M[v][c] is packed(v, c) = Cp[tri(v) + c] for c <= v and packed(c, v) = Cp[tri(c) + v] past the
+      // diagonal: lane address + compile-time offset either way. Rows h <= 15 < 16 <= h + 16 settle the
+      // choice for r0's columns 0 and 16..31 and r1's columns 0..16; r0[c] and r1[c + 16], c = 1..15,
+      // share the lane mask h >= c and take the two-read form
+      const unsigned lo0 = lds_addr(Cp + tri(h)), up0 = lds_addr(Cp + h);
+      const unsigned lo1 = lds_addr(Cp + tri(v1)), up1 = lds_addr(Cp + v1);
+      r0[0] = Cp[tri(h)];
 #pragma unroll
-    for (int c = 0; c < kK; ++c) {
-      r0[c] = (c <= h) ? Cp[tri(h) + c] : Cp[tri(c) + h];
-      r1[c] = (c <= v1) ? Cp[tri(v1) + c] : Cp[tri(c) + v1];
+      for (int c = 16; c < kK; ++c) r0[c] = Cp[tri(c) + h];
+#pragma unroll
+      for (int c = 0; c <= 16; ++c) r1[c] = Cp[tri(v1) + c];
+      sfor<1, 16>([&](auto C) {
+        constexpr int c = decltype(C)::value;
+        double &p0 = r0[c], &p1 = r1[c + 16];
+        lds_read_split2<c>(p0, p1, up0, up1, lo0, lo1);
+      });
+      // the reads above are not the compiler's to wait for: every use of their registers goes through
+      // these statements, the first of which waits
+      sfor<0, 3>([&](auto Q) {
+        constexpr int q = 1 + 5 * decltype(Q)::value;
+        double &a0 = r0[q], &a1 = r0[q + 1], &a2 = r0[q + 2], &a3 = r0[q + 3], &a4 = r0[q + 4];
+        double &b0 = r1[q + 16], &b1 = r1[q + 17], &b2 = r1[q + 18], &b3 = r1[q + 19], &b4 = r1[q + 20];
+        if constexpr (q == 1)
+          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4));
+        else
+          asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4));
+      });
     }
     double c0, c1, dc0, dc1;
     cfence();
@@ -256,76 +326,50 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
     // Gauss-Jordan, 30 pivots: M[j][c] = M[c][j] from lane c mod 16 (register set c / 16)
     double dg0 = 1., dg1 = 1.;
-    sfor<0, kMK>([&](auto J) {
+    // pivot j's negated multipliers for rows h (pivots 0..15 only) and h + 16; the pivot row's own is 0
+    auto pivot = [&](auto J, double& m0, double& m1) {
       constexpr int j = decltype(J)::value;
       constexpr int jl = j & 15;
-      constexpr bool jhi = j >= 16;
-      const double piv = bcast16<jl>(jhi ? r1[j] : r0[j]);
+      const double piv = bcast16<jl>(j >= 16 ? r1[j] : r0[j]);
       const double rinv = recip(piv);
       const bool own = h == jl;
-      double f0 = r0[j] * rinv, f1 = r1[j] * rinv;
-      if constexpr (jhi) {
-        f1 = own ? 0. : f1;
+      const double f1 = r1[j] * rinv;
+      if constexpr (j >= 16) {
+        m0 = 0.;
+        m1 = -(own ? 0. : f1);
         dg1 = own ? piv : dg1;
       } else {
-        f0 = own ? 0. : f0;
+        const double f0 = r0[j] * rinv;
+        m0 = -(own ? 0. : f0);
+        m1 = -f1;
         dg0 = own ? piv : dg0;
       }
-#if GPB_ROWS16_FMAC
-      // each broadcast folded into its two FMAs: v_fmac_f64_dpp row_newbcast (gfx950 takes DPP on the
-      // 64-bit fmac; the compiler never folds a 64-bit DPP move into its uses), so a column costs two
-      // VALU ops instead of three and no move -> FMA dependency
-      constexpr bool upd0 = !GPB_ROWS16_BACKSUB || !jhi;   // A rows take part in pivots 0..15 only
-      const double nf0 = upd0 ? -f0 : 0., nf1 = -f1;
+    };
+    sfor<0, kMK>([&](auto J) {
+      constexpr int j = decltype(J)::value;
+      constexpr bool jhi = j >= 16;
+      double nf0, nf1;
+      pivot(J, nf0, nf1);
+      // each broadcast folded into its FMAs: v_fmac_f64_dpp row_newbcast (gfx950 takes DPP on the 64-bit
+      // fmac; the compiler never folds a 64-bit DPP move into its uses), so a column costs one VALU op
+      // per updated row and no move -> FMA dependency
+      constexpr int cA = jhi ? 0 : 16;   // the A rows take columns j + 1 .. cA - 1
       sfor<j + 1, kK>([&](auto C) {
         constexpr int c = decltype(C)::value;
         constexpr bool first = c == j + 1;   // wait states before the step's first DPP read
         const double& src = c >= 16 ? r1[j] : r0[j];
-        if constexpr (upd0) fmac_bcast16<c & 15, first>(r0[c], src, nf0);
-        fmac_bcast16<c & 15, first && !upd0>(r1[c], src, nf1);
+        if constexpr (c < cA) fmac_bcast16<c & 15, first>(r0[c], src, nf0);
+        fmac_bcast16<c & 15, first && !(c < cA)>(r1[c], src, nf1);
       });
-#elif GPB_ROWS16_BCG > 1
-      // GPB_ROWS16_BCG broadcasts in flight: a group's DPP moves issue before its FMAs (the compiler
-      // otherwise reuses one temporary, a DPP -> FMA dependency per column)
-      constexpr int BG = GPB_ROWS16_BCG;
-      constexpr int ncol = kK - 1 - j;   // columns j + 1 .. kK - 1
-      sfor<0, ncol / BG>([&](auto P) {
-        constexpr int c0g = j + 1 + BG * decltype(P)::value;
-        double m[BG];
-        sfor<0, BG>([&](auto Q) {
-          constexpr int c = c0g + decltype(Q)::value;
-          m[decltype(Q)::value] = bcast16<c & 15>(c >= 16 ? r1[j] : r0[j]);
-        });
-        if constexpr (BG == 2) asm volatile("" ::"v"(m[0]), "v"(m[1]));
-        if constexpr (BG == 4) asm volatile("" ::"v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]));
-#pragma unroll
-        for (int q = 0; q < BG; ++q) {
-          r0[c0g + q] = fma(-f0, m[q], r0[c0g + q]);
-          r1[c0g + q] = fma(-f1, m[q], r1[c0g + q]);
-        }
-      });
-      sfor<j + 1 + BG * (ncol / BG), kK>([&](auto C) {   // the remainder, one at a time
-        constexpr int c = decltype(C)::value;
-        const double mc = bcast16<c & 15>(c >= 16 ? r1[j] : r0[j]);
-        r0[c] = fma(-f0, mc, r0[c]);
-        r1[c] = fma(-f1, mc, r1[c]);
-      });
-#else
+      // pin this step's updates (otherwise the broadcasts stay live)
       sfor<j + 1, kK>([&](auto C) {
         constexpr int c = decltype(C)::value;
-        const double mc = bcast16<c & 15>(c >= 16 ? r1[j] : r0[j]);
-        r0[c] = fma(-f0, mc, r0[c]);
-        r1[c] = fma(-f1, mc, r1[c]);
+        double &p0 = r0[c], &p1 = r1[c];
+        if constexpr (c < cA) asm volatile("" : "+v"(p0), "+v"(p1));
+        else asm volatile("" : "+v"(p1));
       });
-#endif
-      // pin this step's updates (otherwise the FMAs are deferred and the broadcasts stay live)
-#pragma unroll
-      for (int c = j + 1; c < kK; ++c) {
-        if (GPB_ROWS16_BACKSUB && jhi) asm volatile("" : "+v"(r1[c]));
-        else asm volatile("" : "+v"(r0[c]), "+v"(r1[c]));
-      }
+      if constexpr (!jhi) r0[j] = nf0;   // column j of the A rows is dead: keep the step's multiplier there
     });
-#if GPB_ROWS16_FMAC && GPB_ROWS16_BACKSUB
     {   // A rows: M[h][30..31] -= sum_{c=16..29} M[h][c] x_c, x_c = M[c][30..31] / M[c][c] (lane c - 16)
       const double i1 = recip(dg1);
       const double na = rv1 ? -(r1[kMK] * i1) : 0., nw = rv1 ? -(r1[kMK + 1] * i1) : 0.;
@@ -334,8 +378,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         fmac_bcast16<c & 15, c == 16>(r0[kMK], na, r0[c]);
         fmac_bcast16<c & 15, c == 16>(r0[kMK + 1], nw, r0[c]);
       });
+      // ... with the A rows' original columns 16..29; now the 16 Jordan steps on the two right-hand
+      // sides alone, z_h -= f_j[h] z_j in pivot order (the same row operations, by linearity the same
+      // solution). Each step reads, by DPP, what the step before wrote: the two sides alternate and
+      // the first carries the remaining wait states.
+      sfor<0, 16>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        fmac_bcast16<j, true>(r0[kMK], r0[kMK], r0[j]);
+        fmac_bcast16<j>(r0[kMK + 1], r0[kMK + 1], r0[j]);
+      });
     }
-#endif
     {   // the stashed c, y_nbr back (read before the [a, w] array below overwrites the area); dc_v = dC(v, 30):
         // the slot-30 pair at delta = v + 1 (v <= 14), slot v's pair at delta = 30 - v (v = 15..29)
       lds_sync();
