@@ -586,6 +586,12 @@ class GPModel:
         _safe_call(lib().GPB_GetVecchiaFactor(self.handle, _dp(cp), _dp(dinv), _dp(b)))
         return dinv, b
 
+    def vecchia_rows_info(self):
+        """Stored pair distances of the exact Vecchia row kernel: stored (0/1), bytes, rows, build_ms."""
+        out = np.zeros(4)
+        _safe_call(lib().GPB_GetVecchiaRowsInfo(self.handle, _dp(out)))
+        return dict(stored=int(out[0]), bytes=int(out[1]), rows=int(out[2]), build_ms=float(out[3]))
+
     def last_kernel_ms(self):
         out = np.zeros(2)
         _safe_call(lib().GPB_GetLastKernelTimes(self.handle, _dp(out)))

@@ -874,6 +874,12 @@ int GPB_GetVecchiaFactor(REModelHandle handle, const double* cov_pars, double* D
   API_END();
 }
 
+int GPB_GetVecchiaRowsInfo(REModelHandle handle, double* out) {
+  API_BEGIN();
+  model(handle)->GetVecchiaRowsInfo(out);
+  API_END();
+}
+
 int GPB_GetLastKernelTimes(REModelHandle handle, double* kernel_ms) {
   API_BEGIN();
   model(handle)->GetLastKernelTimes(kernel_ms);

@@ -84,11 +84,10 @@ __device__ __forceinline__ double exp_nonpos(double x, const ExpCoef& k = ExpCoe
   return __builtin_amdgcn_ldexp(p, (int)n);
 }
 
-// cov_dcov on the squared distance with the device forms above (identical formulas)
+// cov_dcov on the distance with the device exp above (identical formulas)
 template <int COV>
-__device__ __forceinline__ void cov_dcov_sq(double s, double var, double phi, double& c, double& dc,
-                                            const ExpCoef& k = ExpCoef{}) {
-  const double r = sqrt_nonneg(s);
+__device__ __forceinline__ void cov_dcov_r(double r, double var, double phi, double& c, double& dc,
+                                           const ExpCoef& k = ExpCoef{}) {
   if constexpr (COV == kMatern05) {
     const double e = exp_nonpos(-phi * r, k);
     c = var * e;
@@ -108,6 +107,13 @@ __device__ __forceinline__ void cov_dcov_sq(double s, double var, double phi, do
     c = var * e;
     dc = -phi * r * r * c;
   }
+}
+
+// ... and on the squared distance: the device sqrt, then the form above
+template <int COV>
+__device__ __forceinline__ void cov_dcov_sq(double s, double var, double phi, double& c, double& dc,
+                                            const ExpCoef& k = ExpCoef{}) {
+  cov_dcov_r<COV>(sqrt_nonneg(s), var, phi, c, dc, k);
 }
 
 }  // namespace gpb_amd

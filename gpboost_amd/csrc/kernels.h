@@ -28,12 +28,21 @@ struct VecchiaRowsArgs {
   int sched;             // 16-lane kernel, grid grid G < problem sets: 0 = wave w takes sets w, w + G, ...;
                          // 1 = the last, partial round's sets spread evenly over the waves;
                          // 2 = as 0 with G = ceil(sets / rounds) (every wave the same count)
+  const double* R;       // 16-lane kernel, optional: the pair distances of phase 1, kRows16DistDoubles per row,
+                         // indexed from row_base as nbr is (layout: vecchia_rows16.hip); null: computed per launch
 };
+
+// Stored pair distances of the 16-lane row kernel: 15 deltas x 16 lanes x 2 slots per row (3840 bytes)
+constexpr int kRows16DistDoubles = 15 * 16 * 2;
 
 int vecchia_rows_blocks(int rows, int m);   // upper bound of the grid (block-partial buffer size)
 int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);   // returns the grid size
 // 16-lane form for m <= 30 (vecchia_rows16.hip; DPP broadcasts, four rows per wave), same contract
 int launch_vecchia_rows16(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);
+// True when launch_vecchia_rows would run the 16-lane form for this m (the A/B environment switches included)
+bool vecchia_rows16_selected(int m);
+// The distances of rows a.r0..a.r1 (a.X, a.nbr, a.d, a.m, a.row_base) into R, indexed as VecchiaRowsArgs::R
+void launch_vecchia_rows16_dist(const VecchiaRowsArgs& a, double* R, hipStream_t s);
 // Predictions from the prediction rows' factor: out[p] = -sum_r B[p, r] y[nbr[p, r]] (mean),
 // out[n_pred + p] = (1 / Dinv[p] - nugget_sub) * sigma2 (variance). B, nbr: n_pred x m.
 void launch_predict_mean_var(int n_pred, int m, const int* nbr, const double* B, const double* Dinv, const double* y,

@@ -312,6 +312,7 @@ void REModelAMD::BuildVecchiaStructure() {
   // Only this rank's rows are needed on the device (each row's neighbours are earlier points).
   nbr_.assign((size_t)(row_end_ - row_begin_) * m, -1);
   nbr_row0_ = row_begin_;
+  d_rows_dist_.release();   // distances of the old neighbour sets / row block; rebuilt at the next row launch
   static const bool host_knn = std::getenv("GPBOOST_AMD_HOST_KNN") != nullptr;   // A/B: host OpenMP search
   if (host_knn || m > 64 || cfg_.d > 3)
     vecchia_neighbors(coords_vo_.data(), n, cfg_.d, m, row_begin_, row_end_, nbr_.data());
@@ -1302,11 +1303,59 @@ void REModelAMD::SetY(const double* y) {
   y_set_ = true;
 }
 
+// GPBOOST_AMD_ROWS16_DIST=0: the 16-lane kernel computes the distances at every launch (A/B and tests).
+// GPBOOST_AMD_ROWS16_DIST_MB: cap of the buffer in MB (default 4096, about 1.1 M rows; 0: never store);
+// a model over the cap keeps the on-the-fly kernel. Both are read at every launch, as GPBOOST_AMD_ROWS16 is.
+const double* REModelAMD::RowsDist() {
+  const int m = cfg_.num_neighbors, rows = row_end_ - row_begin_;
+  if (cfg_.latent || rows <= 0 || !vecchia_rows16_selected(m)) return nullptr;
+  const char* e = std::getenv("GPBOOST_AMD_ROWS16_DIST");
+  if (e != nullptr && e[0] == '0') return nullptr;
+  const char* c = std::getenv("GPBOOST_AMD_ROWS16_DIST_MB");
+  const double cap_mb = c != nullptr ? std::atof(c) : 4096.;
+  const size_t count = (size_t)rows * kRows16DistDoubles;
+  if ((double)count * sizeof(double) > cap_mb * 1048576.) {
+    d_rows_dist_.release();
+    return nullptr;
+  }
+  if (d_rows_dist_.size() != count) {
+    d_rows_dist_.alloc(count);
+    VecchiaRowsArgs a{};
+    a.X = d_X_.get();
+    a.nbr = d_nbr_.get();
+    a.n = cfg_.n; a.d = cfg_.d; a.m = m; a.r0 = row_begin_; a.r1 = row_end_;
+    hipEvent_t t0, t1;
+    HIP_CHECK(hipEventCreate(&t0));
+    HIP_CHECK(hipEventCreate(&t1));
+    HIP_CHECK(hipEventRecord(t0, stream_));
+    // indexed by global row, as nbr is: row row_begin_ sits at the head of the buffer
+    launch_vecchia_rows16_dist(a, d_rows_dist_.get() - (size_t)row_begin_ * kRows16DistDoubles, stream_);
+    HIP_CHECK(hipEventRecord(t1, stream_));
+    HIP_CHECK(hipEventSynchronize(t1));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+    rows_dist_ms_ = ms;
+    HIP_CHECK(hipEventDestroy(t0));
+    HIP_CHECK(hipEventDestroy(t1));
+  }
+  return d_rows_dist_.get() - (size_t)row_begin_ * kRows16DistDoubles;
+}
+
+void REModelAMD::GetVecchiaRowsInfo(double* out) {
+  if (!vecchia_) Fatal("model does not use the Vecchia approximation");
+  const bool stored = d_rows_dist_.size() > 0;
+  out[0] = stored ? 1. : 0.;
+  out[1] = (double)(d_rows_dist_.size() * sizeof(double));
+  out[2] = stored ? (double)(d_rows_dist_.size() / kRows16DistDoubles) : 0.;
+  out[3] = stored ? rows_dist_ms_ : 0.;
+}
+
 void REModelAMD::LaunchVecchiaRows(const double* trafo, int r0, int r1, double* sums, bool allreduce) {
   VecchiaRowsArgs a{};
   a.X = d_X_.get();
   a.Y = d_y_.get();
   a.nbr = d_nbr_.get();
+  a.R = RowsDist();
   a.n = cfg_.n;
   a.d = cfg_.d;
   a.m = cfg_.num_neighbors;
@@ -1578,6 +1627,7 @@ void REModelAMD::GetVecchiaFactor(const double* cov_pars_orig, double* Dinv, dou
   a.diag_mult = 1.; a.diag_add = 1.; a.d_nugget = 1.;
   a.Dinv_out = dD.get();
   a.B_out = dB.get();
+  a.R = RowsDist();
   launch_vecchia_rows(cfg_.cov_type, a, stream_);
   HIP_CHECK(hipMemcpyAsync(Dinv, dD.get(), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipMemcpyAsync(Bvals, dB.get(), sizeof(double) * n * m, hipMemcpyDeviceToHost, stream_));

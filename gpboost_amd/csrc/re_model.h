@@ -131,6 +131,8 @@ class REModelAMD {
 
   void GetVecchiaStructure(int* perm, int* nbr) const;
   void GetVecchiaFactor(const double* cov_pars_orig, double* Dinv, double* Bvals);
+  // [stored (0/1), bytes, rows, build ms] of the 16-lane row kernel's stored pair distances (EXTENSION)
+  void GetVecchiaRowsInfo(double* out);
   // Latent factor with range derivatives (EXTENSION, latent models only).
   void GetLatentVecchiaFactor(const double* cov_pars_orig, double* Dinv, double* Bvals, double* dD, double* dBvals);
   // [newton iterations, mode-finding CG iterations, Lanczos steps, log|Sigma W + I|] of the last latent eval
@@ -295,6 +297,7 @@ class REModelAMD {
   void BuildVecchiaStructure();
   void EvalVecchia(const double* trafo, double* sums);  // sums over this rank's rows, all-reduced
   void LaunchVecchiaRows(const double* trafo, int r0, int r1, double* sums_host, bool allreduce);
+  const double* RowsDist();   // VecchiaRowsArgs::R of this rank's rows (built on first use), or null
   void EvalDense(const double* trafo, bool want_grad, double* sums);
   // "none" and "fitc" share the Gaussian Cholesky bookkeeping (dense_ or fitc_)
   void EvalExactGaussian(const double* trafo, bool want_grad, double* sums);
@@ -321,6 +324,12 @@ class REModelAMD {
   hipEvent_t ev_[3] = {nullptr, nullptr, nullptr};
   DevBuf<double> d_X_, d_y_, d_block_sums_, d_sums_;
   DevBuf<int> d_nbr_;
+  // The pair distances the 16-lane row kernel reads instead of recomputing them at every evaluation
+  // (kRows16DistDoubles per row of this rank's block; they depend on the coordinates and the neighbour
+  // sets alone, so they live and die with the structure). The reference keeps the same distances from
+  // construction on (dist_obs_neighbors / dist_between_neighbors, Vecchia_utils.h).
+  DevBuf<double> d_rows_dist_;
+  double rows_dist_ms_ = 0.;   // the one-time distance kernel, by HIP events
   double* h_sums_ = nullptr;  // pinned
   double* h_sums_dev_ = nullptr;  // device address of h_sums_ (the single-rank sum kernel writes it directly)
   unsigned long long sum_seq_ = 0;  // completion flag value of the last single-rank evaluation (h_sums_[8])

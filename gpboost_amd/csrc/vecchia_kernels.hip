@@ -997,6 +997,11 @@ bool rows16() {
   return e == nullptr || e[0] != '0';
 }
 
+bool rows_prof() {
+  static const bool prof = std::getenv("GPBOOST_AMD_ROWS_PROF") != nullptr;
+  return prof;
+}
+
 template <int K>
 int rows_per_block() { return use_v4(K) ? 64 / (K / 2) : (block_threads<K>() / 64) * (64 / K); }
 
@@ -1057,7 +1062,7 @@ int launch_k(const VecchiaRowsArgs& a, hipStream_t s) {
   }
   size_t lds = (size_t)rpb * group_lds_doubles<K>() * sizeof(double);
   if (lds < red) lds = red;
-  static const bool prof = std::getenv("GPBOOST_AMD_ROWS_PROF") != nullptr;
+  const bool prof = rows_prof();
   const bool dpp = rows_dpp();
   if constexpr (K == 32) {
     if (!prof && a.m <= 30) {   // the headline configuration (m = 30): 30 elimination steps
@@ -1116,6 +1121,10 @@ int launch_cov(int cov, const VecchiaRowsArgs& a, hipStream_t s) {
 int vecchia_rows_blocks(int rows, int m) {
   if (lanes_for_m(m) == 0) Fatal("num_neighbors = %d > 64 is not supported by the GPU Vecchia kernel", m);
   return std::min(std::max(rows, 1), kMaxBlocksAny);   // >= any launch's grid (one row group per block at least)
+}
+
+bool vecchia_rows16_selected(int m) {   // launch_k<32>'s choice
+  return lanes_for_m(m) == 32 && m <= 30 && !rows_prof() && rows16() && !rows_dpp() && !rows_slots();
 }
 
 int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s) {

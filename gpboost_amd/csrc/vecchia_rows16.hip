@@ -31,6 +31,10 @@
 //      a_v = M[v][30] / M[v][v], w_v = M[v][31] / M[v][v] (the pivots are captured when broadcast);
 //   3. a^T dC a and w^T dC a over each lane's circulant pairs ([a, w] pairs with the same wrap copies);
 //   4. the eight group sums by DPP within the 16-lane row, then the six row partials.
+// Two kernels run this loop (rows16_body): vecchia_rows16_kernel computes every pair's distance from the
+// coordinates as described in 1.; vecchia_rows16d_kernel (VecchiaRowsArgs::R set) reads the distances
+// that vecchia_rows16_dist_kernel stored once per structure, loaded one problem set ahead, and holds no
+// coordinates at all. Both feed the same bits to the same operation sequence.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -59,6 +63,9 @@ constexpr int kD3 = 3;   // coordinate dimension bound (VecchiaRowsArgs.d <= 3)
 //     entry (about 290 VALU ops per problem set): 5616 vs 5458;
 //   - exp's constants held in scalar registers across the loop (ExpCoef::scalar(), cov.h) instead of
 //     64-bit VALU moves at each use (63 per problem set): 5616 vs 5500.
+//   - the pair distances stored per structure and streamed (profiles/rows16_dist/RESULTS.md; the parent's
+//     spread 28): 6378 vs 5628, 2183 instead of 2661 VALU instructions per problem set for 384 MB more HBM
+//     reads per launch at n = 100k. Non-temporal loads of the records: 6241 vs 6230, inside the noise.
 // Rejected: the next pivot's broadcast, reciprocal and multipliers issued after the step's first three
 // columns and left to the compiler to schedule under the rest of the step's fmacs (it did interleave
 // them): 5616 with vs 5628 without, inside the noise; round 4 had measured the hand-pinned form slower.
@@ -159,13 +166,75 @@ constexpr int kPacked = kK * (kK + 1) / 2;   // 528
 template <int CS>
 constexpr int problem_doubles() { return kPacked + 48 * CS; }   // packed C (then dC) | 48 coordinate rows
 
-template <int COV, int DIM>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) vecchia_rows16_kernel(VecchiaRowsArgs a) {
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+// ---- the pieces of phase 1 that do not depend on the covariance parameters, shared by the row kernel
+// and the distance kernel below (the same source, so the stored distances are the bits the row kernel
+// computes on the fly)
+
+// Coordinates of the row's own point and of slots h and h + 16. Padding slots sit at distinct far-away
+// points: covariances exactly 0 (see vecchia_rows_kernel); slot 30 (lane 14's second slot) is the row's
+// own point, lane 15's second slot (31) holds no point.
+template <int ND>
+__device__ __forceinline__ void load_points(const VecchiaRowsArgs& a, int d, int irow, int h, bool rv0, bool rv1,
+                                            int nb0, int nb1, double (&xi)[ND], double (&x0)[ND], double (&x1)[ND]) {
+#pragma unroll
+  for (int q = 0; q < ND; ++q) {
+    xi[q] = (q < d) ? a.X[(size_t)irow * d + q] : 0.;
+    x0[q] = (q < d && rv0) ? a.X[(size_t)nb0 * d + q] : 0.;
+    x1[q] = (q < d && rv1) ? a.X[(size_t)nb1 * d + q] : 0.;
+  }
+}
+
+template <int ND>
+__device__ __forceinline__ void pad_points(int h, bool rv0, bool rv1, const double (&xi)[ND], double (&x0)[ND],
+                                           double (&x1)[ND]) {
+  const int v1 = h + 16;
+  const bool own1 = v1 == kMK;
+#pragma unroll
+  for (int q = 0; q < ND; ++q) x1[q] = own1 ? xi[q] : x1[q];
+  x0[0] = rv0 ? x0[0] : 1e30 * (h + 1);
+  x1[0] = (rv1 || own1) ? x1[0] : 1e30 * (v1 + 1);
+}
+
+// ... into the problem's 48 coordinate rows: partners past slot 30 wrap, copies of slots 0..15 at 31..46
+template <int ND>
+__device__ __forceinline__ void put_points(double* nbx, int h, const double (&x0)[ND], const double (&x1)[ND]) {
+  const int v1 = h + 16;
+#pragma unroll
+  for (int q = 0; q < ND; ++q) {
+    nbx[h * ND + q] = x0[q];
+    nbx[(h + 31) * ND + q] = x0[q];
+    if (v1 <= kMK) nbx[v1 * ND + q] = x1[q];
+  }
+}
+
+template <int ND>
+__device__ __forceinline__ double sq_dist(const double (&x)[ND], const double* xp) {
+  double s = 0.;
+#pragma unroll
+  for (int q = 0; q < ND; ++q) {
+    const double t = x[q] - xp[q];
+    s += t * t;
+  }
+  return s;
+}
+
+// Stored distances (VecchiaRowsArgs::R): row i owns 15 x 16 records of two doubles, record (q, h) =
+// { r(h, q + 1), r(h + 16, q + 1) }, r(v, delta) the distance of slot v's pair at that delta as phase 1
+// computes it (wrap copies, slot 30 and the padding points included). A wave's 16-byte load of one q
+// reads four contiguous 256-byte segments, one per row of the set.
+constexpr int kDistRecs = 15 * 16;   // v2d records per row (kRows16DistDoubles = 2 kDistRecs)
+static_assert(2 * kDistRecs == kRows16DistDoubles, "record layout");
+
+// The row kernel's loop, in two forms: STORED = false computes every pair's distance from the
+// coordinates (DIM = 2 or 0 for the generic d <= 3); STORED = true reads it from a.R (DIM unused).
+template <int COV, int DIM, bool STORED>
+__device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
   constexpr int ND = DIM > 0 ? DIM : kD3;
-  constexpr int CS = ND;
+  constexpr int CS = STORED ? 2 : ND;   // stored: the area holds only the stash and the [a, w] array (96 doubles)
   constexpr int PD = problem_doubles<CS>();
   static_assert(PD % 2 == 0, "16-byte aligned problems");
-  typedef double v2d __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int g = lane >> 4;
@@ -175,7 +244,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const double cdiag = var * a.diag_mult + a.diag_add;
   const double delta = cdiag - var;
   const bool want_like = a.Y != nullptr;
-  const int d = DIM > 0 ? DIM : a.d;
+  [[maybe_unused]] const int d = DIM > 0 ? DIM : a.d;
 
   // the row partials accumulate in LDS (4 problems x 6 doubles after the problems' areas): a register
   // accumulator would be live across the elimination, where the registers run out
@@ -193,8 +262,30 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const long lo = (long)w * E / G, hi = (long)(w + 1) * E / G;
     last_set = hi > lo ? (R - 1) * G + (int)lo : nsets;
   }
+  auto set_at = [&](int it) { return it + 1 < R ? it * G + w : last_set; };
+  // Stored form, software pipeline: a set's neighbour indices and its 15 distance records per lane (60
+  // VGPRs) are loaded one set ahead, right after the elimination, when the 128 row registers are dead;
+  // the traces, the sums, the next gather and the SIMD's other wave cover the stream. The indices go
+  // first: the gather's Y loads wait for them alone (loads return in order), the records are waited for
+  // at the first pair. Rows past r1 in a partial last set read row r0's records.
+  v2d rr[STORED ? 15 : 1];
+  int pnb0 = 0, pnb1 = 0;
+  auto prefetch = [&](int set) {
+    if constexpr (STORED) {
+      const int h = lane & 15;
+      const int i = a.r0 + set * 4 + g;
+      const bool active = i < a.r1;
+      const int k = active ? min(i, a.m) : 0;
+      pnb0 = h < k ? a.nbr[(size_t)(i - a.row_base) * a.m + h] : 0;
+      pnb1 = h + 16 < k ? a.nbr[(size_t)(i - a.row_base) * a.m + h + 16] : 0;
+      const v2d* rp = reinterpret_cast<const v2d*>(a.R) + (size_t)((active ? i : a.r0) - a.row_base) * kDistRecs + h;
+#pragma unroll
+      for (int q = 0; q < 15; ++q) rr[q] = rp[q * 16];
+    }
+  };
+  if (set_at(0) < nsets) prefetch(set_at(0));
   for (int it = 0; it < R; ++it) {
-    const int set = it + 1 < R ? it * G + w : last_set;
+    const int set = set_at(it);
     if (set >= nsets) break;
     const int base = set * 4;
     int h = lane & 15;
@@ -207,32 +298,22 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int irow = active ? i : a.r0;
 
     // ---- gather (rows h and h + 16)
-    const int nb0 = rv0 ? a.nbr[(size_t)(i - a.row_base) * a.m + h] : 0;
-    const int nb1 = rv1 ? a.nbr[(size_t)(i - a.row_base) * a.m + v1] : 0;
+    int nb0, nb1;
     double xi[ND], x0[ND], x1[ND];
-#pragma unroll
-    for (int q = 0; q < ND; ++q) {
-      xi[q] = (q < d) ? a.X[(size_t)irow * d + q] : 0.;
-      x0[q] = (q < d && rv0) ? a.X[(size_t)nb0 * d + q] : 0.;
-      x1[q] = (q < d && rv1) ? a.X[(size_t)nb1 * d + q] : 0.;
+    if constexpr (STORED) {
+      nb0 = pnb0;
+      nb1 = pnb1;
+    } else {
+      nb0 = rv0 ? a.nbr[(size_t)(i - a.row_base) * a.m + h] : 0;
+      nb1 = rv1 ? a.nbr[(size_t)(i - a.row_base) * a.m + v1] : 0;
+      load_points<ND>(a, d, irow, h, rv0, rv1, nb0, nb1, xi, x0, x1);
     }
     const double yi = want_like ? a.Y[irow] : 0.;
     double y0s = (want_like && rv0) ? a.Y[nb0] : 0.;
     double y1s = (want_like && rv1) ? a.Y[nb1] : 0.;
-    // padding rows at distinct far-away points: covariances exactly 0 (see vecchia_rows_kernel); slot
-    // 30 (lane 14's second slot) is the row's own point, lane 15's second slot (31) holds no point
-    const bool own1 = v1 == kMK;
-#pragma unroll
-    for (int q = 0; q < ND; ++q) x1[q] = own1 ? xi[q] : x1[q];
-    x0[0] = rv0 ? x0[0] : 1e30 * (h + 1);
-    x1[0] = (rv1 || own1) ? x1[0] : 1e30 * (v1 + 1);
+    if constexpr (!STORED) pad_points<ND>(h, rv0, rv1, xi, x0, x1);
     cfence();   // the previous problem's LDS reads are issued before these writes
-#pragma unroll
-    for (int q = 0; q < ND; ++q) {
-      nbx[h * CS + q] = x0[q];
-      nbx[(h + 31) * CS + q] = x0[q];   // partners past slot 30 wrap: copies of slots 0..15 at 31..46
-      if (v1 <= kMK) nbx[v1 * CS + q] = x1[q];
-    }
+    if constexpr (!STORED) put_points<ND>(nbx, h, x0, x1);
     Cp[tri(h) + h] = rv0 ? cdiag : 1.;
     Cp[tri(v1) + v1] = rv1 ? cdiag : 1.;   // slots 30, 31: 1 (border rows, not pivots)
     lds_sync();
@@ -243,29 +324,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       const int b0 = tri(h) + h, b1 = tri(v1) + v1;
 #pragma unroll
       for (int dl = 1; dl <= 15; ++dl) {
-        const double* xp = nbx + (h + dl) * CS;
-        double s = 0.;
-#pragma unroll
-        for (int q = 0; q < ND; ++q) {
-          const double t = x0[q] - xp[q];
-          s += t * t;
-        }
         double cv, dcv;
-        cov_dcov_sq<COV>(s, var, phi, cv, dcv, ek);
+        if constexpr (STORED) cov_dcov_r<COV>(rr[dl - 1].x, var, phi, cv, dcv, ek);
+        else cov_dcov_sq<COV>(sq_dist<ND>(x0, nbx + (h + dl) * CS), var, phi, cv, dcv, ek);
         Cp[b0 + h * dl + dl * (dl + 1) / 2] = cv;   // packed(h + dl, h)
         w0[dl - 1] = dcv;
       }
 #pragma unroll
       for (int dl = 1; dl <= 15; ++dl) {
-        const double* xp = nbx + (v1 + dl) * CS;
-        double s = 0.;
-#pragma unroll
-        for (int q = 0; q < ND; ++q) {
-          const double t = x1[q] - xp[q];
-          s += t * t;
-        }
         double cv, dcv;
-        cov_dcov_sq<COV>(s, var, phi, cv, dcv, ek);
+        if constexpr (STORED) cov_dcov_r<COV>(rr[dl - 1].y, var, phi, cv, dcv, ek);
+        else cov_dcov_sq<COV>(sq_dist<ND>(x1, nbx + (v1 + dl) * CS), var, phi, cv, dcv, ek);
         // packed(v1 + dl, v1), or past slot 30 packed(v1, v1 + dl - 31) (slot 31: row 31, overwritten below)
         const int pos = (v1 + dl <= kMK) ? b1 + v1 * dl + dl * (dl + 1) / 2 : b1 + dl - 31;
         Cp[pos] = cv;
@@ -388,6 +457,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         fmac_bcast16<j>(r0[kMK + 1], r0[kMK + 1], r0[j]);
       });
     }
+    if constexpr (STORED) {   // the row registers are dead: the next set's loads go out here
+      cfence();
+      // no branch around the loads (the records just consumed would stay live through the elimination on the
+      // path that skips them): the wave's last set loads its own records again
+      const int nxt = it + 1 < R ? set_at(it + 1) : nsets;
+      prefetch(nxt < nsets ? nxt : set);
+    }
     {   // the stashed c, y_nbr back (read before the [a, w] array below overwrites the area); dc_v = dC(v, 30):
         // the slot-30 pair at delta = v + 1 (v <= 14), slot v's pair at delta = 30 - v (v = 15..29)
       lds_sync();
@@ -468,19 +544,63 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 
+template <int COV, int DIM>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) vecchia_rows16_kernel(VecchiaRowsArgs a) {
+  rows16_body<COV, DIM, false>(a);
+}
+
+// The stored-distance form (a.R set): no coordinate is read, so one instantiation serves every d.
+template <int COV>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) vecchia_rows16d_kernel(VecchiaRowsArgs a) {
+  rows16_body<COV, 2, true>(a);
+}
+
+// The distances of rows r0..r1, once per structure: phase 1's gather, padding, wrap copies and squared
+// distance, then the device sqrt, written in the record layout above. Four rows per wave as in the row
+// kernel, a set per wave and grid stride.
+template <int DIM>
+__global__ void __launch_bounds__(64) vecchia_rows16_dist_kernel(VecchiaRowsArgs a, double* R) {
+  constexpr int ND = DIM > 0 ? DIM : kD3;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int lane = threadIdx.x;
+  const int g = lane >> 4, h = lane & 15, v1 = h + 16;
+  double* nbx = smem + g * 48 * ND;
+  const int d = DIM > 0 ? DIM : a.d;
+  const int nsets = (a.r1 - a.r0 + 3) / 4;
+  for (int set = blockIdx.x; set < nsets; set += gridDim.x) {
+    const int i = a.r0 + set * 4 + g;
+    const bool active = i < a.r1;
+    const int k = active ? min(i, a.m) : 0;
+    const bool rv0 = h < k, rv1 = v1 < k;
+    const int irow = active ? i : a.r0;
+    const int nb0 = rv0 ? a.nbr[(size_t)(i - a.row_base) * a.m + h] : 0;
+    const int nb1 = rv1 ? a.nbr[(size_t)(i - a.row_base) * a.m + v1] : 0;
+    double xi[ND], x0[ND], x1[ND];
+    load_points<ND>(a, d, irow, h, rv0, rv1, nb0, nb1, xi, x0, x1);
+    pad_points<ND>(h, rv0, rv1, xi, x0, x1);
+    cfence();   // the previous set's LDS reads are issued before these writes
+    put_points<ND>(nbx, h, x0, x1);
+    lds_sync();
+    v2d* out = reinterpret_cast<v2d*>(R) + (size_t)(irow - a.row_base) * kDistRecs + h;
+#pragma unroll
+    for (int dl = 1; dl <= 15; ++dl) {
+      const double ra = sqrt_nonneg(sq_dist<ND>(x0, nbx + (h + dl) * ND));
+      const double rb = sqrt_nonneg(sq_dist<ND>(x1, nbx + (v1 + dl) * ND));
+      if (active) out[(dl - 1) * 16] = v2d{ra, rb};
+    }
+  }
+}
+
 constexpr int kMaxGrid = 2048;   // vecchia_rows_blocks' bound (kernels.h)
 
-template <int COV, int DIM>
-int launch16(const VecchiaRowsArgs& a, hipStream_t s) {
-  constexpr int CS = DIM > 0 ? DIM : kD3;
-  const size_t lds = (size_t)(4 * problem_doubles<CS>() + 4 * kVecchiaSums) * sizeof(double);
-  auto kern = vecchia_rows16_kernel<COV, DIM>;
-  static int cap = 0;
+template <auto KERN>
+int launch16_at(size_t lds, const VecchiaRowsArgs& a, hipStream_t s) {
+  static int cap = 0;   // per kernel instance
   if (cap == 0) {
     int dev = 0, cus = 0, per_cu = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, lds));
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERN, 64, lds));
     cap = std::max(1, std::min(per_cu * cus, kMaxGrid));
   }
   const int need = (a.r1 - a.r0 + 3) / 4;
@@ -489,9 +609,17 @@ int launch16(const VecchiaRowsArgs& a, hipStream_t s) {
     const int rounds = (need + blocks - 1) / blocks;
     blocks = (need + rounds - 1) / rounds;
   }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, s, a);
+  hipLaunchKernelGGL(KERN, dim3(blocks), dim3(64), lds, s, a);
   HIP_CHECK(hipGetLastError());
   return blocks;
+}
+
+template <int COV, int DIM>
+int launch16(const VecchiaRowsArgs& a, hipStream_t s) {
+  if (a.R != nullptr)
+    return launch16_at<vecchia_rows16d_kernel<COV>>((size_t)(4 * problem_doubles<2>() + 4 * kVecchiaSums) * sizeof(double), a, s);
+  constexpr int CS = DIM > 0 ? DIM : kD3;
+  return launch16_at<vecchia_rows16_kernel<COV, DIM>>((size_t)(4 * problem_doubles<CS>() + 4 * kVecchiaSums) * sizeof(double), a, s);
 }
 
 }  // namespace
@@ -508,6 +636,16 @@ int launch_vecchia_rows16(int cov_type, const VecchiaRowsArgs& a, hipStream_t s)
     default: Fatal("unsupported covariance type %d", cov_type);
   }
   return 0;
+}
+
+void launch_vecchia_rows16_dist(const VecchiaRowsArgs& a, double* R, hipStream_t s) {
+  if (a.m > kMK) Fatal("16-lane row kernel: num_neighbors %d > %d", a.m, kMK);
+  if (a.d < 1 || a.d > kD3) Fatal("16-lane row kernel: dim_gp_coords %d", a.d);
+  if (a.r1 <= a.r0) return;
+  const int blocks = std::min((a.r1 - a.r0 + 3) / 4, 1 << 16);
+  if (a.d == 2) hipLaunchKernelGGL(vecchia_rows16_dist_kernel<2>, dim3(blocks), dim3(64), 4 * 48 * 2 * sizeof(double), s, a, R);
+  else hipLaunchKernelGGL(vecchia_rows16_dist_kernel<0>, dim3(blocks), dim3(64), 4 * 48 * kD3 * sizeof(double), s, a, R);
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpb_amd

@@ -329,6 +329,11 @@ GPBOOST_AMD_EXPORT int GPB_GetVecchiaStructure(REModelHandle handle, int32_t* pe
 GPBOOST_AMD_EXPORT int GPB_GetVecchiaFactor(REModelHandle handle, const double* cov_pars,
     double* D_inv, double* B_vals);
 
+/* Stored pair distances of the exact Vecchia row kernel (num_neighbors 17..30; built at the first
+ * evaluation): out[0] 1 if this model holds them, out[1] their bytes of device memory, out[2] the
+ * rows they cover (this rank's), out[3] the milliseconds the one-time distance kernel took. */
+GPBOOST_AMD_EXPORT int GPB_GetVecchiaRowsInfo(REModelHandle handle, double* out);
+
 /* Latent Vecchia factor at cov_pars = (sigma1^2, rho) (latent models): D^-1 (n), B values
  * (n x num_neighbors) and their derivatives with respect to log(range transform)
  * (Vecchia_utils.cpp:1307-1632 with gauss_likelihood = false). Computed on the GPU. */

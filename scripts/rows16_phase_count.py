@@ -1,13 +1,14 @@
 """Static instruction counts of the 16-lane Vecchia row kernel's loop body, by phase.
 
-    python scripts/rows16_phase_count.py [CSRC_DIR] [-DNAME=VALUE ...]
+    python scripts/rows16_phase_count.py [CSRC_DIR] [-DNAME=VALUE ...] [--kernel=MANGLED_PREFIX]
 
 Copies vecchia_rows16.hip from CSRC_DIR (default: gpboost_amd/csrc) to a temporary directory with an
 assembler comment inserted at each phase boundary (an empty volatile asm: it orders against the other
 volatile asm statements and memory operations, plain arithmetic may still drift a few instructions
 across it), compiles it for gfx950 with build.py's flags and counts, for
 vecchia_rows16_kernel<matern05, DIM = 2>, the instructions of one trip of the problem-set loop
-between the markers. Prints a markdown table.
+between the markers. --kernel names another instantiation by the head of its mangled name, e.g.
+--kernel=vecchia_rows16d_kernelILi0E for the stored-distance form. Prints a markdown table.
 """
 import collections
 import os
@@ -19,7 +20,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = sys.argv[1:]
 defs = [a for a in args if a.startswith("-D")]
-dirs = [a for a in args if not a.startswith("-D")]
+kern = [a.split("=", 1)[1] for a in args if a.startswith("--kernel=")]
+dirs = [a for a in args if not a.startswith("-")]
 csrc = os.path.abspath(dirs[0]) if dirs else os.path.join(ROOT, "gpboost_amd", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
@@ -53,7 +55,7 @@ with tempfile.TemporaryDirectory() as tmp:
     text = open(asm).read()
     remarks = r.stderr
 
-name = "vecchia_rows16_kernelILi0ELi2E"
+name = kern[0] if kern else "vecchia_rows16_kernelILi0ELi2E"
 body = text[text.index(f"{name}EEvNS_15VecchiaRowsArgsE:"):]
 body = body[:body.index("s_endpgm")]
 lines = body.split("\n")
