@@ -17,6 +17,7 @@
 
 #include "grouped_model.h"
 #include "re_model.h"
+#include "sparse_chol.h"
 
 using gpb_amd::GroupedModel;
 using gpb_amd::REModelAMD;
@@ -718,6 +719,104 @@ int GPB_TestDenseChol(int n, int ld, double* A, double* W, int want_inverse, dou
 int GPB_TestDenseSpdSolveInverse(int n, const double* A, const double* b, double* x, double* diag, double* inv) {
   API_BEGIN();
   gpb_amd::test_dense_spd_solve_inverse(n, A, b, x, diag, inv);
+  API_END();
+}
+
+int GPB_TestSparseCholPlan(int n, int m, const int32_t* nbr, int64_t nbr_len, int d, const double* X, int64_t x_len,
+                           const int64_t* opts, int t, int mode, int32_t* perm, int32_t* sfirst, int32_t* sparent,
+                           int64_t* rptr, int32_t* rows, int64_t rows_cap, int32_t* lvl_ptr, int32_t* lvl_sup,
+                           int64_t* stats, int64_t stats_len) {
+  API_BEGIN();
+  gpb_amd::test_sparse_chol_check_graph("GPB_TestSparseCholPlan", n, m, nbr, nbr_len, d, X, x_len);
+  if (perm == nullptr || sfirst == nullptr || sparent == nullptr || rptr == nullptr || lvl_ptr == nullptr ||
+      lvl_sup == nullptr || stats == nullptr)
+    gpb_amd::Fatal("GPB_TestSparseCholPlan: an output is NULL");
+  if (stats_len != gpb_amd::kTestCholStats)
+    gpb_amd::Fatal("GPB_TestSparseCholPlan: stats holds %lld entries, not %d", (long long)stats_len, gpb_amd::kTestCholStats);
+  gpb_amd::test_sparse_chol_plan(n, m, nbr, d, X, gpb_amd::test_sparse_chol_options(opts), t, mode, perm, sfirst, sparent,
+                                 rptr, rows, rows_cap, lvl_ptr, lvl_sup, stats);
+  API_END();
+}
+
+static gpb_amd::TestSparseChol* test_chol(void* handle, const char* fn) {
+  if (handle == nullptr) gpb_amd::Fatal("%s: handle is NULL", fn);
+  return static_cast<gpb_amd::TestSparseChol*>(handle);
+}
+
+int GPB_TestSparseCholCreate(int n, int m, const int32_t* nbr, int64_t nbr_len, int d, const double* X, int64_t x_len,
+                             const int64_t* opts, void** out) {
+  API_BEGIN();
+  gpb_amd::test_sparse_chol_check_graph("GPB_TestSparseCholCreate", n, m, nbr, nbr_len, d, X, x_len);
+  if (out == nullptr) gpb_amd::Fatal("GPB_TestSparseCholCreate: out is NULL");
+  *out = new gpb_amd::TestSparseChol(n, m, nbr, d, X, gpb_amd::test_sparse_chol_options(opts));
+  API_END();
+}
+
+int GPB_TestSparseCholFree(void* handle) {
+  API_BEGIN();
+  delete static_cast<gpb_amd::TestSparseChol*>(handle);
+  API_END();
+}
+
+int GPB_TestSparseCholSetB(void* handle, const double* Bv, int64_t bv_len, const double* Dinv, int64_t dinv_len,
+                           const double* dBv, int64_t dbv_len, const double* dD, int64_t dd_len) {
+  API_BEGIN();
+  const char* fn = "GPB_TestSparseCholSetB";
+  gpb_amd::TestSparseChol* c = test_chol(handle, fn);
+  const int64_t nm = (int64_t)c->n() * c->m(), n = c->n();
+  if (Bv == nullptr || Dinv == nullptr || bv_len != nm || dinv_len != n)
+    gpb_amd::Fatal("%s: Bv / Dinv hold %lld / %lld entries, n m = %lld, n = %lld", fn, (long long)bv_len,
+                   (long long)dinv_len, (long long)nm, (long long)n);
+  if ((dBv == nullptr) != (dD == nullptr)) gpb_amd::Fatal("%s: dBv and dD go together", fn);
+  if (dBv != nullptr && (dbv_len != nm || dd_len != n))
+    gpb_amd::Fatal("%s: dBv / dD hold %lld / %lld entries, n m = %lld, n = %lld", fn, (long long)dbv_len, (long long)dd_len,
+                   (long long)nm, (long long)n);
+  c->SetB(Bv, Dinv, dBv, dD);
+  API_END();
+}
+
+int GPB_TestSparseCholFactor(void* handle, const double* W, int64_t w_len, int* out_info, double* logdet) {
+  API_BEGIN();
+  const char* fn = "GPB_TestSparseCholFactor";
+  gpb_amd::TestSparseChol* c = test_chol(handle, fn);
+  if (out_info == nullptr) gpb_amd::Fatal("%s: out_info is NULL", fn);
+  if (W != nullptr && w_len != c->n()) gpb_amd::Fatal("%s: W holds %lld entries, n = %d", fn, (long long)w_len, c->n());
+  *out_info = c->Factor(W, logdet);
+  API_END();
+}
+
+int GPB_TestSparseCholSolve(void* handle, int op, int nrhs, int inplace, const double* b, int64_t b_len, double* x,
+                            int64_t x_len) {
+  API_BEGIN();
+  const char* fn = "GPB_TestSparseCholSolve";
+  gpb_amd::TestSparseChol* c = test_chol(handle, fn);
+  if (op < 0 || op > 3 || nrhs < 1 || (op == 0 && nrhs != 1)) gpb_amd::Fatal("%s: op = %d, nrhs = %d", fn, op, nrhs);
+  const int64_t len = (int64_t)c->n() * nrhs;
+  if (b == nullptr || x == nullptr || b_len != len || x_len != len)
+    gpb_amd::Fatal("%s: b / x hold %lld / %lld entries, n nrhs = %lld", fn, (long long)b_len, (long long)x_len,
+                   (long long)len);
+  c->Solve(op, nrhs, inplace, b, x);
+  API_END();
+}
+
+int GPB_TestSparseCholSelectedInverse(void* handle, double* tr_bdb, double* tr_da, double* diagS, int64_t diag_len) {
+  API_BEGIN();
+  const char* fn = "GPB_TestSparseCholSelectedInverse";
+  gpb_amd::TestSparseChol* c = test_chol(handle, fn);
+  if (diagS != nullptr && diag_len != c->n())
+    gpb_amd::Fatal("%s: diagS holds %lld entries, n = %d", fn, (long long)diag_len, c->n());
+  c->SelectedInverse(tr_bdb, tr_da, diagS);
+  API_END();
+}
+
+int GPB_TestSparseCholDense(void* handle, int which, double* out, int64_t out_len) {
+  API_BEGIN();
+  const char* fn = "GPB_TestSparseCholDense";
+  gpb_amd::TestSparseChol* c = test_chol(handle, fn);
+  if (which < 0 || which > 2) gpb_amd::Fatal("%s: which = %d", fn, which);
+  if (out == nullptr || out_len != (int64_t)c->n() * c->n())
+    gpb_amd::Fatal("%s: out holds %lld entries, n n = %lld", fn, (long long)out_len, (long long)c->n() * c->n());
+  c->Dense(which, out);
   API_END();
 }
 

@@ -51,6 +51,12 @@ struct CholGemmTask {
   double alpha, beta;
 };
 constexpr int kCgTA = 1, kCgTB = 2, kCgLower = 4;
+// bit 3 (a launch of such tasks only): the factorization's panel step C = C L^-T in place by substitution
+// (chol_trsm_kernel; M <= 256 rows per task), L = the ib x ib diagonal block that starts doff rows above C's tile in C's buffer (N = K = ib,
+// ld ldc), B = its inverse (ld 64; the diagonal 1 / L_jj is what the kernel uses). The product C B^T is the same
+// matrix, but only normwise stable: entries of C L^-T that cancel to nearly zero would carry the rounding of the
+// large ones.
+constexpr int kCgTrsm = 8;
 inline int cg_bufs(int a, int b, int c) { return (a << 4) | (b << 7) | (c << 10); }
 // C (M x N <= 64 x 64, ld ldc, buffer bufc) = beta C + alpha sum_{q < nslices} P[p + q pstride] (slices M x N, ld M)
 struct CholReduceTask {
@@ -138,14 +144,27 @@ struct CholPlan {
 // Graph of A: vertex i's clique is {i} U nbr[i*m + r] for r < kcount(i) = min(i, m) (entries < 0
 // skipped). X: host coordinates row-major n x d (geometric bisection of the nested dissection).
 // leaf: largest subgraph left undivided.
+// The switches of the plan, the schedules and the launches. chol_default_options(): what the environment gives
+// (GPBOOST_AMD_CHOL_LEAF, GPBOOST_AMD_CHOL_K64 read at every call; GPBOOST_AMD_CHOL_SMALL_PANEL and
+// GPBOOST_AMD_CHOL_FWDVEC read once per process); the tests pass their own.
+struct CholOptions {
+  int leaf = 64;                  // nested dissection: largest subgraph left undivided
+  int64_t small_panel = 65536;    // t = 1: fs x ns of the largest panel a single-workgroup level sweep takes
+  bool fuse_vec = true;           // t = 1, larger panels: the fused vector kernels (false: the two-launch GEMM form)
+  bool k64 = true;                // GEMM launches of few tiles with K <= 64 on chol_gemm_k64_kernel
+  int poison = -1;                // tests: 0 / 1 = every scratch and output buffer of a phase filled with zeros / NaN
+                                  // before the phase runs; -1 = left as it is (production)
+};
+CholOptions chol_default_options();
 void chol_analyze(int n, int m, const int* nbr, int d, const double* X, int leaf, CholPlan& plan);
 // Schedule of a forward + backward solve with t right-hand sides (front vectors fs x t per supernode
 // in the scratch, ld fs; the global X is n x t, ld n, in elimination positions). vofs: per supernode
 // scratch offsets (nsup + 1). forward_only: stop after the forward sweep (L^-1 b left in the fronts,
 // scattered to X). backward_only: the backward sweep alone, its input (the layout a forward-only sweep
 // leaves in X) loaded into the fronts first.
+// opt: small_panel and fuse_vec (null: chol_default_options()).
 void chol_solve_schedule(const CholPlan& P, int t, bool forward_only, CholSchedule& S, std::vector<int64_t>& vofs,
-                         bool backward_only = false);
+                         bool backward_only = false, const CholOptions* opt = nullptr);
 
 // A's lower entries in the front layout and their clique contributions (host, once per plan):
 //   column g (elimination position) holds entries [ecol[g], ecol[g+1]) (rows ascending, the diagonal
@@ -165,7 +184,8 @@ class SparseChol {
  public:
   // nbr: host n x m neighbour table of the Vecchia factor (row i holds min(i, m) entries); X: host
   // coordinates row-major n x d. Builds the plan and the entry lists (host), uploads them.
-  SparseChol(int n, int m, const int* nbr, int d, const double* X, hipStream_t s);
+  // opt: null = chol_default_options().
+  SparseChol(int n, int m, const int* nbr, int d, const double* X, hipStream_t s, const CholOptions* opt = nullptr);
   ~SparseChol();
   SparseChol(const SparseChol&) = delete;
   SparseChol& operator=(const SparseChol&) = delete;
@@ -197,12 +217,19 @@ class SparseChol {
   void SelectedInverse(double* tr_bdb, double* tr_da, double* diagS);
   // device time of the last Factor (ms; HIP events; synchronises)
   float last_factor_ms();
+  // Tests: the factor (which = 0: exact zeros outside the structure) or the selected inverse (which = 1: NaN
+  // outside the lower structure; which = 2: the same entries read from their mirrored copies S[j][r] in the fronts)
+  // as a dense n x n column-major host array in elimination positions, expanded from the fronts through plan().
+  // Synchronises.
+  void TestDense(int which, double* out);
 
  private:
+  void Poison(int phase, double* out, size_t out_doubles);   // phase 0: Factor, 1: a solve, 2: SelectedInverse
   void Run(const SparseCholDev& sch, double* ybuf, const void* solve_args);
   void SolveCols(const double* b, double* x, int t, int mode);   // mode 0: full, 1: forward only, 2: backward only
   struct Impl;
   CholPlan plan_;
+  CholOptions opt_;
   hipStream_t s_;
   int n_ = 0, m_ = 0;
   std::unique_ptr<Impl> impl_;
@@ -221,6 +248,43 @@ class SparseChol {
   const double* cur_W_ = nullptr;
   bool has_dA_ = false, factored_ = false, timed_ = false;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
+};
+
+// Test entries (GPB_TestSparseChol*, include/gpboost_amd.h): host arrays in and out, every extent checked on the
+// host before any device call (a violation is a Fatal naming the entry point).
+// n >= 1, 1 <= m <= 254, d >= 1, nbr_len = n m, x_len = n d, -1 <= nbr[i m + r] < i for r < min(i, m)
+void test_sparse_chol_check_graph(const char* fn, int n, int m, const int* nbr, int64_t nbr_len, int d, const double* X,
+                                  int64_t x_len);
+// opts (nullable): {leaf, small_panel, fuse_vec, k64, poison}, an entry < 0 = chol_default_options()'s
+CholOptions test_sparse_chol_options(const int64_t* opts);
+constexpr int kCholNumOps = kOpBwdVecFin + 1;
+constexpr int kTestCholStats = 6 + 3 * (kCholNumOps + 2);
+// The plan alone (sparse_chol_sym.cpp: no HIP call). perm, sparent, lvl_sup: n entries; sfirst, lvl_ptr: n + 1
+// (nsup + 1 and levels + 1 used); rptr: n + 1 (nsup + 1 used); rows (nullable): rows_cap >= rptr[nsup] entries.
+// stats[kTestCholStats]: nsup, levels, max_fs, max_ns, nnz_l, rptr[nsup], then for the factor, the selected
+// inverse and the solve schedule of (t, mode; mode 0 full, 1 forward only, 2 backward only): the number of ops of
+// each CholOpType, the largest nslices of a CholReduceTask, the largest chunk count of a kOpBwdVecFin task.
+void test_sparse_chol_plan(int n, int m, const int* nbr, int d, const double* X, const CholOptions& opt, int t, int mode,
+                           int* perm, int* sfirst, int* sparent, int64_t* rptr, int* rows, int64_t rows_cap, int* lvl_ptr,
+                           int* lvl_sup, int64_t* stats);
+// A SparseChol on the null stream with its own device copies of the inputs and outputs.
+class TestSparseChol {
+ public:
+  TestSparseChol(int n, int m, const int* nbr, int d, const double* X, const CholOptions& opt);
+  void SetB(const double* Bv, const double* Dinv, const double* dBv, const double* dD);   // host n x m, n
+  int Factor(const double* W, double* logdet);   // W host n or null; returns Info(); logdet nullable
+  // op 0: Solve (nrhs = 1), 1: SolveMulti, 2: ForwardCols, 3: BackwardCols; b, x host n x nrhs; inplace: x aliases b
+  // on the device
+  void Solve(int op, int nrhs, int inplace, const double* b, double* x);
+  void SelectedInverse(double* tr_bdb, double* tr_da, double* diagS);   // each nullable; diagS host n
+  void Dense(int which, double* out) { chol_.TestDense(which, out); }
+  int n() const { return n_; }
+  int m() const { return m_; }
+
+ private:
+  int n_, m_;
+  SparseChol chol_;
+  DevBuf<double> Bv_, Dinv_, dBv_, dD_, W_, b_, x_, diag_;
 };
 
 // Helpers of the Cholesky Laplace path (sparse_chol.hip).

@@ -10,9 +10,10 @@
 //                   W on lane r, columns / rows split over the waves, the pivot column broadcast
 //                   through LDS, one barrier per step)
 //   chol_gemm       one 64 x 64 output tile per 256-thread workgroup, v_mfma_f64_16x16x4 on 4 waves
-//                   (2 x 2 MFMA tiles each), K staged through double-buffered LDS: TRSM (times W^T),
+//                   (2 x 2 MFMA tiles each), K staged through double-buffered LDS:
 //                   the panel updates, the update block U -= L21 L21^T (K = ns), the solves' block
 //                   steps and the selected inverse's products
+//   chol_trsm       the panel step, the rows below a diagonal block times L_bb^-T, by substitution (thread = row)
 //   chol_gather_s / chol_mirror / chol_asmv / chol_gather_x / chol_scatter_x: the selected inverse's
 //                   parent-to-child gathers, symmetric completion, and the solves' front vectors.
 // Reductions (log-determinant, traces) are two-pass with a fixed order: results are bitwise repeatable.
@@ -184,7 +185,9 @@ __global__ void __launch_bounds__(256) chol_reduce_kernel(const CholReduceTask* 
 
 // ---- one 64 x 64 diagonal block: L and W = L^-1 by four waves. Lane r of wave w holds row r of the block
 // at the columns x = 4k + w (L) and column r of W at the rows x = 4k + w. Step j: the wave owning column
-// j takes the pivot from lane j, scales its column (divisions, as the LLT) and its W row j, publishes
+// j takes the pivot from lane j, scales its column and its W row j by y = 1 / sqrt(pivot) (the hardware
+// estimate refined by two Newton steps; a pivot that is not positive and finite counts in info and is
+// replaced by 1, so the block stays free of new NaN), publishes
 // l_x = L[x][j] and W[j][r] to LDS; after one barrier every wave applies them to its columns of the
 // trailing matrix (A[r][x] -= l_r l_x) and its rows of W (W[x][r] -= l_x W[j][r]). The padding of a
 // partial block (ib < 64) is the identity.
@@ -215,10 +218,11 @@ __global__ void __launch_bounds__(256) chol_diag_kernel(const CholDiagTask* __re
       const int lo = __builtin_amdgcn_readlane(__double2loint(row[kj]), j);
       const int hi = __builtin_amdgcn_readlane(__double2hiint(row[kj]), j);
       const double p = __hiloint2double(hi, lo);
-      bad = bad || !(p > 0.);
+      const bool ok = p > 0. && p < __builtin_huge_val();   // +inf: rsq = 0 and 0 * inf = NaN in the Newton step
+      bad = bad || !ok;
       // y = 1 / sqrt(p) by the hardware estimate and two Newton steps, d = p y; the column and W row scaled by y
       // (multiplies instead of a square root and two IEEE divisions on the pivot chain)
-      const double ps = p > 0. ? p : 1., h = 0.5 * ps;
+      const double ps = ok ? p : 1., h = 0.5 * ps;
       double y = __builtin_amdgcn_rsq(ps);
       y = y * fma(-h * y, y, 1.5);
       y = y * fma(-h * y, y, 1.5);
@@ -428,6 +432,59 @@ __global__ void __launch_bounds__(256) chol_gemm_k64_kernel(const CholGemmTask* 
     acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
   }
   chol_gemm_epilogue(g, C, acc, wm, wn, lane);
+}
+
+// ---- the factorization's panel step (kCgTrsm tasks): X L_bb^T = F for up to 256 rows below a diagonal block, in
+// place, thread = row (M <= 256 here, unlike the 64 x 64 tiles of the products). Forward substitution along the
+// row, x_j = (f_j - sum_{k<j} x_k L[j][k]) / L_jj
+// (four partial sums, the division as a product with W[j][j] = 1 / L_jj from chol_diag_kernel), with L_bb broadcast
+// from LDS: componentwise backward stable, |x L_bb^T - f| <= gamma_ib |x||L_bb^T|, which the product with the explicit
+// inverse W_b^T is not. Only the lower triangle of L_bb is read (the upper one of a front is never written).
+__global__ void __launch_bounds__(256) chol_trsm_kernel(const CholGemmTask* __restrict__ tasks, int64_t t0, Bufs bufs) {
+  const CholGemmTask g = tasks[t0 + blockIdx.x];
+  if (g.M <= 0 || g.N <= 0) return;
+  double* C = bufs.p[(g.flags >> 10) & 7] + g.c;
+  const double* L = C - g.doff;
+  const double* W = bufs.p[(g.flags >> 7) & 7] + g.b;
+  const int ld = g.ldc, ib = g.N, lane = threadIdx.x;
+  __shared__ double Ls[64][66];   // even row stride: a row's entries pair up for 16-byte reads
+  __shared__ double dinv[64];
+  // the thread's row first (threads past M read row M - 1 and leave after the barrier), in flight with L_bb's loads
+  const int r = min(lane, g.M - 1);
+  double x[64];
+#pragma unroll
+  for (int j = 0; j < 64; ++j) x[j] = C[r + (size_t)min(j, ib - 1) * ld];
+  for (int e = lane; e < 64 * 64; e += 256) {
+    const int j = e & 63, k = e >> 6;
+    const int jc = min(j, ib - 1), kc = min(k, jc);
+    const double v = L[jc + (size_t)kc * ld];
+    Ls[j][k] = (j < ib && k <= j) ? v : 0.;
+  }
+  if (lane < 64) dinv[lane] = lane < ib ? W[lane * 65] : 1.;
+  __syncthreads();
+  if (lane >= g.M) return;   // (no barrier below)
+  // 16 columns per (uniform) branch, straight-line inside: row j of L_bb is read from LDS as a whole before its
+  // products (one LDS latency per column, not per product; the next rows' reads can move above), four partial sums.
+  // Columns >= ib of a ragged block compute on clamped copies and zeros and are not stored.
+#pragma unroll
+  for (int jb = 0; jb < 64; jb += 16) {
+    if (jb < ib) {
+#pragma unroll
+      for (int jj = 0; jj < 16; ++jj) {
+        const int j = jb + jj;
+        double l[64];
+#pragma unroll
+        for (int k = 0; k < j; ++k) l[k] = Ls[j][k];
+        double acc[4] = {x[j], 0., 0., 0.};
+#pragma unroll
+        for (int k = 0; k < j; ++k) acc[k & 3] = fma(-x[k], l[k], acc[k & 3]);
+        x[j] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) * dinv[j];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 64; ++j)
+    if (j < ib) C[lane + (size_t)j * ld] = x[j];
 }
 
 // ---- selected inverse: S_RR of supernode s from its parent's front (both triangles), R columns [c0, c1)
@@ -877,11 +934,14 @@ struct SparseCholDev {
   DevBuf<CholReduceTask> red;
   std::vector<CholOp> ops;
   std::vector<char> k64;   // per op: a GEMM launch of few tiles, all with K <= 64 (chol_gemm_k64_kernel)
+  std::vector<char> trsm;  // per op: a launch of kCgTrsm tasks (chol_trsm_kernel)
   int64_t y_doubles = 0, p_doubles = 0;
-  void Upload(const CholSchedule& S) {
+  void Upload(const CholSchedule& S, bool use_k64) {   // use_k64 = false: always the K-pipelined form (A/B)
     k64.assign(S.ops.size(), 0);
-    const char* e = std::getenv("GPBOOST_AMD_CHOL_K64");   // "0": always the K-pipelined form (A/B)
-    if (!(e && std::string(e) == "0"))
+    trsm.assign(S.ops.size(), 0);
+    for (size_t o = 0; o < S.ops.size(); ++o)
+      trsm[o] = S.ops[o].type == kOpGemm && S.ops[o].ntask > 0 && (S.gemm[S.ops[o].task0].flags & kCgTrsm) != 0;
+    if (use_k64)
       for (size_t o = 0; o < S.ops.size(); ++o) {
         const CholOp& op = S.ops[o];
         if (op.type != kOpGemm || op.ntask > kSmallGemmTiles) continue;
@@ -909,11 +969,9 @@ struct SparseChol::Impl {
   DevBuf<double> XS;  // t = 1 fused forward steps' block results
 };
 
-SparseChol::SparseChol(int n, int m, const int* nbr, int d, const double* X, hipStream_t s)
-    : s_(s), n_(n), m_(m), impl_(new Impl) {
-  int leaf = 64;
-  if (const char* e = std::getenv("GPBOOST_AMD_CHOL_LEAF")) leaf = std::max(1, std::atoi(e));
-  chol_analyze(n, m, nbr, d, X, leaf, plan_);
+SparseChol::SparseChol(int n, int m, const int* nbr, int d, const double* X, hipStream_t s, const CholOptions* opt)
+    : opt_(opt ? *opt : chol_default_options()), s_(s), n_(n), m_(m), impl_(new Impl) {
+  chol_analyze(n, m, nbr, d, X, std::max(1, opt_.leaf), plan_);
   CholEntries E;
   chol_entry_lists(plan_, m, nbr, E);
   nent_ = E.ecol[n];
@@ -942,8 +1000,8 @@ SparseChol::SparseChol(int n, int m, const int* nbr, int d, const double* X, hip
     vofs1_total_ = v1[P.nsup];
     upload(d_vofs1_, v1);
   }
-  impl_->factor.Upload(P.factor);
-  impl_->selinv.Upload(P.selinv);
+  impl_->factor.Upload(P.factor, opt_.k64);
+  impl_->selinv.Upload(P.selinv, opt_.k64);
   DevPlan& dp = impl_->dp;
   dp.n = n;
   dp.sfirst = d_sfirst_.get();
@@ -1001,7 +1059,9 @@ void SparseChol::Run(const SparseCholDev& sch, double* ybuf, const void* solve_a
                            d_info_.get());
         break;
       case kOpGemm:
-        if (sch.k64[oi])
+        if (sch.trsm[oi])
+          hipLaunchKernelGGL(chol_trsm_kernel, grid, dim3(256), 0, s_, sch.gemm.get(), op.task0, b);
+        else if (sch.k64[oi])
           hipLaunchKernelGGL(chol_gemm_k64_kernel, grid, dim3(256), 0, s_, sch.gemm.get(), op.task0, b);
         else
           hipLaunchKernelGGL(chol_gemm_kernel, grid, dim3(256), 0, s_, sch.gemm.get(), op.task0, b);
@@ -1070,6 +1130,7 @@ void SparseChol::Factor(const double* W) {
   // (the info counter is reset by the first assembly launch)
   HIP_CHECK(hipEventRecord(ev0_, s_));
   cur_W_ = W;
+  if (opt_.poison >= 0) Poison(0, nullptr, 0);
   Run(impl_->factor, nullptr, nullptr);
   HIP_CHECK(hipEventRecord(ev1_, s_));
   factored_ = true;
@@ -1112,9 +1173,9 @@ void SparseChol::SolveCols(const double* b, double* x, int t, int mode) {
   if (it == I.solve.end()) {
     CholSchedule S;
     std::vector<int64_t> vofs;
-    chol_solve_schedule(plan_, t, mode == 1, S, vofs, mode == 2);
+    chol_solve_schedule(plan_, t, mode == 1, S, vofs, mode == 2, &opt_);
     std::unique_ptr<SparseCholDev> dev(new SparseCholDev);
-    dev->Upload(S);
+    dev->Upload(S, opt_.k64);
     std::unique_ptr<DevBuf<int64_t>> dv(new DevBuf<int64_t>);
     upload(*dv, vofs);
     I.vofs_d[key] = std::move(dv);
@@ -1125,7 +1186,57 @@ void SparseChol::SolveCols(const double* b, double* x, int t, int mode) {
   if (t == 1 && (int64_t)I.XS.size() < sch.y_doubles) I.XS.alloc(sch.y_doubles);
   SolveArgs a{I.V.get(), I.vofs_d[key]->get(), b, x, t, t == 1 ? I.XS.get() : nullptr, d_F_.get(), d_Wd_.get(),
               d_woff_.get()};
+  if ((int64_t)d_P_.size() < sch.p_doubles) d_P_.alloc(sch.p_doubles);
+  if (opt_.poison >= 0) Poison(1, x == b ? nullptr : x, (size_t)n_ * t);
   Run(sch, I.V.get(), &a);
+}
+
+// Tests (CholOptions::poison): every buffer the phase writes or uses as scratch is filled with zeros or NaN (all
+// bits set) first, so a read of an element the phase has not written itself shows in the results. Wd: only the
+// ib x ib part of each 64 x 64 block, which chol_diag_kernel rewrites; the rest stays the constructor's zeros.
+void SparseChol::Poison(int phase, double* out, size_t out_doubles) {
+  const int byte = opt_.poison ? 0xFF : 0;
+  auto fill = [&](double* p, size_t doubles) {
+    if (p != nullptr && doubles > 0) HIP_CHECK(hipMemsetAsync(p, byte, sizeof(double) * doubles, s_));
+  };
+  fill(d_P_.get(), d_P_.size());
+  fill(out, out_doubles);
+  if (phase == 0) {
+    fill(d_F_.get(), d_F_.size());
+    for (int s = 0; s < plan_.nsup; ++s)
+      for (int k = 0; k < plan_.nblk(s); ++k) {
+        const int ib = std::min(64, plan_.ns(s) - 64 * k);
+        HIP_CHECK(hipMemset2DAsync(d_Wd_.get() + plan_.woff[s] + (int64_t)k * 4096, sizeof(double) * 64, byte,
+                                   sizeof(double) * ib, ib, s_));
+      }
+  } else if (phase == 1) {
+    fill(impl_->V.get(), impl_->V.size());
+    fill(impl_->XS.get(), impl_->XS.size());
+  } else {
+    fill(d_S_.get(), d_S_.size());
+    fill(d_Y_.get(), d_Y_.size());
+  }
+}
+
+void SparseChol::TestDense(int which, double* out) {
+  if (!factored_) Fatal("sparse Cholesky: dense expansion before a factorization");
+  const DevBuf<double>& src = which == 0 ? d_F_ : d_S_;
+  if (src.size() < (size_t)std::max<int64_t>(plan_.front_doubles, 1)) Fatal("sparse Cholesky: no selected inverse yet");
+  std::vector<double> h(src.size());
+  HIP_CHECK(hipMemcpyAsync(h.data(), src.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, s_));
+  HIP_CHECK(hipStreamSynchronize(s_));
+  const CholPlan& P = plan_;
+  const size_t n = (size_t)n_;
+  std::fill(out, out + n * n, which == 0 ? 0. : std::nan(""));
+  for (int s = 0; s < P.nsup; ++s) {
+    const int fs = P.fs(s), ns = P.ns(s);
+    for (int j = 0; j < ns; ++j)
+      for (int r = j; r < fs; ++r) {
+        const int pr = r < ns ? P.sfirst[s] + r : P.rows[P.rptr[s] + r - ns];
+        // which = 2: the mirrored copy S[j][r] of the front, returned at the place of S[r][j]
+        out[pr + n * (size_t)(P.sfirst[s] + j)] = which == 2 ? h[P.foff[s] + j + (size_t)r * fs] : h[P.foff[s] + r + (size_t)j * fs];
+      }
+  }
 }
 
 void SparseChol::Solve(const double* b, double* x) { SolveCols(b, x, 1, 0); }
@@ -1140,6 +1251,8 @@ void SparseChol::SelectedInverse(double* tr_bdb, double* tr_da, double* diagS) {
   if (!factored_) Fatal("sparse Cholesky: selected inverse before a factorization");
   if (d_S_.size() < (size_t)std::max<int64_t>(plan_.front_doubles, 1)) d_S_.alloc(std::max<int64_t>(plan_.front_doubles, 1));
   if ((int64_t)d_Y_.size() < impl_->selinv.y_doubles) d_Y_.alloc(std::max<int64_t>(impl_->selinv.y_doubles, 1));
+  if ((int64_t)d_P_.size() < impl_->selinv.p_doubles) d_P_.alloc(impl_->selinv.p_doubles);
+  if (opt_.poison >= 0) Poison(2, diagS, diagS ? (size_t)n_ : 0);
   Run(impl_->selinv, d_Y_.get(), nullptr);
   const int nb = std::min(kRedBlocks, grid_for(n_, 256));
   hipLaunchKernelGGL(chol_trace_kernel, dim3(nb), dim3(256), 0, s_, n_, d_ecol_.get(), d_eoff_.get(), d_aval_.get(),
@@ -1156,6 +1269,58 @@ void SparseChol::SelectedInverse(double* tr_bdb, double* tr_da, double* diagS) {
   HIP_CHECK(hipStreamSynchronize(s_));
   if (tr_bdb) *tr_bdb = h[0];
   if (tr_da) *tr_da = h[1];
+}
+
+// ---- test entries (sparse_chol.h): the arguments were checked by the caller (c_api.cpp)
+namespace {
+void to_device(DevBuf<double>& d, const double* h, size_t doubles) {
+  d.alloc(std::max<size_t>(doubles, 1));
+  HIP_CHECK(hipMemcpy(d.get(), h, sizeof(double) * doubles, hipMemcpyHostToDevice));
+}
+}  // namespace
+
+TestSparseChol::TestSparseChol(int n, int m, const int* nbr, int d, const double* X, const CholOptions& opt)
+    : n_(n), m_(m), chol_(n, m, nbr, d, X, nullptr, &opt) {}
+
+void TestSparseChol::SetB(const double* Bv, const double* Dinv, const double* dBv, const double* dD) {
+  to_device(Bv_, Bv, (size_t)n_ * m_);
+  to_device(Dinv_, Dinv, n_);
+  if (dBv != nullptr) {
+    to_device(dBv_, dBv, (size_t)n_ * m_);
+    to_device(dD_, dD, n_);
+  }
+  chol_.SetB(Bv_.get(), Dinv_.get(), dBv ? dBv_.get() : nullptr, dBv ? dD_.get() : nullptr);
+  HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+
+int TestSparseChol::Factor(const double* W, double* logdet) {
+  if (Bv_.size() == 0) Fatal("GPB_TestSparseCholFactor: factorization before SetB");
+  if (W != nullptr) to_device(W_, W, n_);
+  chol_.Factor(W ? W_.get() : nullptr);
+  const int info = chol_.Info();
+  if (logdet != nullptr) *logdet = chol_.LogDet();
+  return info;
+}
+
+void TestSparseChol::Solve(int op, int nrhs, int inplace, const double* b, double* x) {
+  const size_t len = (size_t)n_ * nrhs;
+  to_device(b_, b, len);
+  double* xd = b_.get();
+  if (!inplace) {
+    x_.alloc(len);
+    xd = x_.get();
+  }
+  if (op == 0) chol_.Solve(b_.get(), xd);
+  else if (op == 1) chol_.SolveMulti(b_.get(), xd, nrhs);
+  else if (op == 2) chol_.ForwardCols(b_.get(), xd, nrhs);
+  else chol_.BackwardCols(b_.get(), xd, nrhs);
+  HIP_CHECK(hipMemcpy(x, xd, sizeof(double) * len, hipMemcpyDeviceToHost));
+}
+
+void TestSparseChol::SelectedInverse(double* tr_bdb, double* tr_da, double* diagS) {
+  if (diagS != nullptr) diag_.alloc(n_);
+  chol_.SelectedInverse(tr_bdb, tr_da, diagS ? diag_.get() : nullptr);
+  if (diagS != nullptr) HIP_CHECK(hipMemcpy(diagS, diag_.get(), sizeof(double) * n_, hipMemcpyDeviceToHost));
 }
 
 }  // namespace gpb_amd

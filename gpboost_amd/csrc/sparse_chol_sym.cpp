@@ -383,7 +383,6 @@ namespace {
 
 constexpr int kSplitK = 512;        // K chunk of the selected inverse's long products
 constexpr int kSplitKSolve = 256;   // K chunk of the backward solve's transposed products
-constexpr int64_t kSmallPanel = 64 * 1024;   // fs x ns of the largest panel a single-workgroup level sweep takes
 
 CholGemmTask gemm_task(int bufa, int64_t a, int lda, int bufb, int64_t b, int ldb, int bufc, int64_t c, int ldc, int M,
                        int N, int K, int flags, int doff, double alpha, double beta) {
@@ -450,16 +449,16 @@ void build_factor_schedule(const CholPlan& P, CholSchedule& S) {
         S.diag.push_back(CholDiagTask{P.foff[s] + j0 + (int64_t)j0 * fs, P.woff[s] + (int64_t)k * 4096, fs, ib});
       }
       ob.end();
-      ob.begin(kOpGemm);   // TRSM: L[r0:fs, blk] = F[r0:fs, blk] W_b^T (in place)
+      ob.begin(kOpGemm);   // TRSM: L[r0:fs, blk] = F[r0:fs, blk] L_bb^-T (in place, by substitution: kCgTrsm)
       for (int q = P.lvl_ptr[l]; q < P.lvl_ptr[l + 1]; ++q) {
         const int s = P.lvl_sup[q];
         if (P.nblk(s) <= k) continue;
         const int fs = P.fs(s), j0 = 64 * k, ib = std::min(64, P.ns(s) - j0), r0 = j0 + ib;
         const int64_t w = P.woff[s] + (int64_t)k * 4096;
-        for (int rt = r0; rt < fs; rt += 64) {
+        for (int rt = r0; rt < fs; rt += 256) {   // 256 rows per task: four waves share one LDS copy of L_bb
           const int64_t c = P.foff[s] + rt + (int64_t)j0 * fs;
-          S.gemm.push_back(gemm_task(kCbF, c, fs, kCbW, w, 64, kCbF, c, fs, std::min(64, fs - rt), ib, ib, kCgTB, 0,
-                                     1., 0.));
+          S.gemm.push_back(gemm_task(kCbF, c, fs, kCbW, w, 64, kCbF, c, fs, std::min(256, fs - rt), ib, ib,
+                                     kCgTB | kCgTrsm, rt - j0, 1., 0.));
         }
       }
       ob.end();
@@ -604,8 +603,27 @@ void build_selinv_schedule(const CholPlan& P, CholSchedule& S) {
 
 }  // namespace
 
+CholOptions chol_default_options() {
+  CholOptions o;
+  if (const char* e = std::getenv("GPBOOST_AMD_CHOL_LEAF")) o.leaf = std::max(1, std::atoi(e));
+  // GPBOOST_AMD_CHOL_SMALL_PANEL: the fs x ns bound (A/B)
+  static const int64_t small_panel = [] {
+    const char* e = std::getenv("GPBOOST_AMD_CHOL_SMALL_PANEL");
+    return e ? std::max<int64_t>(0, std::atoll(e)) : CholOptions().small_panel;
+  }();
+  static const bool fuse_vec = [] {   // GPBOOST_AMD_CHOL_FWDVEC=0: the two-launch tiled form for t = 1 (A/B)
+    const char* e = std::getenv("GPBOOST_AMD_CHOL_FWDVEC");
+    return !(e && e[0] == '0');
+  }();
+  o.small_panel = small_panel;
+  o.fuse_vec = fuse_vec;
+  const char* e = std::getenv("GPBOOST_AMD_CHOL_K64");   // "0": always the K-pipelined form (A/B)
+  o.k64 = !(e && e[0] == '0' && e[1] == 0);
+  return o;
+}
+
 void chol_solve_schedule(const CholPlan& P, int t, bool forward_only, CholSchedule& S, std::vector<int64_t>& vofs,
-                         bool backward_only) {
+                         bool backward_only, const CholOptions* opt) {
   S = CholSchedule();
   OpBuilder ob(S);
   vofs.assign(P.nsup + 1, 0);
@@ -614,16 +632,10 @@ void chol_solve_schedule(const CholPlan& P, int t, bool forward_only, CholSchedu
   const int nlev = (int)P.lvl_ptr.size() - 1;
   // t = 1: levels whose panels are all small run one workgroup per supernode (two launches per level); the
   // levels of large separators keep the tiled form (its parallelism over row tiles).
-  // GPBOOST_AMD_CHOL_SMALL_PANEL: the fs x ns bound (A/B)
-  static const int64_t small_panel = [] {
-    const char* e = std::getenv("GPBOOST_AMD_CHOL_SMALL_PANEL");
-    return e ? std::max<int64_t>(0, std::atoll(e)) : kSmallPanel;
-  }();
+  const CholOptions o = opt ? *opt : chol_default_options();
+  const int64_t small_panel = o.small_panel;
+  const bool fuse_vec = o.fuse_vec;
   std::vector<char> small(nlev, 0);
-  static const bool fuse_vec = [] {   // GPBOOST_AMD_CHOL_FWDVEC=0: the two-launch tiled form for t = 1 (A/B)
-    const char* e = std::getenv("GPBOOST_AMD_CHOL_FWDVEC");
-    return !(e && e[0] == '0');
-  }();
   if (t == 1)
     for (int l = 0; l < nlev; ++l) {
       int64_t mx = 0;
@@ -943,6 +955,78 @@ void chol_entry_lists(const CholPlan& P, int m, const int* nbr, CholEntries& E) 
         const int i = std::max(q[a], q[b]), g = std::min(q[a], q[b]);
         E.ctr[pos[find(i, g)]++] = ((uint64_t)r << 16) | ((uint64_t)slot[a] << 8) | (uint64_t)slot[b];
       }
+  }
+}
+
+}  // namespace gpb_amd
+
+// ---- test entries (sparse_chol.h): argument checks and the plan alone, host only
+namespace gpb_amd {
+
+void test_sparse_chol_check_graph(const char* fn, int n, int m, const int* nbr, int64_t nbr_len, int d, const double* X,
+                                  int64_t x_len) {
+  if (n < 1) Fatal("%s: n = %d (at least 1)", fn, n);
+  if (m < 1 || m > 254) Fatal("%s: m = %d outside [1, 254]", fn, m);
+  if (d < 1) Fatal("%s: d = %d (at least 1)", fn, d);
+  if (nbr == nullptr || X == nullptr) Fatal("%s: nbr or X is NULL", fn);
+  if (nbr_len != (int64_t)n * m) Fatal("%s: nbr holds %lld entries, n m = %lld", fn, (long long)nbr_len, (long long)n * m);
+  if (x_len != (int64_t)n * d) Fatal("%s: X holds %lld entries, n d = %lld", fn, (long long)x_len, (long long)n * d);
+  for (int i = 0; i < n; ++i)
+    for (int r = 0; r < std::min(i, m); ++r) {
+      const int j = nbr[(size_t)i * m + r];
+      if (j < -1 || j >= i) Fatal("%s: nbr[%d][%d] = %d outside [-1, %d)", fn, i, r, j, i);
+    }
+}
+
+CholOptions test_sparse_chol_options(const int64_t* opts) {
+  CholOptions o = chol_default_options();
+  if (opts == nullptr) return o;
+  if (opts[0] >= 0) o.leaf = (int)std::max<int64_t>(1, std::min<int64_t>(opts[0], 1 << 30));
+  if (opts[1] >= 0) o.small_panel = opts[1];
+  if (opts[2] >= 0) o.fuse_vec = opts[2] != 0;
+  if (opts[3] >= 0) o.k64 = opts[3] != 0;
+  if (opts[4] >= 0) o.poison = opts[4] != 0;
+  return o;
+}
+
+void test_sparse_chol_plan(int n, int m, const int* nbr, int d, const double* X, const CholOptions& opt, int t, int mode,
+                           int* perm, int* sfirst, int* sparent, int64_t* rptr, int* rows, int64_t rows_cap, int* lvl_ptr,
+                           int* lvl_sup, int64_t* stats) {
+  if (t < 1 || mode < 0 || mode > 2) Fatal("GPB_TestSparseCholPlan: t = %d, mode = %d", t, mode);
+  CholPlan P;
+  chol_analyze(n, m, nbr, d, X, std::max(1, opt.leaf), P);
+  CholEntries E;   // also proves every entry of A lies in the structure (Fatal otherwise)
+  chol_entry_lists(P, m, nbr, E);
+  const int nlev = (int)P.lvl_ptr.size() - 1;
+  std::copy(P.perm.begin(), P.perm.end(), perm);
+  std::copy(P.sfirst.begin(), P.sfirst.end(), sfirst);
+  std::copy(P.sparent.begin(), P.sparent.end(), sparent);
+  std::copy(P.rptr.begin(), P.rptr.end(), rptr);
+  std::copy(P.lvl_ptr.begin(), P.lvl_ptr.end(), lvl_ptr);
+  std::copy(P.lvl_sup.begin(), P.lvl_sup.end(), lvl_sup);
+  const int64_t nrows = P.rptr[P.nsup];
+  if (rows != nullptr) {
+    if (rows_cap < nrows) Fatal("GPB_TestSparseCholPlan: rows holds %lld entries, %lld needed", (long long)rows_cap, (long long)nrows);
+    std::copy(P.rows.begin(), P.rows.begin() + nrows, rows);
+  }
+  std::fill(stats, stats + kTestCholStats, 0);
+  stats[0] = P.nsup; stats[1] = nlev; stats[2] = P.max_fs; stats[3] = P.max_ns; stats[4] = P.nnz_l; stats[5] = nrows;
+  CholSchedule solve;
+  std::vector<int64_t> vofs;
+  chol_solve_schedule(P, t, mode == 1, solve, vofs, mode == 2, &opt);
+  const CholSchedule* sch[3] = {&P.factor, &P.selinv, &solve};
+  for (int q = 0; q < 3; ++q) {
+    int64_t* out = stats + 6 + q * (kCholNumOps + 2);
+    for (const CholOp& op : sch[q]->ops) {
+      if (op.type < 0 || op.type >= kCholNumOps) Fatal("GPB_TestSparseCholPlan: unknown op %d", op.type);
+      ++out[op.type];
+      if (op.type == kOpReduce)
+        for (int64_t k = op.task0; k < op.task0 + op.ntask; ++k)
+          out[kCholNumOps] = std::max<int64_t>(out[kCholNumOps], sch[q]->red[k].nslices);
+      if (op.type == kOpBwdVecFin)
+        for (int64_t k = op.task0; k < op.task0 + op.ntask; ++k)
+          out[kCholNumOps + 1] = std::max<int64_t>(out[kCholNumOps + 1], sch[q]->col[k].c1);
+    }
   }
 }
 

@@ -423,6 +423,52 @@ GPBOOST_AMD_EXPORT int GPB_TestDenseChol(int n, int ld, double* A, double* W, in
 GPBOOST_AMD_EXPORT int GPB_TestDenseSpdSolveInverse(int n, const double* A, const double* b, double* x,
                                                     double* diag, double* inv);
 
+/* The sparse multifrontal Cholesky of A = B^T D^-1 B + diag(W) (matrix_inversion_method = "cholesky") on host
+ * arrays: its plan alone, and the numeric operations on a small handle. No reference counterpart (tests).
+ * Graph: nbr is n x m row-major (row i holds min(i, m) entries, entries < 0 skipped), X the coordinates n x d
+ * row-major. Checked on the host before anything else, a violation being an error return: n >= 1,
+ * 1 <= m <= 254, d >= 1, nbr_len = n m, x_len = n d, -1 <= nbr[i][r] < i for r < min(i, m), and every other
+ * *_len against the size it names.
+ * opts (nullable): {leaf, small_panel, fuse_vec, k64, poison}; an entry < 0 keeps the default, which for the
+ * first four is what GPBOOST_AMD_CHOL_LEAF / _SMALL_PANEL / _FWDVEC / _K64 give. poison = 1 / 0 fills every
+ * device scratch and output buffer a phase (Factor, a solve, SelectedInverse) writes with NaN / zeros before the
+ * phase; default: left as they are.
+ * GPB_TestSparseCholPlan makes no device call. perm, sparent, lvl_sup: n entries; sfirst, rptr, lvl_ptr: n + 1
+ * (nsup + 1, nsup + 1, levels + 1 used); rows (nullable; rows_cap entries, at least stats[5]): the supernodes'
+ * row structures. stats (stats_len = 63): nsup, levels, max_fs, max_ns, nnz_l, rptr[nsup], then for the factor,
+ * the selected-inverse and the solve schedule of t right-hand sides (mode 0 full, 1 forward only, 2 backward
+ * only) 19 entries each: the number of ops of each of the 17 CholOpType values (csrc/sparse_chol.h), the largest
+ * nslices of a split-K reduction, the largest chunk count of a kOpBwdVecFin task. */
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholPlan(int n, int m, const int32_t* nbr, int64_t nbr_len, int d,
+                                              const double* X, int64_t x_len, const int64_t* opts, int t, int mode,
+                                              int32_t* perm, int32_t* sfirst, int32_t* sparent, int64_t* rptr,
+                                              int32_t* rows, int64_t rows_cap, int32_t* lvl_ptr, int32_t* lvl_sup,
+                                              int64_t* stats, int64_t stats_len);
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholCreate(int n, int m, const int32_t* nbr, int64_t nbr_len, int d,
+                                                const double* X, int64_t x_len, const int64_t* opts, void** out);
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholFree(void* handle);
+/* Bv, dBv: n x m row-major (B(i, nbr[i][r]), unit diagonal implicit); Dinv, dD: n. dBv and dD are nullable
+ * together (no derivative: tr_da of the selected inverse is 0). */
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholSetB(void* handle, const double* Bv, int64_t bv_len, const double* Dinv,
+                                              int64_t dinv_len, const double* dBv, int64_t dbv_len, const double* dD,
+                                              int64_t dd_len);
+/* Factor A + diag(W) (W nullable = 0). out_info: non-zero exactly when some pivot was not positive and finite;
+ * logdet (nullable): 2 sum log L_ii. */
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholFactor(void* handle, const double* W, int64_t w_len, int* out_info,
+                                                double* logdet);
+/* op 0: Solve (nrhs = 1), 1: SolveMulti, 2: ForwardCols, 3: BackwardCols; b, x: n x nrhs column-major in the
+ * matrix labels (ForwardCols' result: elimination position k at label perm[k]). inplace = 1: x aliases b on
+ * the device. An error before the first factorization. */
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholSolve(void* handle, int op, int nrhs, int inplace, const double* b,
+                                               int64_t b_len, double* x, int64_t x_len);
+/* tr(S B^T D^-1 B), tr(S dA), diag(S) in the matrix labels; each output nullable. */
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholSelectedInverse(void* handle, double* tr_bdb, double* tr_da, double* diagS,
+                                                         int64_t diag_len);
+/* which = 0: the factor L, exact zeros outside its structure; 1: the selected inverse, NaN outside the lower
+ * structure of L; 2: the same entries of the selected inverse read from their mirrored (upper) copies in the
+ * fronts. n x n column-major in elimination positions (row / column k = label perm[k]). */
+GPBOOST_AMD_EXPORT int GPB_TestSparseCholDense(void* handle, int which, double* out, int64_t out_len);
+
 /* ---------------------------------------------------------------- prediction */
 
 /* replaces GPB_SetPredictionData (include/LightGBM/c_api.h:1578; c_api.cpp). Only the settings

@@ -1,6 +1,8 @@
 // Development check of the sparse Cholesky plan and its task schedules on the host (no GPU): every
 // op of the factorization / selected-inverse / solve schedules executed by plain loops on a random
-// matrix A = B^T D^-1 B + W with the Vecchia clique structure, compared with a dense Cholesky.
+// matrix A = B^T D^-1 B + W with the Vecchia clique structure, compared with a dense Cholesky. An op without
+// a host form is a fatal error. "260 254 64" takes the fused t = 1 vector ops (kOpFwdVec .. kOpBwdVecFin);
+// GPBOOST_AMD_CHOL_SMALL_PANEL=0 sends every level there, GPBOOST_AMD_CHOL_FWDVEC=0 to the GEMM form.
 //   hipcc -O2 -fopenmp -I gpboost_amd/csrc scripts/chol/chol_cpu_check.cpp gpboost_amd/csrc/sparse_chol_sym.cpp \
 //         gpboost_amd/csrc/vecchia_host.cpp -o /tmp/chol_cpu_check && /tmp/chol_cpu_check 1500 10 32
 #include <cmath>
@@ -25,6 +27,7 @@ struct Exec {
   const std::vector<double>* A;   // dense n x n (matrix labels)
   int n;
   const double* b = nullptr; double* X = nullptr; int t = 1; const std::vector<int64_t>* vofs = nullptr;
+  std::vector<double> XS;   // the fused t = 1 forward steps' block results (V's layout)
   double* buf(int id) { return id == kCbF ? F.data() : id == kCbS ? S.data() : id == kCbW ? Wd.data() : id == kCbY ? Y.data() : Pp.data(); }
   void run(const CholSchedule& sch) {
     for (const CholOp& op : sch.ops)
@@ -181,6 +184,44 @@ struct Exec {
       const double* V = Y.data() + (*vofs)[s];
       for (int k = 0; k < t; ++k)
         for (int a = c.c0; a < c.c1; ++a) X[P.perm[P.sfirst[s] + a] + (size_t)k * n] = V[a + (size_t)k * fs];
+    } else if (type == kOpLoadV) {
+      double* V = Y.data() + (*vofs)[s];
+      for (int k = 0; k < t; ++k)
+        for (int a = c.c0; a < c.c1; ++a) V[a + (size_t)k * fs] = b[P.perm[P.sfirst[s] + a] + (size_t)k * n];
+    } else if (type == kOpFwdVec) {   // {s, block k, row tile rt}: the tasks of one op are independent (x_b to XS)
+      const int k = c.c0, rt = c.c1, j0 = 64 * k, ib = std::min(64, ns - j0), r0 = j0 + ib;
+      double* V = Y.data() + (*vofs)[s];
+      const double* W = Wd.data() + P.woff[s] + (int64_t)k * 4096;
+      double x[64];
+      for (int i = 0; i < ib; ++i) { double v = 0.; for (int j = 0; j <= i; ++j) v += W[i + j * 64] * V[j0 + j]; x[i] = v; }
+      if (XS.size() < Y.size()) XS.resize(Y.size(), 0.);
+      if (rt == r0) for (int i = 0; i < ib; ++i) XS[(*vofs)[s] + j0 + i] = x[i];
+      for (int r = rt; r < std::min(rt + 64, fs); ++r)
+        for (int j = 0; j < ib; ++j) V[r] -= Fs[r + (size_t)(j0 + j) * fs] * x[j];
+    } else if (type == kOpCopyXS) {
+      for (int a = c.c0; a < c.c1; ++a) Y[(*vofs)[s] + a] = XS[(*vofs)[s] + a];
+    } else if (type == kOpBwdVecPart) {   // {s, block k, row chunk kc, slot}
+      const int k = c.c0, kc = c.c1, j0 = 64 * k, ib = std::min(64, ns - j0), r0 = j0 + ib;
+      const int rs = r0 + 256 * kc, re = std::min(rs + 256, fs);
+      const double* V = Y.data() + (*vofs)[s];
+      for (int j = 0; j < ib; ++j) {
+        double d = 0.;
+        for (int r = rs; r < re; ++r) d += Fs[r + (size_t)(j0 + j) * fs] * V[r];
+        Pp[(size_t)c.pad * 64 + j] = d;
+      }
+    } else if (type == kOpBwdVecFin) {   // {s, block k, nch, slot0}
+      const int k = c.c0, nch = c.c1, j0 = 64 * k, ib = std::min(64, ns - j0);
+      double* V = Y.data() + (*vofs)[s];
+      const double* W = Wd.data() + P.woff[s] + (int64_t)k * 4096;
+      double vb[64];
+      for (int j = 0; j < ib; ++j) {
+        double d = 0.;
+        for (int q = 0; q < nch; ++q) d += Pp[(size_t)(c.pad + q) * 64 + j];
+        vb[j] = V[j0 + j] - d;
+      }
+      for (int i = 0; i < ib; ++i) { double v = 0.; for (int j = i; j < ib; ++j) v += W[j + i * 64] * vb[j]; V[j0 + i] = v; }
+    } else {
+      Fatal("chol_cpu_check: op type %d has no host form", type);
     }
   }
 };
