@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "grouped_model.h"
+#include "latent_test.h"
 #include "re_model.h"
 #include "sparse_chol.h"
 
@@ -817,6 +818,98 @@ int GPB_TestSparseCholDense(void* handle, int which, double* out, int64_t out_le
   if (out == nullptr || out_len != (int64_t)c->n() * c->n())
     gpb_amd::Fatal("%s: out holds %lld entries, n n = %lld", fn, (long long)out_len, (long long)c->n() * c->n());
   c->Dense(which, out);
+  API_END();
+}
+
+static gpb_amd::TestLatentOps* test_latent(void* handle, const char* fn) {
+  if (handle == nullptr) gpb_amd::Fatal("%s: handle is NULL", fn);
+  return static_cast<gpb_amd::TestLatentOps*>(handle);
+}
+
+int GPB_TestLatentOpsCreate(int n, int m, const int32_t* nbr, int64_t nbr_len, int d, const double* X, int64_t x_len,
+                            const int64_t* opts, void** out) {
+  API_BEGIN();
+  const char* fn = "GPB_TestLatentOpsCreate";
+  gpb_amd::test_latent_check_graph(fn, n, m, nbr, nbr_len, d, X, x_len);
+  if (out == nullptr) gpb_amd::Fatal("%s: out is NULL", fn);
+  const gpb_amd::LatentOptions o = gpb_amd::test_latent_options(fn, opts, n);
+  *out = new gpb_amd::TestLatentOps(n, m, nbr, d, X, o);
+  API_END();
+}
+
+int GPB_TestLatentOpsFree(void* handle) {
+  API_BEGIN();
+  delete static_cast<gpb_amd::TestLatentOps*>(handle);
+  API_END();
+}
+
+int GPB_TestLatentOpsSetValues(void* handle, const double* Bv, int64_t bv_len, const double* Dinv, const double* W,
+                               const double* dw, int64_t vec_len, const double* alt_vals, int64_t alt_len) {
+  API_BEGIN();
+  const char* fn = "GPB_TestLatentOpsSetValues";
+  gpb_amd::TestLatentOps* c = test_latent(handle, fn);
+  const int64_t nm = (int64_t)c->n() * c->m(), n = c->n();
+  if (Bv == nullptr || Dinv == nullptr || W == nullptr || dw == nullptr) gpb_amd::Fatal("%s: an input is NULL", fn);
+  if (bv_len != nm || vec_len != n || (alt_vals != nullptr && alt_len != nm))
+    gpb_amd::Fatal("%s: Bv / vectors / alt_vals hold %lld / %lld / %lld entries, n m = %lld, n = %lld", fn,
+                   (long long)bv_len, (long long)vec_len, (long long)alt_len, (long long)nm, (long long)n);
+  c->lv().TestSetValues(Bv, Dinv, W, dw, alt_vals);
+  API_END();
+}
+
+int GPB_TestLatentOpsInfo(void* handle, int64_t* stats, int64_t stats_len, int32_t* vo, int64_t vo_len) {
+  API_BEGIN();
+  const char* fn = "GPB_TestLatentOpsInfo";
+  gpb_amd::TestLatentOps* c = test_latent(handle, fn);
+  if (stats == nullptr || stats_len != gpb_amd::kTestLatentStats)
+    gpb_amd::Fatal("%s: stats holds %lld entries, not %d", fn, (long long)stats_len, gpb_amd::kTestLatentStats);
+  if (vo != nullptr && vo_len != c->n()) gpb_amd::Fatal("%s: vo holds %lld entries, n = %d", fn, (long long)vo_len, c->n());
+  c->lv().TestInfo(stats, vo);
+  API_END();
+}
+
+int GPB_TestLatentOpsApply(void* handle, int op, int form, int t, int unit, int use_alt_vals, const double* X,
+                           const double* pre, const double* scale, const double* W, int64_t vec_len, const double* H,
+                           double* Y, double* Y2, int64_t block_len, int* guard_flag) {
+  API_BEGIN();
+  const char* fn = "GPB_TestLatentOpsApply";
+  gpb_amd::TestLatentOps* c = test_latent(handle, fn);
+  if (t < 1 || t > 1024) gpb_amd::Fatal("%s: t = %d", fn, t);
+  if (block_len != (int64_t)c->n() * t)
+    gpb_amd::Fatal("%s: the blocks hold %lld entries, n t = %lld", fn, (long long)block_len, (long long)c->n() * t);
+  if ((pre != nullptr || scale != nullptr || W != nullptr) && vec_len != c->n())
+    gpb_amd::Fatal("%s: the vectors hold %lld entries, n = %d", fn, (long long)vec_len, c->n());
+  c->lv().TestApply(op, form, t, unit, use_alt_vals, X, pre, scale, W, H, Y, Y2, guard_flag);
+  API_END();
+}
+
+int GPB_TestLatentOpsVector(int op, int n, int t, int np, int ia, int ib, double alpha, double beta,
+                            const double* const* blocks, int64_t block_len, const double* sv0, const double* sv1,
+                            const int32_t* act, int64_t small_len, double* out0, double* out1, double* small_out,
+                            int64_t small_out_len, int* guard_flag) {
+  API_BEGIN();
+  const char* fn = "GPB_TestLatentOpsVector";
+  if (n < 1 || t < 1 || t > 1024) gpb_amd::Fatal("%s: n = %d, t = %d", fn, n, t);
+  if (block_len != (int64_t)n * t) gpb_amd::Fatal("%s: the blocks hold %lld entries, n t = %lld", fn, (long long)block_len, (long long)n * t);
+  if ((sv0 != nullptr || sv1 != nullptr || act != nullptr) && small_len != t)
+    gpb_amd::Fatal("%s: the column vectors hold %lld entries, t = %d", fn, (long long)small_len, t);
+  const int64_t so = op == gpb_amd::kVecColdots ? (int64_t)np * t : op == gpb_amd::kVecCgUpdate ? t
+                     : op == gpb_amd::kVecAlpha ? 2 * t : op == gpb_amd::kVecBeta ? 3 * t : 0;
+  if (small_out != nullptr && small_out_len != so)
+    gpb_amd::Fatal("%s: small_out holds %lld entries, op %d writes %lld", fn, (long long)small_out_len, op, (long long)so);
+  gpb_amd::test_latent_vector(op, n, t, np, ia, ib, alpha, beta, blocks, sv0, sv1, act, out0, out1, small_out, guard_flag);
+  API_END();
+}
+
+int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, double delta, int pmax_single, int pmax_block,
+                         const double* RHS, double* U, int64_t block_len, int* its, int* flags) {
+  API_BEGIN();
+  const char* fn = "GPB_TestLatentOpsPcg";
+  gpb_amd::TestLatentOps* c = test_latent(handle, fn);
+  if (t < 1 || t > 1024) gpb_amd::Fatal("%s: t = %d", fn, t);
+  if (block_len != (int64_t)c->n() * t)
+    gpb_amd::Fatal("%s: the blocks hold %lld entries, n t = %lld", fn, (long long)block_len, (long long)c->n() * t);
+  c->lv().TestPcg(t, n_single, delta, pmax_single, pmax_block, RHS, U, its, flags);
   API_END();
 }
 

@@ -60,8 +60,9 @@ int env_rows(const char* name, int def) {
 }
 }  // namespace
 
-LatentVecchia::LatentVecchia(int n, int d, int m, const double* d_X, const int* nbr, hipStream_t stream)
-    : n_(n), d_(d), m_(m), d_X_(d_X), s_(stream) {
+LatentVecchia::LatentVecchia(int n, int d, int m, const double* d_X, const int* nbr, hipStream_t stream,
+                             const LatentOptions& opt)
+    : n_(n), d_(d), m_(m), d_X_(d_X), s_(stream), opt_(opt) {
   HIP_CHECK(hipEventCreate(&ev0_));
   HIP_CHECK(hipEventCreate(&ev1_));
   HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_out_), kOutDoubles * sizeof(double), hipHostMallocDefault));
@@ -74,8 +75,9 @@ LatentVecchia::LatentVecchia(int n, int d, int m, const double* d_X, const int* 
   // tail. K0 = 2048: the first 2048 rows span 201 of the 388 levels of each solve at n = 100k.
   // K = 14336: 112 KB of segment values per column workgroup (K sweep 12288 / 14336 / 16384:
   // 1.741 / 1.719 / 1.732 ms per application at t = 51 with K0 = 0).
-  dense_rows_ = std::min(env_rows("GPBOOST_AMD_DENSE_ROWS", 2048), n);
-  head_rows_ = std::max(std::min(env_rows("GPBOOST_AMD_HEAD_ROWS", 14336), n), dense_rows_);
+  dense_rows_ = std::min(opt_.dense_rows >= 0 ? opt_.dense_rows : env_rows("GPBOOST_AMD_DENSE_ROWS", 2048), n);
+  head_rows_ = std::max(std::min(opt_.head_rows >= 0 ? opt_.head_rows : env_rows("GPBOOST_AMD_HEAD_ROWS", 14336), n),
+                        dense_rows_);
   std::vector<int> nbr_p;
   Relabel(nbr, nbr_p);
   BuildStructure(nbr_p.data());
@@ -132,7 +134,8 @@ void LatentVecchia::Relabel(const int* nbr, std::vector<int>& nbr_p) {
   std::vector<double> X((size_t)n * d);   // the caller's upload runs on our (non-blocking) stream
   HIP_CHECK(hipMemcpyAsync(X.data(), d_X_, sizeof(double) * X.size(), hipMemcpyDeviceToHost, s_));
   HIP_CHECK(hipStreamSynchronize(s_));
-  if (std::getenv("GPBOOST_AMD_NO_RELABEL") == nullptr && n > m0 && d >= 1 && d <= 3) {
+  const bool relabel = opt_.relabel >= 0 ? opt_.relabel != 0 : std::getenv("GPBOOST_AMD_NO_RELABEL") == nullptr;
+  if (relabel && n > m0 && d >= 1 && d <= 3) {
     std::vector<double> lo(d, 0.), hi(d, 0.);
     for (int q = 0; q < d; ++q) {
       lo[q] = hi[q] = X[q];
@@ -190,7 +193,7 @@ void LatentVecchia::BuildStructure(const int* nbr) {
       ++fill[j];
     }
   }
-  pre_.reset(new VaduPrecond(n, m, s_));
+  pre_.reset(new VaduPrecond(n, m, s_, opt_.vadu));
   pre_->Build(nbr, vo_, lab_, tptr, trow, tslot, dense_rows_, head_rows_);
 
   d_nbr_.alloc((size_t)n * m);
@@ -220,6 +223,14 @@ void LatentVecchia::BuildStructure(const int* nbr) {
     HIP_CHECK(hipMemcpy(d_longr_.get(), longr.data(), sizeof(int) * longr.size(), hipMemcpyHostToDevice));
   sp_.longr = d_longr_.get();
   sp_.nlong = (int)longr.size();
+  stats_.assign(kTestLatentStats, 0);
+  stats_[kLsNnz] = nnz;
+  stats_[kLsMinList] = nnz;
+  for (int j = 0; j < n; ++j) {
+    stats_[kLsMaxList] = std::max<int64_t>(stats_[kLsMaxList], tptr[j + 1] - tptr[j]);
+    stats_[kLsMinList] = std::min<int64_t>(stats_[kLsMinList], tptr[j + 1] - tptr[j]);
+  }
+  stats_[kLsLong] = sp_.nlong;
   {   // LDS tiles of the t >= 2 operator (TileOp): greedy runs of consecutive storage rows
     auto build = [&](bool trans, TileDev& td) {
       std::vector<int> r0{0}, uoff{0}, urow, fb;
@@ -288,12 +299,14 @@ void LatentVecchia::BuildStructure(const int* nbr) {
     };
     build(false, tile_b_);
     build(true, tile_bt_);
+    stats_[kLsTileB] = tile_b_.op.ntile; stats_[kLsFbB] = tile_b_.op.nfb; stats_[kLsUmaxB] = tile_b_.op.umax;
+    stats_[kLsTileBt] = tile_bt_.op.ntile; stats_[kLsFbBt] = tile_bt_.op.nfb; stats_[kLsUmaxBt] = tile_bt_.op.umax;
   }
   {   // t = 1 form of B: ELL, column-major (SparseB). A row's entries in ascending storage index:
       // lane l's r-th gather is then the r-th smallest neighbour of row base + l, so the 64 gathers
       // of one load instruction fall on fewer cache lines than in neighbour (distance) order
       // (GPBOOST_AMD_ELL_UNSORTED: distance order, A/B)
-    static const bool unsorted = std::getenv("GPBOOST_AMD_ELL_UNSORTED") != nullptr;
+    const bool unsorted = std::getenv("GPBOOST_AMD_ELL_UNSORTED") != nullptr;
     std::vector<int> eidx((size_t)m * n), eslot((size_t)m * n);
     std::vector<std::pair<int, int>> row(m);
     for (int i = 0; i < n; ++i) {
@@ -324,10 +337,12 @@ void LatentVecchia::BuildStructure(const int* nbr) {
     for (int j = 0; j < n; ++j) {
       const int len = tptr[j + 1] - tptr[j];
       if (cr > 0 && (ce + len > kSegEntries || cr >= kSegRows)) {
+        ++stats_[cr >= kSegRows ? kLsSegByRows : kLsSegByEntries];
         seg.push_back(j);
         ce = 0;
         cr = 0;
       }
+      if (len > kSegEntries) ++stats_[kLsSegOverlong];
       for (int e = tptr[j]; e < tptr[j + 1]; ++e)
         pk[e] = (uint32_t)trow[e] | ((uint32_t)cr << 24) | (e + 1 == tptr[j + 1] ? 0x80000000u : 0u);
       ce += len;
@@ -367,6 +382,8 @@ void LatentVecchia::BuildStructure(const int* nbr) {
     sp_.seg_pk = d_seg_pk_.get();
     sp_.seg_info = d_seg_info_.get();
     sp_.nseg = (int)seg.size() - 1;
+    stats_[kLsSeg] = sp_.nseg;
+    stats_[kLsSegPad] = seg2_n_ - nnz;
   }
 }
 
@@ -676,7 +693,7 @@ void LatentVecchia::BenchOperators(int t, int reps, double* out) {
 // V = (B^T D^-1 B + W) H   (CG_utils.cpp:75, 161-164)
 void LatentVecchia::ApplyA(const double* H, double* V, double* G, int t) {
   g_timer.begin(s_);
-  static const bool tiled = std::getenv("GPBOOST_AMD_SPMV_TILED") != nullptr;   // A/B: LDS-tiled operator
+  const bool tiled = spmv_default_options().tiled;   // A/B: LDS-tiled operator
   if (t >= 2 && tiled && sp_.tval_of == d_Bv_.get()) {
     launch_b_apply_tiled(sp_, tile_b_.op, d_Bv_.get(), H, t, d_Dinv_.get(), G, s_);
     launch_bt_apply_tiled(sp_, tile_bt_.op, d_tval_.get(), G, t, d_W_.get(), H, V, s_);

@@ -65,6 +65,33 @@ inline double digamma_asa103(double x) {
   return value - r * (1.0 / 12.0 - r * (1.0 / 120.0 - r * (1.0 / 252.0 - r * (1.0 / 240.0 - r * (1.0 / 132.0)))));
 }
 
+// What TestInfo reports: the counts that show which kernel paths a structure reaches.
+enum LatentStat : int {
+  kLsNnz = 0,        // entries of B below the diagonal
+  kLsMaxList,        // longest / shortest transposed list
+  kLsMinList,
+  kLsLong,           // lists longer than kLongRow
+  kLsSeg,            // runs of the segmented t = 1 form of B^T
+  kLsSegByEntries,   // runs closed by the entry limit / by the row limit / holding one list longer than kSegEntries
+  kLsSegByRows,
+  kLsSegOverlong,
+  kLsSegPad,         // pad entries of the paired layout
+  kLsTileB,          // tiles, fallback rows, largest union of the B tile plan, then of B^T's
+  kLsFbB,
+  kLsUmaxB,
+  kLsTileBt,
+  kLsFbBt,
+  kLsUmaxBt,
+  kLsK0,             // VADU plan: dense head, segment end, padded order of the dense head
+  kLsK,
+  kLsLd0,
+  kLsTailBt,         // merged tail levels of the two solves, segment passes, launches per application
+  kLsTailLow,
+  kLsSegPasses,
+  kLsLaunches,
+  kTestLatentStats
+};
+
 struct LatentNan : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
@@ -106,12 +133,40 @@ class LatentSolverBase {
   double loglik_const_ = 0.;
 };
 
+// Structure and plan choices of a LatentVecchia. An entry < 0 takes the environment's value
+// (GPBOOST_AMD_NO_RELABEL, _DENSE_ROWS, _HEAD_ROWS and VaduOptions' variables) or, without one, the default.
+struct LatentOptions {
+  int relabel = -1;      // 0: storage order = Vecchia order
+  int dense_rows = -1;   // K0: dense head [0, K0)
+  int head_rows = -1;    // K: LDS segment [K0, K)
+  VaduOptions vadu;
+};
+
 class LatentVecchia : public LatentSolverBase {
  public:
   // d_X: coordinates (Vecchia order, row-major n x d) on the device, owned by the caller.
   // nbr: host n x m neighbour table (row i holds min(i, m) entries).
-  LatentVecchia(int n, int d, int m, const double* d_X, const int* nbr, hipStream_t stream);
+  LatentVecchia(int n, int d, int m, const double* d_X, const int* nbr, hipStream_t stream,
+                const LatentOptions& opt = LatentOptions());
   ~LatentVecchia();
+
+  // ---- test entries (GPB_TestLatentOps*, include/gpboost_amd.h; latent_test.cpp). Host arrays in Vecchia
+  // order in and out, synchronised; the caller has checked every extent.
+  // The per-evaluation refresh of Eval on given values: Bv (n x m), Dinv, W, dw (n), alt (nullable, n x m: a
+  // second value array on B's pattern, the operators' vals != tval_of paths).
+  void TestSetValues(const double* Bv, const double* Dinv, const double* W, const double* dw, const double* alt);
+  // stats[kTestLatentStats] (LatentStat), vo (nullable, n): storage row -> Vecchia row
+  void TestInfo(int64_t* stats, int* vo) const;
+  // One operator application on n x t blocks (see GPB_TestLatentOpsApply). Y2: B^-T R of op 3, else unused.
+  // guard: set to 1 when a word of the 64-double guard bands around an output changed.
+  void TestApply(int op, int form, int t, int unit, int use_alt, const double* X, const double* pre,
+                 const double* scale, const double* W, const double* H, double* Y, double* Y2, int* guard);
+  // The private Pcg on the set values' operator and preconditioner from a zero start: columns [0, n_single) by
+  // the single-vector rule, the rest by the block rule. its: {single, block}; flags: {nan, zero rhs}.
+  void TestPcg(int t, int n_single, double delta, int pmax_single, int pmax_block, const double* RHS, double* U,
+               int* its, int* flags);
+  bool test_values_set() const { return test_values_; }
+  bool test_has_alt() const { return test_alt_; }
 
   // Repeated coordinates (the reference's unique-location form, Vecchia_utils.cpp:1121-1139): the
   // latent variables are the n unique locations and obs_row[i] is the latent Vecchia row of
@@ -252,6 +307,10 @@ class LatentVecchia : public LatentSolverBase {
   int n_, d_, m_;
   const double* d_X_;
   hipStream_t s_;
+  LatentOptions opt_;
+  std::vector<int64_t> stats_;   // structure counts of BuildStructure (LatentStat)
+  bool test_values_ = false, test_alt_ = false;
+  DevBuf<double> test_buf_[4];   // TestApply: X, Y, Y2, G with their guard bands
   std::vector<int> vo_, lab_;   // storage row p holds Vecchia row vo_[p]; lab_ = inverse
   DevBuf<double> d_Xp_;         // coordinates in storage order
   DevBuf<double> d_tval_;       // B values in transposed-list order (refreshed per evaluation)

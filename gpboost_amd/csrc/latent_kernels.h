@@ -104,12 +104,26 @@ void launch_b_apply_tiled(const SparseB& B, const TileOp& op, const double* vals
                           const double* scale, double* Y, hipStream_t s);
 void launch_bt_apply_tiled(const SparseB& B, const TileOp& op, const double* tval, const double* X, int t,
                            const double* W, const double* H, double* Y, hipStream_t s);
+// Kernel selection of launch_b_apply / launch_bt_apply / LatentVecchia::ApplyA (the A/B forms).
+// spmv_default_options() resolves it once per process from the environment; the launchers take an
+// override (the test hooks, GPB_TestLatentOpsApply), null = the default.
+struct SpmvOptions {
+  int ch = -1, pers = 0, cap = 2048;   // GPBOOST_AMD_SPMV="ch,pers,cap" (t >= 2; ch = -1 / -2: wave-per-row forms)
+  bool old1 = false;                   // GPBOOST_AMD_SPMV1_OLD: t = 1, one row per lane group
+  bool groups1 = false;                // GPBOOST_AMD_SPMV1_GROUPS: t = 1 lane-group form of B
+  bool bt_groups1 = false;             // GPBOOST_AMD_BT1_GROUPS: t = 1 lane-group form of B^T
+  bool scan_shfl = false;              // GPBOOST_AMD_BT1_SCAN_SHFL: ds_bpermute scan
+  bool e1 = false;                     // GPBOOST_AMD_BT1_E1: one entry per lane
+  int epl = 0;                         // GPBOOST_AMD_BT1_E = 2 / 4 (E entries per lane); other values != 0: two per lane, unpaired
+  bool tiled = false;                  // GPBOOST_AMD_SPMV_TILED (ApplyA, t >= 2)
+};
+const SpmvOptions& spmv_default_options();
 // Y = diag(scale) (unit*X + V X)   with V = vals on the B pattern (rows list optional)
 void launch_b_apply(const SparseB& B, const double* vals, bool unit, const double* X, int t, const double* scale,
-                    double* Y, hipStream_t s);
+                    double* Y, hipStream_t s, const SpmvOptions* opt = nullptr);
 // Y = unit*pre.*X + V^T (pre.*X) + W.*H  (pre, W/H nullable)
 void launch_bt_apply(const SparseB& B, const double* vals, bool unit, const double* X, int t, const double* pre,
-                     const double* W, const double* H, double* Y, hipStream_t s);
+                     const double* W, const double* H, double* Y, hipStream_t s, const SpmvOptions* opt = nullptr);
 // ---- VADU preconditioner Z = P^-1 R = B^-1 diag(1/dw) B^-T R (CG_utils.cpp:56-60); the plan that
 // strings these kernels together is VaduPrecond (vadu_precond.h).
 //
@@ -205,7 +219,7 @@ struct HeadSolve {
 };
 void launch_vadu_head(const HeadSolve& h, const double* in, const double* dw, double* X, int t, hipStream_t s);
 void set_vadu_head_lds_limit(int K);
-// One-wave form of the same segment solve (the default): the passes are run by ONE wave per column
+// One-wave form of the same segment solve (GPBOOST_AMD_SEG_FORM=wave; the block form above is the default): the passes are run by ONE wave per column
 // (the workgroup's other waves only load the segment into LDS and write it back), so a pass is one
 // wave's instruction stream with no workgroup barrier — LDS operations of one wave complete in
 // order, which orders every pass's writes before the next pass's reads. A pass holds up to 64 >> lg

@@ -1341,16 +1341,20 @@ __global__ void __launch_bounds__(kBT) mode_deriv_kernel(ModeDerivArgs a, int sh
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
-// Form of the t >= 2 operator kernels (A/B switch GPBOOST_AMD_SPMV="ch,pers,cap"; ch = -1,
-// the default, selects the wave-per-row kernels).
-struct SpmvForm {
-  int ch, pers, cap;
-};
-SpmvForm spmv_form() {
-  static const SpmvForm f = [] {
-    SpmvForm r{-1, 0, 2048};
+// Forms of the operator kernels (A/B switches, SpmvOptions), read from the environment once per process.
+// GPBOOST_AMD_SPMV="ch,pers,cap": the t >= 2 kernels (ch = -1, the default, selects the wave-per-row kernels).
+const SpmvOptions& spmv_default_options() {
+  static const SpmvOptions f = [] {
+    SpmvOptions r;
     if (const char* e = std::getenv("GPBOOST_AMD_SPMV")) std::sscanf(e, "%d,%d,%d", &r.ch, &r.pers, &r.cap);
     if (r.cap < 8) r.cap = 8;
+    r.old1 = std::getenv("GPBOOST_AMD_SPMV1_OLD") != nullptr;           // A/B: one row per group
+    r.groups1 = std::getenv("GPBOOST_AMD_SPMV1_GROUPS") != nullptr;     // A/B: lane-group forms
+    r.bt_groups1 = std::getenv("GPBOOST_AMD_BT1_GROUPS") != nullptr;    // A/B: lane-group form
+    r.scan_shfl = std::getenv("GPBOOST_AMD_BT1_SCAN_SHFL") != nullptr;  // A/B: ds_bpermute scan
+    r.e1 = std::getenv("GPBOOST_AMD_BT1_E1") != nullptr;                // A/B: one entry per lane
+    if (const char* e = std::getenv("GPBOOST_AMD_BT1_E")) r.epl = std::atoi(e);   // A/B: unpaired layout, E per lane
+    r.tiled = std::getenv("GPBOOST_AMD_SPMV_TILED") != nullptr;         // A/B: LDS-tiled operator
     return r;
   }();
   return f;
@@ -1359,10 +1363,10 @@ SpmvForm spmv_form() {
 // The SpMV grids cover every row with one pass (no grid-stride loop): the XCD block mapping
 // needs the whole grid, and at n <= 2^31 / rpb the x dimension never overflows.
 void launch_b_apply(const SparseB& B, const double* vals, bool unit, const double* X, int t, const double* scale,
-                    double* Y, hipStream_t s) {
+                    double* Y, hipStream_t s, const SpmvOptions* opt) {
   if (B.n <= 0) return;
-  static const bool old1 = std::getenv("GPBOOST_AMD_SPMV1_OLD") != nullptr;   // A/B: one row per group
-  static const bool groups1 = std::getenv("GPBOOST_AMD_SPMV1_GROUPS") != nullptr;   // A/B: lane-group forms
+  const SpmvOptions& f = opt ? *opt : spmv_default_options();
+  const bool old1 = f.old1, groups1 = f.groups1;
   if (t == 1 && !old1 && !groups1 && B.ell_idx != nullptr && vals == B.vals_of) {
     hipLaunchKernelGGL(b_apply1e_kernel, dim3(grid_x(B.n, kBT, 1 << 30)), dim3(kBT), 0, s, B.n, B.m, B.ell_idx,
                        B.ell_val, unit ? 1 : 0, X, scale, Y);
@@ -1383,7 +1387,6 @@ void launch_b_apply(const SparseB& B, const double* vals, bool unit, const doubl
     return;
   }
   const Lanes L = lanes_for(t);
-  const SpmvForm f = spmv_form();
   if (f.ch < 0 && B.m <= 64) {   // default: wave-per-row form
     const dim3 g(grid_x(B.n, kBT / 64, 1 << 30), L.gy);
     if (f.ch == -2)
@@ -1405,18 +1408,14 @@ void launch_b_apply(const SparseB& B, const double* vals, bool unit, const doubl
 }
 
 void launch_bt_apply(const SparseB& B, const double* vals, bool unit, const double* X, int t, const double* pre,
-                     const double* W, const double* H, double* Y, hipStream_t s) {
+                     const double* W, const double* H, double* Y, hipStream_t s, const SpmvOptions* opt) {
   if (B.n <= 0) return;
   const double* tval = (B.tval != nullptr && vals == B.tval_of) ? B.tval : nullptr;
-  static const bool old1 = std::getenv("GPBOOST_AMD_SPMV1_OLD") != nullptr;
-  static const bool groups1 = std::getenv("GPBOOST_AMD_BT1_GROUPS") != nullptr;   // A/B: lane-group form
+  const SpmvOptions& f = opt ? *opt : spmv_default_options();
+  const bool old1 = f.old1, groups1 = f.bt_groups1;
   if (t == 1 && tval != nullptr && !old1 && !groups1 && B.seg_rb != nullptr) {
-    static const bool shfl = std::getenv("GPBOOST_AMD_BT1_SCAN_SHFL") != nullptr;   // A/B: ds_bpermute scan
-    static const bool one = std::getenv("GPBOOST_AMD_BT1_E1") != nullptr;   // A/B: one entry per lane
-    static const int epl = [] {   // A/B: GPBOOST_AMD_BT1_E = 2 / 4 (unpaired layout, E entries per lane)
-      const char* e = std::getenv("GPBOOST_AMD_BT1_E");
-      return e ? std::atoi(e) : 0;
-    }();
+    const bool shfl = f.scan_shfl, one = f.e1;
+    const int epl = f.epl;
     const dim3 g((B.nseg + kSegWaves - 1) / kSegWaves), b(64 * kSegWaves);
     if (!one && !shfl && epl == 0 && B.seg_info != nullptr) {   // default: paired layout
 #ifndef GPB_PAIR_U
@@ -1475,7 +1474,6 @@ void launch_bt_apply(const SparseB& B, const double* vals, bool unit, const doub
     return;
   }
   const Lanes L = lanes_for(t);
-  const SpmvForm f = spmv_form();
   if (f.ch < 0 && tval != nullptr) {   // default: wave-per-row form
     const dim3 g(grid_x(B.n, kBT / 64, 1 << 30), L.gy);
     if (f.ch == -2)

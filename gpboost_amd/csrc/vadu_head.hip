@@ -305,7 +305,10 @@ __global__ void __launch_bounds__(256) vadu_partial_kernel(PartialList p, const 
     const int my_id = ok ? p.eidx[e] : j;
     const double my_w = ok ? p.eval[e] : 0.;
     const int cnt = e1 - b0 < 64 ? e1 - b0 : 64;
-    acc = wave_dot<16>(my_id, my_w, cnt, src, t, cc, j, acc);
+    // padding gathers re-read the chunk's first entry's row: row j of src may be the row this launch
+    // writes (out == src), whose old contents (NaN or inf in a fresh or poisoned buffer) times the
+    // padding's zero weight would turn the sum into NaN
+    acc = wave_dot<16>(my_id, my_w, cnt, src, t, cc, __builtin_amdgcn_readlane(my_id, 0), acc);
   }
   if (c < t) {
     out[(size_t)j * t + c] = x - acc;

@@ -136,7 +136,11 @@ __global__ void __launch_bounds__(NW * 64) merged_levelR_kernel(MergedSolve ms, 
   const int p = p0 + xcd_block(blockIdx.x, gridDim.x);
   const int i = ms.rows[p];
   const int e0 = ms.eoff[p], ex = ms.xoff[p], e1 = ms.eoff[p + 1];
-  const int safe = ms.eidx[e0];       // padding gathers re-read the first entry's row
+  // padding gathers re-read the first entry's row from `in` (the row's own input: an IN entry). Read from X
+  // it would be the row this launch writes, whose old contents (NaN or inf in a fresh or poisoned buffer)
+  // times the padding's zero weight would turn the sum into NaN.
+  const int safe = ms.eidx[e0];
+  const unsigned nx = (unsigned)(e1 - ex);   // X entries are [ex, e1)
   double acc = 0.;
   for (int b = e0 + wave * CH; b < e1; b += NW * CH) {
     const int e = b + lane;
@@ -151,7 +155,7 @@ __global__ void __launch_bounds__(NW * 64) merged_levelR_kernel(MergedSolve ms, 
       w[q] = readlane_f64(my_w, q);
     }
 #pragma unroll
-    for (int q = 0; q < CH; ++q) g[q] = (b + q < ex ? in : X)[(size_t)id[q] * t + cc];
+    for (int q = 0; q < CH; ++q) g[q] = ((unsigned)(b + q - ex) < nx ? X : in)[(size_t)id[q] * t + cc];
 #pragma unroll
     for (int q = 0; q < CH; ++q) acc = fma(w[q], g[q], acc);
   }
@@ -206,7 +210,8 @@ __global__ void __launch_bounds__(256) merged_levelW_kernel(MergedSolve ms, cons
     const bool ok = e < e1;
     const int my_id = ok ? ms.eidx[e] : i;
     const double my_w = ok ? coef[e] : 0.;
-    s = wave_dot<CH>(my_id, my_w, e1 - b0 < 64 ? e1 - b0 : 64, X, t, cc, i, s);
+    // padding gathers re-read the chunk's first entry's row, not row i of X, which this launch writes
+    s = wave_dot<CH>(my_id, my_w, e1 - b0 < 64 ? e1 - b0 : 64, X, t, cc, __builtin_amdgcn_readlane(my_id, 0), s);
   }
   if (c < t) X[(size_t)i * t + c] = s;
 }

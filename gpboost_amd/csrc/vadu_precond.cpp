@@ -193,7 +193,10 @@ void VaduPrecond::Build(const int* nbr, const std::vector<int>& vo, const std::v
   K_ = K;
   DropGraphs();
   use_graph_ = std::getenv("GPBOOST_AMD_NO_GRAPH") == nullptr;   // diagnostics: eager launches (profilers)
-  if (const char* e = std::getenv("GPBOOST_AMD_SEG_FORM")) {
+  if (opt_.no_graph >= 0) use_graph_ = opt_.no_graph == 0;
+  if (opt_.seg_form >= 0) {
+    seg_wave_ = opt_.seg_form == 1;
+  } else if (const char* e = std::getenv("GPBOOST_AMD_SEG_FORM")) {
     const std::string f(e);
     if (f != "wave" && f != "block") Fatal("GPBOOST_AMD_SEG_FORM must be wave or block (got '%s')", e);
     seg_wave_ = f == "wave";
@@ -243,7 +246,10 @@ void VaduPrecond::Build(const int* nbr, const std::vector<int>& vo, const std::v
   // g = 8 1.05; g <= 16 with 150k entries 0.78 — beyond ~3 levels the fill's gather bytes, not the
   // launches, set the time)
   int g = 16;
-  if (const char* e = std::getenv("GPBOOST_AMD_TAIL_MERGE")) {
+  if (opt_.tail_merge >= 0) {
+    g = opt_.tail_merge;
+    if (g < 1 || g > 64) Fatal("VADU tail merge must be 1..64 (got %d)", g);
+  } else if (const char* e = std::getenv("GPBOOST_AMD_TAIL_MERGE")) {
     g = std::atoi(e);
     if (g < 1 || g > 64) Fatal("GPBOOST_AMD_TAIL_MERGE must be 1..64 (got '%s')", e);
   }
@@ -266,7 +272,7 @@ void VaduPrecond::Build(const int* nbr, const std::vector<int>& vo, const std::v
     const char* tord = std::getenv("GPBOOST_AMD_TAIL_ORDER");
     if (tord && std::string(tord) != "level" && std::string(tord) != "row")
       Fatal("GPBOOST_AMD_TAIL_ORDER must be row or level (got '%s')", tord);
-    if (!tord || std::string(tord) == "row") {
+    if (opt_.tail_order >= 0 ? opt_.tail_order == 0 : (!tord || std::string(tord) == "row")) {
       sort_merged_by_row(mb);
       sort_merged_by_row(ml);
     }
@@ -320,9 +326,11 @@ void VaduPrecond::Build(const int* nbr, const std::vector<int>& vo, const std::v
       if (f != "persist" && f != "launch") Fatal("GPBOOST_AMD_TAIL_FORM must be persist or launch (got '%s')", e);
       tail_persist_ = f == "persist";
     }
+    if (opt_.tail_form >= 0) tail_persist_ = opt_.tail_form == 1;
     if (tail_persist_) {
       int W = std::min(64, tail_persist_max_w());
-      if (const char* e = std::getenv("GPBOOST_AMD_TAIL_W")) W = std::atoi(e);
+      if (opt_.tail_w >= 0) W = opt_.tail_w;
+      else if (const char* e = std::getenv("GPBOOST_AMD_TAIL_W")) W = std::atoi(e);
       if (W < 1 || W > tail_persist_max_w())
         Fatal("GPBOOST_AMD_TAIL_W: %d workgroups per XCD group, at most %d resident", W, tail_persist_max_w());
       std::vector<int> pint;

@@ -38,9 +38,20 @@
 
 namespace gpb_amd {
 
+// Plan choices of Build. An entry < 0 takes the environment's value (GPBOOST_AMD_TAIL_MERGE, _SEG_FORM,
+// _TAIL_ORDER, _TAIL_FORM, _TAIL_W, _NO_GRAPH) or, without one, the default.
+struct VaduOptions {
+  int tail_merge = -1;   // merged levels per launch, 1..64
+  int seg_form = -1;     // 0 block, 1 wave
+  int tail_order = -1;   // 0 row, 1 level
+  int tail_form = -1;    // 0 launch, 1 persist
+  int tail_w = -1;       // workgroups per XCD group of the persistent tail
+  int no_graph = -1;     // 1: eager launches
+};
+
 class VaduPrecond {
  public:
-  VaduPrecond(int n, int m, hipStream_t s) : n_(n), m_(m), s_(s) {}
+  VaduPrecond(int n, int m, hipStream_t s, const VaduOptions& opt = VaduOptions()) : n_(n), m_(m), s_(s), opt_(opt) {}
   ~VaduPrecond();
   VaduPrecond(const VaduPrecond&) = delete;
   VaduPrecond& operator=(const VaduPrecond&) = delete;
@@ -55,7 +66,9 @@ class VaduPrecond {
   // Per system: dw = D^-1 + W (device, n), after its values are written (stream order). Must
   // precede Apply; the pointer is captured and the lower solve's coefficients are rescaled.
   void SetDiag(const double* dw);
-  // Z = P^-1 R for t columns (row-major n x t); Xt: n x t scratch (holds B^-T R afterwards).
+  // Z = P^-1 R for t columns (row-major n x t); Xt: n x t scratch. Afterwards it holds B^-T R on the rows
+  // of Vecchia index >= K0; the dense head's rows hold the head's input (R minus the later rows' terms),
+  // whose own B_00^-T is applied inside the dense products.
   // stream: null = the model's; applications that may run concurrently (on different streams)
   // use different scratch slots (< kSlots).
   static constexpr int kSlots = 2;
@@ -66,6 +79,7 @@ class VaduPrecond {
 
   int K0() const { return K0_; }
   int K() const { return K_; }
+  int ld0() const { return ld0_; }
   int tail_levels_bt() const { return (int)mt_bt_.lptr.size() - 1; }
   int tail_levels_lower() const { return (int)mt_low_.lptr.size() - 1; }
   int segment_passes() const { return seg_bt_.npass + seg_low_.npass; }
@@ -79,6 +93,7 @@ class VaduPrecond {
 
   int n_, m_;
   hipStream_t s_;
+  VaduOptions opt_;
   int K0_ = 0, K_ = 0, ld0_ = 0;
   DenseHead dh_{};
   const double* dw_ = nullptr;

@@ -469,6 +469,66 @@ GPBOOST_AMD_EXPORT int GPB_TestSparseCholSelectedInverse(void* handle, double* t
  * fronts. n x n column-major in elimination positions (row / column k = label perm[k]). */
 GPBOOST_AMD_EXPORT int GPB_TestSparseCholDense(void* handle, int which, double* out, int64_t out_len);
 
+/* The operator layer of the iterative latent-Vecchia path on host arrays: the sparse operators
+ * Y = diag(scale)(unit X + V X) and Y = unit pre.*X + V^T (pre.*X) + W.*H in every selectable kernel form, their
+ * production composition (B^T D^-1 B + W) X, and the VADU preconditioner. No reference counterpart (tests).
+ * Graph: nbr is n x m row-major (row i holds min(i, m) entries), X the coordinates n x d row-major (used only
+ * by the storage relabelling). Checked on the host before any device call, a violation being an error return:
+ * 1 <= n < 2^24, m >= 1, d >= 1, nbr_len = n m, x_len = n d, 0 <= nbr[i][r] < i and distinct within a row for
+ * r < min(i, m), finite coordinates, and every other *_len against the size it names.
+ * opts (nullable, 9 entries): {relabel (0: storage order = Vecchia order), dense_rows, head_rows, tail_merge,
+ * seg_form (0 block, 1 wave), tail_order (0 row, 1 level), tail_form (0 launch, 1 persist), tail_w, no_graph};
+ * an entry < 0 keeps what GPBOOST_AMD_NO_RELABEL / _DENSE_ROWS / _HEAD_ROWS / _TAIL_MERGE / _SEG_FORM /
+ * _TAIL_ORDER / _TAIL_FORM / _TAIL_W / _NO_GRAPH give. */
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsCreate(int n, int m, const int32_t* nbr, int64_t nbr_len, int d,
+                                               const double* X, int64_t x_len, const int64_t* opts, void** out);
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsFree(void* handle);
+/* The per-evaluation refresh of an evaluation on given values, all in Vecchia order: Bv (n x m: B(i, nbr[i][r]),
+ * unit diagonal implicit), Dinv, W, dw (n each, vec_len = n), alt_vals (nullable, n x m: a second value array on
+ * B's pattern for the operators' use_alt_vals paths). */
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsSetValues(void* handle, const double* Bv, int64_t bv_len, const double* Dinv,
+                                                  const double* W, const double* dw, int64_t vec_len,
+                                                  const double* alt_vals, int64_t alt_len);
+/* stats (stats_len = 22): nnz, the longest and the shortest transposed list, lists longer than 64 (long-row
+ * waves), runs of the segmented t = 1 form, runs closed by the entry limit / by the row limit, runs that are
+ * one list longer than the entry limit, pad entries of the paired layout, {tiles, fallback rows, largest union}
+ * of the B and of the B^T tile plan, K0, K, the dense head's padded order, merged tail levels of the B^T and of
+ * the lower solve, segment passes, launches per preconditioner application. vo (nullable, vo_len = n): the
+ * Vecchia row of storage row p. */
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsInfo(void* handle, int64_t* stats, int64_t stats_len, int32_t* vo,
+                                             int64_t vo_len);
+/* One application on n x t row-major blocks in Vecchia order (block_len = n t, vec_len = n for each given vector).
+ * op 0: Y = diag(scale)(unit X + V X); op 1: Y = unit pre.*X + V^T (pre.*X) + W.*H (W and H go together);
+ * V = Bv's values, or alt_vals' with use_alt_vals. op 2: Y = (B^T D^-1 B + W) X of the set values (form 0 the
+ * production dispatch, 1 the LDS-tiled pair). op 3: Y = P^-1 X of the VADU plan and Y2 = the plan's scratch, B^-T X on
+ * the Vecchia rows >= K0 (the dense head's rows hold the head's input); with graphs on, a second call at the same t replays the captured graph. form 0 = the production dispatch, other values the
+ * kernels listed in csrc/latent_test.h (LatentBForm / LatentBtForm); a form the shape or the arguments do not
+ * admit is an error return. Outputs start as NaN between 64 guard doubles on either side; guard_flag = 1 when a
+ * guard word changed. */
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsApply(void* handle, int op, int form, int t, int unit, int use_alt_vals,
+                                              const double* X, const double* pre, const double* scale,
+                                              const double* W, int64_t vec_len, const double* H, double* Y,
+                                              double* Y2, int64_t block_len, int* guard_flag);
+/* The block-CG vector kernels on host arrays of any n and t (no structure; ops: LatentVecOp in
+ * csrc/latent_test.h): 0 coldots (np = 1..3 pairs of blocks, small_out np t), 1 cg_update (blocks H, V, U, R,
+ * sv0 = a; out0 = U, out1 = R, small_out = rr), 2 h_update (blocks Z, H, sv0 = b; out0 = H), 3 cg_alpha
+ * (sv0 = rz, sv1 = hv, act; small_out = a, hist), 4 cg_beta (sv0 = rz_new, sv1 = rz, act; small_out = b, hist,
+ * rz), 5 axpby (blocks X, Y; out0), 6 cap_mode_change (blocks mode, mnew; out0), 7 pack_columns (np columns
+ * from column ia of blocks[0] to column ib of blocks[1]; out0). blocks: 6 pointers (unused ones NULL), each
+ * n x t row-major with block_len = n t; sv0, sv1, act: t entries (small_len = t); act nullable (all active). */
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsVector(int op, int n, int t, int np, int ia, int ib, double alpha,
+                                               double beta, const double* const* blocks, int64_t block_len,
+                                               const double* sv0, const double* sv1, const int32_t* act,
+                                               int64_t small_len, double* out0, double* out1, double* small_out,
+                                               int64_t small_out_len, int* guard_flag);
+/* The PCG of the iterative path on the handle's operator (B^T D^-1 B + W) and VADU preconditioner from a zero
+ * start: RHS, U n x t row-major in Vecchia order (block_len = n t); columns [0, n_single) stop by the
+ * single-vector rule (||r|| < delta, pmax_single), the others by the block rule (mean ||r|| < delta,
+ * pmax_block). its: {single, block} iteration counts; flags: {NaN met, zero right-hand side (t = 1)}. */
+GPBOOST_AMD_EXPORT int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, double delta, int pmax_single,
+                                            int pmax_block, const double* RHS, double* U, int64_t block_len,
+                                            int* its, int* flags);
+
 /* ---------------------------------------------------------------- prediction */
 
 /* replaces GPB_SetPredictionData (include/LightGBM/c_api.h:1578; c_api.cpp). Only the settings
