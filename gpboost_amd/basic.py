@@ -597,6 +597,13 @@ class GPModel:
         _safe_call(lib().GPB_GetLastKernelTimes(self.handle, _dp(out)))
         return out
 
+    def last_gram_ms(self):
+        """[factorization, whole call] device ms of the last covariate Gram matrix of a "fitc" / "full_scale_vecchia"
+        model (GPB_GetLastGramTimes); the evaluation that follows it reuses the factorization."""
+        out = np.zeros(2)
+        _safe_call(lib().GPB_GetLastGramTimes(self.handle, _dp(out)))
+        return out
+
     def bench_latent_operators(self, t: int, reps: int = 20):
         """(ms per A application, ms per preconditioner application, nnz(B), launches per preconditioner application)."""
         out = np.zeros(4)

@@ -723,6 +723,13 @@ int GPB_TestDenseSpdSolveInverse(int n, const double* A, const double* b, double
   API_END();
 }
 
+int GPB_TestWeightedTallSkinny(int m, int n, int c, const double* A, int64_t a_len, const double* w, const double* U,
+                               double* T_out, double* G0_out) {
+  API_BEGIN();
+  gpb_amd::test_weighted_tall_skinny(m, n, c, A, (long)a_len, w, U, T_out, G0_out);
+  API_END();
+}
+
 int GPB_TestSparseCholPlan(int n, int m, const int32_t* nbr, int64_t nbr_len, int d, const double* X, int64_t x_len,
                            const int64_t* opts, int t, int mode, int32_t* perm, int32_t* sfirst, int32_t* sparent,
                            int64_t* rptr, int32_t* rows, int64_t rows_cap, int32_t* lvl_ptr, int32_t* lvl_sup,
@@ -1075,6 +1082,13 @@ int GPB_GetVecchiaRowsInfo(REModelHandle handle, double* out) {
 int GPB_GetLastKernelTimes(REModelHandle handle, double* kernel_ms) {
   API_BEGIN();
   model(handle)->GetLastKernelTimes(kernel_ms);
+  API_END();
+}
+
+int GPB_GetLastGramTimes(REModelHandle handle, double* gram_ms) {
+  API_BEGIN();
+  if (gram_ms == nullptr) gpb_amd::Fatal("GPB_GetLastGramTimes: gram_ms is NULL");
+  model(handle)->GetLastGramTimes(gram_ms);
   API_END();
 }
 

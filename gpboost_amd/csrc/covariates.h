@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "common.h"
+
 namespace gpb_amd {
 
 constexpr int kCovMaxCols = 32;   // covariates + the response column
@@ -22,6 +24,38 @@ void launch_vecchia_gram(int n, int m, int c, const int* nbr, const double* B, c
 void launch_vecchia_psi_inv_diag(int n, int m, const int* nbr, const int* tptr, const int* trow, const int* tslot,
                                  const double* B, const double* Dinv, const double* y, double* u, double* yaux,
                                  double* diag, hipStream_t s);
+
+// ---- Woodbury-form covariances (gp_approx = "fitc", "full_scale_vecchia"; lowrank_gram.hip)
+// Row ranges (one partial each) that launch_weighted_tall_skinny splits n points into.
+int weighted_tall_skinny_ranges(int n);
+// One pass over the n points: T = A diag(w) U (m x c, column-major, leading dimension ldm; rows m..ldm-1
+// zero) and G0 = U^T diag(w) U (packed upper triangle, as launch_vecchia_gram returns it).
+// A: m x n column-major with leading dimension ldm (point i's m entries contiguous); w: n weights;
+// U: n x c row-major, c <= kCovMaxCols. Tpart: ranges * c * ldm doubles, Gpart: ranges * c * c doubles of
+// scratch (one partial per range, summed in a fixed order: equal inputs give equal bits).
+void launch_weighted_tall_skinny(int m, int n, int c, const double* A, int ldm, const double* w, const double* U,
+                                 double* Tpart, double* Gpart, double* T, double* G0, hipStream_t s);
+// U = B Z for the n x c row-major Z: U_i = Z_i + sum_r Bv[i nn + r] Z[nbr[i nn + r]] over row i's min(i, nn)
+// neighbours (B unit lower triangular, its off-diagonal values in Bv).
+void launch_vecchia_bz(int n, int nn, int c, const int* nbr, const double* Bv, const double* Z, double* U,
+                       hipStream_t s);
+
+// Device scratch of lowrank_gram (allocated on first use, kept by the solver)
+struct LowrankGramWork {
+  DevBuf<double> w, Tpart, Gpart, T, S, G0;
+};
+// Z^T Psi^-1 Z (host, c x c row-major) of a low-rank-plus-residual covariance by the Woodbury identity:
+//   G = U^T diag(1 / dvec) U - S^T S,  S = Li (A diag(1 / dvec) U),
+// Li (m x m lower, leading dimension ldm) the inverse Cholesky factor of the Woodbury matrix. FITC: A = K_mn,
+// dvec = d, U = Z; full-scale Vecchia: A = B K_nm, dvec = D, U = B Z. The c x c subtraction runs on the
+// host in a fixed order.
+void lowrank_gram(hipStream_t s, int m, int n, int c, int ldm, const double* A, const double* dvec, const double* U,
+                  const double* Li, LowrankGramWork& ws, double* G_host);
+
+// Test entry (GPB_TestWeightedTallSkinny): host arrays in and out, the default stream, synchronised. A: a_len =
+// round_up(m, 64) * n doubles; T_out: m x c row-major; G0_out: c x c row-major (both triangles).
+void test_weighted_tall_skinny(int m, int n, int c, const double* A, long a_len, const double* w, const double* U,
+                               double* T_out, double* G0_out);
 
 // Host: unpack the packed upper triangle of a c x c Gram matrix into a full row-major matrix.
 std::vector<double> unpack_gram(const double* packed, int c);

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "covariates.h"
 
 namespace gpb_amd {
 
@@ -86,6 +87,12 @@ class FitcSolver {
   // original-scale orig (trafo: the same transformed), Hutchinson estimates over t probes from (seed,
   // run_id): CalcFisherInformation_FITC_FSA (re_model_template.h:9363-9548; fitc_fisher.hip).
   void Fisher(int cov_type, const double* orig, const double* trafo, int t, int seed, uint64_t run_id, double* FI);
+  // G = Z^T Psi^-1 Z (host, c x c row-major) for the device matrix d_Z (n x c row-major, original order) on the
+  // transformed scale (DenseSolver::Gram's contract): G0 - S^T S with T = K_mn diag(1 / d) Z, G0 = Z^T diag(1 / d) Z,
+  // S = L_W^-1 T (lowrank_gram.hip). The factorization it builds (Prior and the Woodbury factor) is kept for the
+  // next Eval at the same (cov_type, var, phi), which then reruns only its response-dependent part. A
+  // non-positive-definite factor gives a NaN G. gram_ms (nullable): device ms of the factorization and of the whole call.
+  void Gram(int cov_type, double var, double phi, const double* d_Z, int c, double* G_host, double* gram_ms = nullptr);
 
  private:
   friend class FitcLaplace;   // the Laplace approximation (fitc_laplace.h) works on these buffers
@@ -94,7 +101,17 @@ class FitcSolver {
   // K_mn, K_mm, K_mm,s, dK_mm, L = chol(K_mm,s) (red[0] = 2 sum log L_ii), L^-1 (Li_), V = L^-1 K_mn,
   // K_mm,s^-1 (Kinv_): the part of the factorization that does not depend on the likelihood
   void Prior(int cov_type, double var, double phi, double* red);
+  // Prior, d (red[2] = sum log d), K_d = K_mn diag(1 / d) and the Woodbury factor L_W (W_, red[1] = log det W), its
+  // inverse (Wi_, WiT_): everything of Factor that does not depend on the response
+  void FactorCommon(int cov_type, double var, double phi, double* red);
   void Factor(int cov_type, double var, double phi, const double* d_y, double* red);
+  // FactorCommon's results are in place for (kept_cov_, kept_var_, kept_phi_) with their sums in kept_red_: set by
+  // Gram, used once by the next Factor, cleared by whatever overwrites the buffers (Prior: every other entry)
+  bool kept_ = false;
+  int kept_cov_ = 0;
+  double kept_var_ = 0., kept_phi_ = 0.;
+  const double* kept_red_ = nullptr;
+  LowrankGramWork gram_ws_;
 
   int n_, d_, m_, ldm_;
   const double* d_X_;

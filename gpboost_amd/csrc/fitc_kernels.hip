@@ -94,11 +94,10 @@ __global__ void __launch_bounds__(256) fitc_kmm_kernel(const double* __restrict_
 }
 
 // d_i = (1 + sigma1^2 jitter) - |V[:, i]|^2 (re_model_template.h:7358-7377), K_d = K_mn diag(1/d),
-// Dy = y / d, block partial of sum log d. One wave per observation.
+// block partial of sum log d. One wave per observation.
 __global__ void __launch_bounds__(256) fitc_diag_kernel(const double* __restrict__ V, const double* __restrict__ Kmn,
-                                                        const double* __restrict__ y, int n, int m, int ldm, double dvar,
-                                                        double* __restrict__ dvec, double* __restrict__ Kd,
-                                                        double* __restrict__ Dy, double* __restrict__ part) {
+                                                        int n, int m, int ldm, double dvar, double* __restrict__ dvec,
+                                                        double* __restrict__ Kd, double* __restrict__ part) {
   __shared__ double red[4];
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -114,14 +113,20 @@ __global__ void __launch_bounds__(256) fitc_diag_kernel(const double* __restrict
     const double di = dvar - s;
     const double inv = 1. / di;
     for (int j = lane; j < m; j += 64) Kd[(size_t)j + (size_t)i * ldm] = Kmn[(size_t)j + (size_t)i * ldm] * inv;
-    if (lane == 0) {
-      dvec[i] = di;
-      Dy[i] = inv * y[i];
-    }
+    if (lane == 0) dvec[i] = di;
     lg = log(di);
   }
   const double t = block4_sum(lg, red);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// Dy = y / d, as (1 / d_i) y_i: the response-dependent part of the step above
+__global__ void __launch_bounds__(256) fitc_dy_kernel(const double* __restrict__ dvec, const double* __restrict__ y, int n,
+                                                      double* __restrict__ Dy) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double inv = 1. / dvec[i];
+  Dy[i] = inv * y[i];
 }
 
 // W = sum_z P_z + K_mm,s over the m x m entries (split-K partials in chunk order)
@@ -739,6 +744,7 @@ FitcSolver::FitcSolver(int n, int d, const double* d_X, const std::vector<double
 
 void FitcSolver::Prior(int cov_type, double var, double phi, double* red) {
   const int n = n_, m = m_, ldm = ldm_, d = d_;
+  kept_ = false;
   HIP_CHECK(hipMemsetAsync(info_.get(), 0, sizeof(int), stream_));
   dispatch_cov_fitc(cov_type, [&](auto c) {
     constexpr int COV = decltype(c)::value;
@@ -762,17 +768,13 @@ void FitcSolver::Prior(int cov_type, double var, double phi, double* red) {
   fitc_lower_t(stream_, Li_.get(), m, ldm, LiT_.get());
 }
 
-void FitcSolver::Factor(int cov_type, double var, double phi, const double* d_y, double* red) {
+void FitcSolver::FactorCommon(int cov_type, double var, double phi, double* red) {
   const int n = n_, m = m_, ldm = ldm_;
   double* dvec = vec_.get();
-  double* Dy = dvec + n;
-  double* yaux = Dy + n;
-  double* u = yaux + n;
-  double* w = u + ldm;
   Prior(cov_type, var, phi, red);
   const int nb4 = (n + 3) / 4;
-  hipLaunchKernelGGL(fitc_diag_kernel, dim3(nb4), dim3(256), 0, stream_, V_.get(), Kmn_.get(), d_y, n, m, ldm,
-                     1. + var * kJitterMult, dvec, Kd_.get(), Dy, part_.get());
+  hipLaunchKernelGGL(fitc_diag_kernel, dim3(nb4), dim3(256), 0, stream_, V_.get(), Kmn_.get(), n, m, ldm,
+                     1. + var * kJitterMult, dvec, Kd_.get(), part_.get());
   HIP_CHECK(hipGetLastError());
   launch_sum_blocks(part_.get(), nb4, 1, red + 2, stream_);
   // W = K_mn K_d^T + K_mm,s (split K over the n observations), Lw = chol(W), Lw^-1, W^-1
@@ -785,17 +787,58 @@ void FitcSolver::Factor(int cov_type, double var, double phi, const double* d_y,
   chol_lower(stream_, W_.get(), Wi_.get(), m, ldm, info_.get());
   launch_logdet_chol(stream_, W_.get(), ldm, m, red + 1);
   trtri_lower(stream_, W_.get(), Wi_.get(), T_.get(), 0, m, ldm);
+  fitc_lower_t(stream_, Wi_.get(), m, ldm, WiT_.get());
+}
+
+void FitcSolver::Factor(int cov_type, double var, double phi, const double* d_y, double* red) {
+  const int n = n_, m = m_, ldm = ldm_;
+  double* dvec = vec_.get();
+  double* Dy = dvec + n;
+  double* yaux = Dy + n;
+  double* u = yaux + n;
+  double* w = u + ldm;
+  // the response-independent part, unless Gram left it in place at these parameters
+  const bool kept = kept_ && kept_cov_ == cov_type && kept_var_ == var && kept_phi_ == phi && kept_red_ == red;
+  if (!kept) FactorCommon(cov_type, var, phi, red);
+  kept_ = false;   // the gradient of the evaluation that follows overwrites V and K_d
+  const int nb4 = (n + 3) / 4;
+  hipLaunchKernelGGL(fitc_dy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream_, dvec, d_y, n, Dy);
   // u = K_mn (y / d), w = W^-1 u = Lw^-T (Lw^-1 u) (fitc_chol_solve; the a slot as scratch), y_aux, q
   const int chunk = 64, nbg = (n + chunk - 1) / chunk;
   hipLaunchKernelGGL(fitc_gemv_part_kernel, dim3(nbg), dim3(256), 0, stream_, Kmn_.get(), Dy, n, m, ldm, chunk,
                      part_.get());
   hipLaunchKernelGGL(fitc_gemv_reduce_kernel, dim3((m + 3) / 4), dim3(256), 0, stream_, part_.get(), nbg, m, ldm, u);
-  fitc_lower_t(stream_, Wi_.get(), m, ldm, WiT_.get());
   fitc_chol_solve(stream_, Wi_.get(), WiT_.get(), u, m, ldm, w + ldm, w);
   hipLaunchKernelGGL(fitc_yaux_kernel, dim3(nb4), dim3(256), 0, stream_, Kmn_.get(), w, d_y, Dy, dvec, n, m, ldm, yaux,
                      part_.get());
   HIP_CHECK(hipGetLastError());
   launch_sum_blocks(part_.get(), nb4, 1, red + 3, stream_);
+}
+
+void FitcSolver::Gram(int cov_type, double var, double phi, const double* d_Z, int c, double* G_host,
+                      double* gram_ms) {
+  double* red = red_.get();
+  HIP_CHECK(hipEventRecord(ev_[0], stream_));
+  FactorCommon(cov_type, var, phi, red);
+  HIP_CHECK(hipEventRecord(ev_[1], stream_));
+  int info = 0;
+  HIP_CHECK(hipMemcpyAsync(&info, info_.get(), sizeof(int), hipMemcpyDeviceToHost, stream_));
+  lowrank_gram(stream_, m_, n_, c, ldm_, Kmn_.get(), vec_.get(), d_Z, Wi_.get(), gram_ws_, G_host);   // synchronises
+  if (gram_ms != nullptr) {
+    HIP_CHECK(hipEventRecord(ev_[2], stream_));
+    HIP_CHECK(hipEventSynchronize(ev_[2]));
+    float ms0 = 0.f, ms1 = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms0, ev_[0], ev_[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms1, ev_[0], ev_[2]));
+    gram_ms[0] = ms0;
+    gram_ms[1] = ms1;
+  }
+  if (info != 0) std::fill(G_host, G_host + (size_t)c * c, std::numeric_limits<double>::quiet_NaN());
+  kept_ = true;
+  kept_cov_ = cov_type;
+  kept_var_ = var;
+  kept_phi_ = phi;
+  kept_red_ = red;
 }
 
 void FitcSolver::Eval(int cov_type, double var, double phi, const double* d_y, bool want_grad, double* sums,

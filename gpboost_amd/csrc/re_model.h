@@ -145,6 +145,9 @@ class REModelAMD {
   int world_size() const { return world_; }
   int num_latent() const { return nu_; }
   void GetLastKernelTimes(double* ms);
+  // [factorization, whole call] device ms of the last covariate Gram matrix of a FITC / full-scale Vecchia model
+  // (EXTENSION: GPB_GetLastGramTimes; the evaluation that follows reuses the factorization)
+  void GetLastGramTimes(double* ms) const { ms[0] = last_gram_ms_[0]; ms[1] = last_gram_ms_[1]; }
   // FITC inducing points (host row-major m x d; EXTENSION: GPB_GetInducingPoints)
   const std::vector<double>& InducingPoints() const;
   bool is_fitc() const { return fitc_ != nullptr; }
@@ -377,10 +380,13 @@ class REModelAMD {
   double last_nll_ = 0.;
   std::vector<double> last_cov_pars_;
   double last_kernel_ms_[2] = {0., 0.};
+  double last_gram_ms_[2] = {0., 0.};
 
   // covariates (OptimLinRegrCoefCovPar) and stored data
   void InitializeOptimizerNames();
-  std::vector<double> Gram(const double* trafo);   // c x c Gram of [X | y - offset] (c = p + 1)
+  // c x c Gram of [X | y - offset] (c = p + 1). FITC / full-scale Vecchia: the solver keeps its factorization for
+  // the evaluation that follows at the same parameters (next_eval_grad: whether that one computes the gradient)
+  std::vector<double> Gram(const double* trafo, bool next_eval_grad = false);
   void UploadCovariates();
   void EnsureTransposedLists();                     // exact Vecchia: B^T lists for the training predictions
   void PsiInvVecchia(const double* trafo, double* yaux, double* diag);
@@ -395,7 +401,7 @@ class REModelAMD {
   bool has_fixed_effects_ = false;
   std::vector<double> offset_vo_;     // latent models: fixed effects F of the last call (Vecchia order)
   bool has_offset_ = false;
-  DevBuf<double> d_Zcov_;            // [X | y - offset], Vecchia order row-major n x c (Vecchia models)
+  DevBuf<double> d_Zcov_;            // [X | y - offset], row-major n x c in the solver's row order (not dense)
   DevBuf<double> d_Bf_, d_Df_, d_gram_part_, d_gram_out_;
   DevBuf<int> d_tptr_, d_trow_, d_tslot_;
   std::string optimizer_cov_, optimizer_coef_;

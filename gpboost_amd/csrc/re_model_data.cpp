@@ -128,15 +128,16 @@ void REModelAMD::AddLinearPredictor(const double* X_pred, int n_pred, double* mu
     for (int p = 0; p < n_pred; ++p) mu[p] += X_pred[(size_t)a * n_pred + p] * coef_[a];
 }
 
-// [X | y - offset] in the layout of the model's solver: Vecchia order row-major on the device
-// (Vecchia models), original order column-major on the host (dense, passed to DenseSolver::Gram).
+// [X | y - offset] in the layout of the model's solver: row-major on the device in the solver's row order
+// (Vecchia and full-scale Vecchia: the model order perm_; FITC: the original order), original order
+// column-major on the host (dense, passed to DenseSolver::Gram).
 void REModelAMD::UploadCovariates() {
-  if (!vecchia_) return;
+  if (!vecchia_ && !fitc_ && !vif_) return;
   const int n = cfg_.n, p = num_covariates_, c = p + 1;
   const double* fe = has_fixed_effects_ ? fixed_effects_.data() : nullptr;
   std::vector<double> Z((size_t)n * c);
   for (int i = 0; i < n; ++i) {
-    const int o = perm_[i];
+    const int o = fitc_ ? i : perm_[i];
     for (int a = 0; a < p; ++a) Z[(size_t)i * c + a] = X_cov_[(size_t)a * n + o];
     Z[(size_t)i * c + p] = y_raw_[o] - (fe ? fe[o] : 0.);
   }
@@ -145,10 +146,17 @@ void REModelAMD::UploadCovariates() {
   HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
-std::vector<double> REModelAMD::Gram(const double* trafo) {
+std::vector<double> REModelAMD::Gram(const double* trafo, bool next_eval_grad) {
   const int n = cfg_.n, p = num_covariates_, c = p + 1;
-  if (fitc_ || vif_)
-    Fatal("linear regression covariates with gp_approx = '%s' are not supported by gpboost_amd", cfg_.gp_approx.c_str());
+  if (fitc_ || vif_) {   // CalcXTPsiInvX, Woodbury forms (re_model_template.h:6078-6117); lowrank_gram.hip
+    if (cfg_.latent)
+      Fatal("linear regression covariates for likelihood '%s' are not supported by gpboost_amd (Gaussian likelihood "
+            "only)", cfg_.likelihood.c_str());
+    std::vector<double> G((size_t)c * c);
+    if (fitc_) fitc_->Gram(cfg_.cov_type, trafo[1], trafo[2], d_Zcov_.get(), c, G.data(), last_gram_ms_);
+    else vif_->Gram(cfg_.cov_type, trafo[1], trafo[2], next_eval_grad, d_Zcov_.get(), c, G.data(), last_gram_ms_);
+    return G;
+  }
   if (!vecchia_) {
     std::vector<double> Z((size_t)n * c), G((size_t)c * c);
     const double* fe = has_fixed_effects_ ? fixed_effects_.data() : nullptr;
@@ -188,7 +196,7 @@ EvalResult REModelAMD::EvalTrafoWls(const double* trafo, bool want_grad, bool fa
   // optim_utils.h:297-313: CalcCovFactorOrModeAndNegLL, ProfileOutCoef (beta by GLS, y_ = residuals),
   // EvalNegLogLikelihoodOnlyUpdateFixedEffects, ProfileOutSigma2; the gradient on the residuals
   UseDevice();
-  const std::vector<double> G = Gram(trafo);
+  const std::vector<double> G = Gram(trafo, want_grad);   // the evaluation below reuses its factorization
   for (double v : G)
     if (!std::isfinite(v)) {
       if (fatal_on_nan) Fatal("NaN or Inf occurred in X^T Psi^-1 X");

@@ -58,6 +58,13 @@ class VifSolver {
   // pvar (np, nullable); pcov (np x np column-major, nullable). Runs Eval(want_grad = false) first.
   void Predict(int cov_type, double var, double phi, const double* d_y, const double* Xp, int np, const int* nbr,
                int mp, bool cond_all, double* mean, double* pvar, double* pcov);
+  // G = Z^T Psi^-1 Z (host, c x c row-major) for the device matrix d_Z (n x c row-major, model order) on the
+  // transformed scale (DenseSolver::Gram's contract): G0 - S^T S with U = B Z, T = BK diag(1 / D) U, G0 = U^T
+  // diag(1 / D) U, S = L_M^-1 T (lowrank_gram.hip). Runs Prepare(grad) and keeps its results for the next
+  // Eval(want_grad == grad) at the same (cov_type, var, phi), which then reruns only its response-dependent part.
+  // A non-positive-definite factor gives a NaN G. gram_ms (nullable): device ms of Prepare and of the whole call.
+  void Gram(int cov_type, double var, double phi, bool grad, const double* d_Z, int c, double* G_host,
+            double* gram_ms = nullptr);
 
  private:
   friend class VifLaplace;   // the Laplace approximation for non-Gaussian likelihoods (vif_laplace.h)
@@ -67,6 +74,13 @@ class VifSolver {
   // K_mm,s, red[1] = log det M; M_copy (nullable, ldm x ldm): M before its factorization
   void Prepare(int cov_type, double var, double phi, bool grad, double* red, double* M_copy = nullptr);
   void Rows(int cov_type, double var, double phi, bool grad);
+  // Prepare's results are in place for (kept_cov_, kept_var_, kept_phi_, kept_grad_) with their sums in red_: set
+  // by Gram, used once by the next Eval, cleared by Prepare (every other entry overwrites the buffers through it)
+  bool kept_ = false, kept_grad_ = false;
+  int kept_cov_ = 0;
+  double kept_var_ = 0., kept_phi_ = 0.;
+  DevBuf<double> gram_U_;   // B Z (n x kCovMaxCols)
+  LowrankGramWork gram_ws_;
   // the prediction points' residual rows (Xp host np x d after the n observed points, nbr host np x mp):
   // KP = K_mp (m x np), Va = [V | L^-1 K_mp], Bvp (np x mp), Dp (np), dnb the neighbour lists on the device
   void PredRows(int cov_type, double var, double phi, const double* Xp, int np, const int* nbr, int mp,

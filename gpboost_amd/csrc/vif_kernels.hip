@@ -1101,6 +1101,7 @@ void VifSolver::Prepare(int cov_type, double var, double phi, bool want_grad, do
   FitcSolver& F = *F_;
   const int n = n_, m = m_, ldm = ldm_;
   const size_t mn = (size_t)ldm * n;
+  kept_ = false;
   // low-rank part (CalcSigmaComps): K_mn, K_mm, K_mm,s, dK_mm, L, L^-1, V = L^-1 K_mn, K_mm,s^-1; red[0] =
   // log det K_mm,s
   F.Prior(cov_type, var, phi, red);
@@ -1152,7 +1153,10 @@ void VifSolver::Eval(int cov_type, double var, double phi, const double* d_y, bo
   const int n = n_, m = m_, ldm = ldm_;
   double* red = red_.get();
   HIP_CHECK(hipEventRecord(ev_[0], s_));
-  Prepare(cov_type, var, phi, want_grad, red);
+  // the response-independent part, unless Gram left it in place at these parameters
+  const bool kept = kept_ && kept_cov_ == cov_type && kept_var_ == var && kept_phi_ == phi && kept_grad_ == want_grad;
+  if (!kept) Prepare(cov_type, var, phi, want_grad, red);
+  kept_ = false;   // the gradient below overwrites V, A, P_0 and P_1
   HIP_CHECK(hipEventRecord(ev_[1], s_));
   // y_aux = R^-1 y - R^-1 K M^-1 K^T R^-1 y with R^-1 = B^T D^-1 B (CalcYAux :8910-8925)
   double* v = vec_.get();
@@ -1285,6 +1289,35 @@ void VifSolver::Eval(int cov_type, double var, double phi, const double* d_y, bo
     sums[2 + p] = quad;
     sums[4 + p] = 2. * tr;
   }
+}
+
+void VifSolver::Gram(int cov_type, double var, double phi, bool grad, const double* d_Z, int c, double* G_host,
+                     double* gram_ms) {
+  if (latent_) Fatal("VifSolver::Gram is the Gaussian likelihood's Gram matrix (the model is latent)");
+  FitcSolver& F = *F_;
+  HIP_CHECK(hipEventRecord(ev_[0], s_));
+  Prepare(cov_type, var, phi, grad, red_.get());
+  HIP_CHECK(hipEventRecord(ev_[1], s_));
+  int info = 0;
+  HIP_CHECK(hipMemcpyAsync(&info, F.info_.get(), sizeof(int), hipMemcpyDeviceToHost, s_));
+  gram_U_.alloc((size_t)n_ * kCovMaxCols);
+  launch_vecchia_bz(n_, nn_, c, nbr_.get(), Bv_.get(), d_Z, gram_U_.get(), s_);
+  lowrank_gram(s_, m_, n_, c, ldm_, BK_.get(), D_.get(), gram_U_.get(), F.Wi_.get(), gram_ws_, G_host);   // synchronises
+  if (gram_ms != nullptr) {
+    HIP_CHECK(hipEventRecord(ev_[2], s_));
+    HIP_CHECK(hipEventSynchronize(ev_[2]));
+    float ms0 = 0.f, ms1 = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms0, ev_[0], ev_[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms1, ev_[0], ev_[2]));
+    gram_ms[0] = ms0;
+    gram_ms[1] = ms1;
+  }
+  if (info != 0) std::fill(G_host, G_host + (size_t)c * c, std::numeric_limits<double>::quiet_NaN());
+  kept_ = true;
+  kept_grad_ = grad;
+  kept_cov_ = cov_type;
+  kept_var_ = var;
+  kept_phi_ = phi;
 }
 
 void VifSolver::GetFactor(double* D, double* Bv) const {

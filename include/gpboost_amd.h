@@ -359,6 +359,10 @@ GPBOOST_AMD_EXPORT int GPB_GetCholeskyPlanInfo(REModelHandle handle, double* inf
  * evaluations after the first call of this function (they cost ~10 us of host time each);
  * before that it returns zeros. */
 GPBOOST_AMD_EXPORT int GPB_GetLastKernelTimes(REModelHandle handle, double* kernel_ms);
+/* Measurement only: device time (HIP events, ms) of the last covariate Gram matrix [X | y]^T Psi^-1 [X | y] of
+ * a gp_approx = "fitc" / "full_scale_vecchia" model: gram_ms[0] = its factorization (which the evaluation that
+ * follows reuses), gram_ms[1] = the whole call. Zeros before the first one. */
+GPBOOST_AMD_EXPORT int GPB_GetLastGramTimes(REModelHandle handle, double* gram_ms);
 
 /* Benchmark support (latent Vecchia, iterative): device time of the operator
  * A = B^T D^-1 B + W and of the VADU preconditioner on t columns, on the factor of the last
@@ -422,6 +426,12 @@ GPBOOST_AMD_EXPORT int GPB_TestDenseChol(int n, int ld, double* A, double* W, in
  * (n x n, nullable). Fails if A is not positive definite. */
 GPBOOST_AMD_EXPORT int GPB_TestDenseSpdSolveInverse(int n, const double* A, const double* b, double* x,
                                                     double* diag, double* inv);
+/* The weighted tall-skinny product behind the covariate Gram matrix of gp_approx = "fitc" / "full_scale_vecchia"
+ * on host arrays: T_out (m x c row-major) = A diag(w) U and G0_out (c x c row-major) = U^T diag(w) U. A: m x n
+ * column-major with leading dimension round_up(m, 64) (a_len doubles, checked); w: n; U: n x c row-major,
+ * 1 <= c <= 32. No reference counterpart (tests). */
+GPBOOST_AMD_EXPORT int GPB_TestWeightedTallSkinny(int m, int n, int c, const double* A, int64_t a_len,
+                                                  const double* w, const double* U, double* T_out, double* G0_out);
 
 /* The sparse multifrontal Cholesky of A = B^T D^-1 B + diag(W) (matrix_inversion_method = "cholesky") on host
  * arrays: its plan alone, and the numeric operations on a small handle. No reference counterpart (tests).
