@@ -28,9 +28,10 @@
 //      675 DPP fmacs per problem set: 376 + 119 on the B rows, 120 + 28 + 32 on the A rows (899 with
 //      the A rows' columns 16..31 carried through pivots 0..15: 376 + 119 and 376 + 28; 990 for the
 //      plain 30-pivot Gauss-Jordan on both rows).
-//      a_v = M[v][30] / M[v][v], w_v = M[v][31] / M[v][v] (the pivots are captured when broadcast);
+//      a_v = M[v][30] / M[v][v], w_v = M[v][31] / M[v][v] (each pivot's reciprocal is kept by its own lane);
 //   3. a^T dC a and w^T dC a over each lane's circulant pairs ([a, w] pairs with the same wrap copies);
-//   4. the eight group sums by DPP within the 16-lane row, then the six row partials.
+//   4. the eight group sums by DPP within the 16-lane row, reduced together (sum16x8), then the row partials
+//      (DESIGN.md §6); log(D) is kept per lane and taken once per 16 problem sets (flush_logs).
 // Two kernels run this loop (rows16_body): vecchia_rows16_kernel computes every pair's distance from the
 // coordinates as described in 1.; vecchia_rows16d_kernel (VecchiaRowsArgs::R set) reads the distances
 // that vecchia_rows16_dist_kernel stored once per structure, loaded one problem set ahead, and holds no
@@ -38,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -66,6 +68,24 @@ constexpr int kD3 = 3;   // coordinate dimension bound (VecchiaRowsArgs.d <= 3)
 //   - the pair distances stored per structure and streamed (profiles/rows16_dist/RESULTS.md; the parent's
 //     spread 28): 6378 vs 5628, 2183 instead of 2661 VALU instructions per problem set for 384 MB more HBM
 //     reads per launch at n = 100k. Non-temporal loads of the records: 6241 vs 6230, inside the noise.
+//   - the per-set scalar and select overhead (profiles/rows16_epilogue/RESULTS.md; five sessions, each on the
+//     card it was given; the parent's spread 42 - 77): 6760 vs 6391, 6714 vs 6522, 6390 vs 6161, 6372 vs 6127,
+//     6337 vs 6055 with all four of the following, 1914 instead of 2174 VALU instructions executed per
+//     problem set.
+//     Without one of them (first session; all four 6760):
+//       log(D) per lane, taken once per 16 sets with all lanes useful, instead of once per set with 4 of 64
+//       lanes (flush_logs; the same additions in the same order, nll bit-equal): 6474 without;
+//       the pivot's own lane by two 64-bit moves under a scalar lane mask, the reciprocal kept instead of
+//       the pivot, instead of a compare and two 64-bit selects per pivot and two reciprocals at the end
+//       (own_lane): 6555 without;
+//       the covariances' store addresses by one add per pair and an immediate, the wrapped slots by two
+//       stores under compile-time lane masks (lds_write_at, lds_write_wrap): 6652 without;
+//       the eight group sums reduced together, 61 instead of 96 instructions (sum16x8): 6707 without; its
+//       margin (53, then 36, 52, 47 in the later sessions) is at or below the parent's spread, see RESULTS.
+// Rejected with them: the next set's loads issued after pivot 15 or 21 instead of after the elimination
+// (6198 and 6304 vs 6338: slower the earlier they go); the own lane zeroing its entry of column j and
+// keeping the pivot right after the broadcast, beside the reciprocal, with the two reciprocals back at the end
+// (10 instructions more, a shorter dependent chain per pivot: 6320 vs 6372).
 // Rejected: the next pivot's broadcast, reciprocal and multipliers issued after the step's first three
 // columns and left to the compiler to schedule under the rest of the step's fmacs (it did interleave
 // them): 5616 with vs 5628 without, inside the noise; round 4 had measured the hand-pinned form slower.
@@ -136,12 +156,96 @@ __device__ __forceinline__ void lds_read_split2(double& a, double& b, unsigned u
       : "memory", "scc");
 }
 
-__device__ __forceinline__ double sum16(double v) {   // fixed-order sum over the 16-lane row
-  v += dpp32x2<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp32x2<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp32x2<0x141>(v);   // row_half_mirror
-  v += dpp32x2<0x140>(v);   // row_mirror
-  return v;
+// 16-bit lane mask of one 16-lane row, for the two rows of an exec half. The statements below narrow exec
+// by immediates (masks in scalar registers were hoisted out of the loop and spilled) and write the mask as
+// the first source: the `exec_lo, exec_lo, mask` form marks lds_read_split2's blocks for
+// tests/test_isa_rows16_loads.py.
+constexpr unsigned rows2(unsigned m16) { return (m16 & 0xFFFFu) * 0x00010001u; }
+
+// Pivot J's own lane (lane J of each 16-lane row) alone: it keeps the pivot's reciprocal and its multiplier
+// becomes 0. Two 64-bit moves under a scalar lane mask instead of a lane compare and two 64-bit selects;
+// the exec mask is saved and restored inside the statement.
+template <int J>
+__device__ __forceinline__ void own_lane(double& inv, double& mul, double rinv) {
+  unsigned long saved;
+  asm volatile(
+      "s_mov_b64 %2, exec\n\t"
+      "s_and_b32 exec_lo, %4, exec_lo\n\t"
+      "s_and_b32 exec_hi, %4, exec_hi\n\t"
+      "v_mov_b64 %0, %3\n\t"
+      "v_mov_b64 %1, 0\n\t"
+      "s_mov_b64 exec, %2"
+      : "+v"(inv), "+v"(mul), "=&s"(saved)
+      : "v"(rinv), "n"(rows2(1u << J))
+      : "scc");
+}
+
+template <int OFF>
+__device__ __forceinline__ void lds_write_at(unsigned addr, double v) {   // LDS byte address + immediate
+  asm volatile("ds_write_b64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+
+// Slot h + 16's pair at delta DL: packed(h + 16 + DL, h + 16) at `in + tri(DL)`, or, in the lanes whose
+// partner wraps past slot 30 (h > 14 - DL, a compile-time lane mask), packed(h + 16, h + DL - 15) at
+// `wrap + DL`: two stores under complementary masks, no compare and no address select.
+template <int DL>
+__device__ __forceinline__ void lds_write_wrap(unsigned in, unsigned wrap, double v) {
+  if constexpr (DL >= 15) {
+    lds_write_at<DL * 8>(wrap, v);
+  } else {
+    unsigned long saved;
+    asm volatile(
+        "s_mov_b64 %0, exec\n\t"
+        "s_and_b32 exec_lo, %4, exec_lo\n\t"
+        "s_and_b32 exec_hi, %4, exec_hi\n\t"
+        "ds_write_b64 %2, %3 offset:%6\n\t"
+        "s_andn2_b64 exec, %0, exec\n\t"
+        "ds_write_b64 %1, %3 offset:%5\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(saved)
+        : "v"(in), "v"(wrap), "v"(v), "n"(rows2(0xFFFFu << (15 - DL))), "n"(DL * (DL + 1) / 2 * 8), "n"(DL * 8)
+        : "memory", "scc");
+  }
+}
+
+// One level of the transposed reduction of two quantities over the lane exchange CTRL, which swaps the
+// banks (4-lane groups of the 16-lane row) in KEEP_X with the others: the lanes of KEEP_X end with
+// x + x', the others with y + y' (' = the exchange partner's). Bank masks do the selects inside the DPP
+// moves: 6 moves and one add for two quantities instead of 4 moves and two adds each level.
+template <int CTRL, int KEEP_X>
+__device__ __forceinline__ double pair_level(double x, double y) {
+  constexpr int KEEP_Y = 0xF & ~KEEP_X, SELF = 0xE4;   // quad_perm [0,1,2,3]
+  int plo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xF, KEEP_X, false);
+  int phi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xF, KEEP_X, false);
+  plo = __builtin_amdgcn_update_dpp(plo, __double2loint(y), CTRL, 0xF, KEEP_Y, false);
+  phi = __builtin_amdgcn_update_dpp(phi, __double2hiint(y), CTRL, 0xF, KEEP_Y, false);
+  const int klo = __builtin_amdgcn_update_dpp(__double2loint(x), __double2loint(y), SELF, 0xF, KEEP_Y, false);
+  const int khi = __builtin_amdgcn_update_dpp(__double2hiint(x), __double2hiint(y), SELF, 0xF, KEEP_Y, false);
+  return __hiloint2double(khi, klo) + __hiloint2double(phi, plo);
+}
+
+// The eight group sums together: q[0..7] of every lane in, the totals out in lane 0 (t[0] in all 16 lanes).
+// Two transposed levels (row_mirror, row_half_mirror: whole banks change places) take 8 registers to 2, each
+// bank then holding one quantity's four partial sums per register; two plain levels sum within the bank.
+__device__ __forceinline__ void sum16x8(const double (&q)[8], double (&t)[8]) {
+  double a[4], b[2];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a[k] = pair_level<0x140, 0x3>(q[2 * k], q[2 * k + 1]);   // banks 0,1: q[2k]; 2,3: q[2k+1]
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    double v = pair_level<0x141, 0x5>(a[2 * k], a[2 * k + 1]);   // banks 0..3: q[4k], q[4k+2], q[4k+1], q[4k+3]
+    v += dpp32x2<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp32x2<0x4E>(v);   // quad_perm [2,3,0,1]
+    b[k] = v;
+  }
+  t[0] = bcast16<0>(b[0]);
+  t[1] = bcast16<8>(b[0]);
+  t[2] = bcast16<4>(b[0]);
+  t[3] = bcast16<12>(b[0]);
+  t[4] = b[1];
+  t[5] = bcast16<8>(b[1]);
+  t[6] = bcast16<4>(b[1]);
+  t[7] = bcast16<12>(b[1]);
 }
 
 __device__ __forceinline__ double recip(double x) {   // hardware reciprocal + two Newton steps (~1 ulp)
@@ -284,6 +388,19 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
     }
   };
   if (set_at(0) < nsets) prefetch(set_at(0));
+  // log(D) leaves the set loop: lane (it & 15) of each 16-lane row keeps trip it's D (1 where the slot has
+  // no row), and every 16th trip, and once after the loop, all lanes take the log of theirs at once and
+  // the 16 logs go to the slot's acc[0] in trip order (the additions the per-trip form made, in its order)
+  double keepD = 1.;
+  bool kept = false;
+  auto flush_logs = [&]() {
+    const double lg = log(keepD);
+    double s = acc[0];
+    sfor<0, 16>([&](auto L) { fmac_bcast16<decltype(L)::value, decltype(L)::value == 0>(s, lg, 1.); });
+    if ((lane & 15) == 0) acc[0] = s;
+    keepD = 1.;
+    kept = false;
+  };
   for (int it = 0; it < R; ++it) {
     const int set = set_at(it);
     if (set >= nsets) break;
@@ -322,24 +439,34 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
     double w0[15], w1[15];
     {
       const int b0 = tri(h) + h, b1 = tri(v1) + v1;
-#pragma unroll
-      for (int dl = 1; dl <= 15; ++dl) {
+      // packed(v + dl, v) = b + v dl + tri(dl): the lane part carried by one add per pair, tri(dl) in the
+      // store's immediate
+      const unsigned h8 = h * 8, v8 = v1 * 8;
+      unsigned p0 = lds_addr(Cp + b0), p1 = lds_addr(Cp + b1);
+      const unsigned pw = lds_addr(Cp + b1 - 31);
+      sfor<1, 16>([&](auto DL) {
+        constexpr int dl = decltype(DL)::value;
         double cv, dcv;
         if constexpr (STORED) cov_dcov_r<COV>(rr[dl - 1].x, var, phi, cv, dcv, ek);
         else cov_dcov_sq<COV>(sq_dist<ND>(x0, nbx + (h + dl) * CS), var, phi, cv, dcv, ek);
-        Cp[b0 + h * dl + dl * (dl + 1) / 2] = cv;   // packed(h + dl, h)
+        p0 += h8;
+        asm("" : "+v"(p0));   // stays an add (not re-formed as h8 * dl)
+        lds_write_at<dl * (dl + 1) / 2 * 8>(p0, cv);   // packed(h + dl, h)
         w0[dl - 1] = dcv;
-      }
-#pragma unroll
-      for (int dl = 1; dl <= 15; ++dl) {
+      });
+      sfor<1, 16>([&](auto DL) {
+        constexpr int dl = decltype(DL)::value;
         double cv, dcv;
         if constexpr (STORED) cov_dcov_r<COV>(rr[dl - 1].y, var, phi, cv, dcv, ek);
         else cov_dcov_sq<COV>(sq_dist<ND>(x1, nbx + (v1 + dl) * CS), var, phi, cv, dcv, ek);
         // packed(v1 + dl, v1), or past slot 30 packed(v1, v1 + dl - 31) (slot 31: row 31, overwritten below)
-        const int pos = (v1 + dl <= kMK) ? b1 + v1 * dl + dl * (dl + 1) / 2 : b1 + dl - 31;
-        Cp[pos] = cv;
+        if constexpr (dl < 15) {
+          p1 += v8;
+          asm("" : "+v"(p1));
+        }
+        lds_write_wrap<dl>(p1, pw, cv);
         w1[dl - 1] = dcv;
-      }
+      });
     }
     lds_sync();
     // border row 31 (y_nbr); row 30 (c) came from the slot-30 pairs
@@ -394,24 +521,20 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
     }
 
     // Gauss-Jordan, 30 pivots: M[j][c] = M[c][j] from lane c mod 16 (register set c / 16)
-    double dg0 = 1., dg1 = 1.;
+    double i0 = 1., i1 = 1.;   // 1 / M[v][v] of rows h and h + 16, each taken in its pivot's own lane (rows 30, 31: 1)
     // pivot j's negated multipliers for rows h (pivots 0..15 only) and h + 16; the pivot row's own is 0
     auto pivot = [&](auto J, double& m0, double& m1) {
       constexpr int j = decltype(J)::value;
       constexpr int jl = j & 15;
       const double piv = bcast16<jl>(j >= 16 ? r1[j] : r0[j]);
       const double rinv = recip(piv);
-      const bool own = h == jl;
-      const double f1 = r1[j] * rinv;
+      m1 = -(r1[j] * rinv);
       if constexpr (j >= 16) {
         m0 = 0.;
-        m1 = -(own ? 0. : f1);
-        dg1 = own ? piv : dg1;
+        own_lane<jl>(i1, m1, rinv);
       } else {
-        const double f0 = r0[j] * rinv;
-        m0 = -(own ? 0. : f0);
-        m1 = -f1;
-        dg0 = own ? piv : dg0;
+        m0 = -(r0[j] * rinv);
+        own_lane<jl>(i0, m0, rinv);
       }
     };
     sfor<0, kMK>([&](auto J) {
@@ -440,7 +563,6 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
       if constexpr (!jhi) r0[j] = nf0;   // column j of the A rows is dead: keep the step's multiplier there
     });
     {   // A rows: M[h][30..31] -= sum_{c=16..29} M[h][c] x_c, x_c = M[c][30..31] / M[c][c] (lane c - 16)
-      const double i1 = recip(dg1);
       const double na = rv1 ? -(r1[kMK] * i1) : 0., nw = rv1 ? -(r1[kMK + 1] * i1) : 0.;
       sfor<16, kMK>([&](auto C) {
         constexpr int c = decltype(C)::value;
@@ -476,7 +598,6 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
       dc0 = Cp[h <= 14 ? h * kK + kMK : 14 * kK + 15];
       dc1 = h <= 13 ? Cp[(13 - h) * kK + v1] : 0.;
     }
-    const double i0 = recip(dg0), i1 = recip(dg1);
     const double a0 = rv0 ? r0[kMK] * i0 : 0., w0v = rv0 ? r0[kMK + 1] * i0 : 0.;
     const double a1 = rv1 ? r1[kMK] * i1 : 0., w1v = rv1 ? r1[kMK + 1] * i1 : 0.;
     if (active && a.B_out != nullptr) {
@@ -509,14 +630,10 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
     }
 
     // ---- 4. group sums (16 lanes) and the row partials
-    const double ac = sum16(a0 * c0 + a1 * c1);
-    const double ay = sum16(a0 * y0s + a1 * y1s);
-    const double aa = sum16(a0 * a0 + a1 * a1);
-    const double avv = sum16(a0 * w0v + a1 * w1v);
-    const double dca = sum16(dc0 * a0 + dc1 * a1);
-    const double dcv = sum16(dc0 * w0v + dc1 * w1v);
-    const double ta = sum16(tA);
-    const double tv = sum16(tV);
+    double gs[8];   // ac in every lane, the others in lane 0 alone (the block below)
+    sum16x8({a0 * c0 + a1 * c1, a0 * y0s + a1 * y1s, a0 * a0 + a1 * a1, a0 * w0v + a1 * w1v, dc0 * a0 + dc1 * a1,
+             dc0 * w0v + dc1 * w1v, tA, tV}, gs);
+    const double ac = gs[0], ay = gs[1], aa = gs[2], avv = gs[3], dca = gs[4], dcv = gs[5], ta = gs[6], tv = gs[7];
     const double D = var + a.d_nugget - ac;          // Vecchia_utils.cpp:1351, 1507, 1562
     const double Dinv = 1. / D;
     if (active && h == 0 && a.Dinv_out != nullptr) a.Dinv_out[i - a.row_base] = Dinv;
@@ -527,15 +644,20 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
       const double uk_var = -delta * avv;
       const double dD_rng = -(2. * dca - ta);
       const double uk_rng = -(dcv - tv);
-      acc[0] += log(D);
       acc[1] += By * u;
       acc[2] += uk_var * u - 0.5 * u * u * dD_var;
       acc[3] += uk_rng * u - 0.5 * u * u * dD_rng;
       acc[4] += Dinv * dD_var;
       acc[5] += Dinv * dD_rng;
     }
+    if (want_like) {
+      keepD = (active && h == (it & 15)) ? D : keepD;
+      kept = true;
+      if ((it & 15) == 15) flush_logs();
+    }
   }
   if (!want_like) return;
+  if (kept) flush_logs();
   __syncthreads();
   const double* red = smem + 4 * PD;   // 4 x kVecchiaSums
   if (lane < kVecchiaSums) {
@@ -605,6 +727,9 @@ int launch16_at(size_t lds, const VecchiaRowsArgs& a, hipStream_t s) {
   }
   const int need = (a.r1 - a.r0 + 3) / 4;
   int blocks = std::min(need, cap);
+  // GPBOOST_AMD_ROWS16_GRID=<G> clamps the grid to [1, cap] (read at every launch): a small model can give a
+  // wave many problem sets, for the tests of what the loop carries from trip to trip
+  if (const char* e = std::getenv("GPBOOST_AMD_ROWS16_GRID")) blocks = std::min(blocks, std::max(1, std::atoi(e)));
   if (a.sched == 2) {   // the same number of sets per wave
     const int rounds = (need + blocks - 1) / blocks;
     blocks = (need + rounds - 1) / rounds;
