@@ -586,6 +586,18 @@ class GPModel:
         _safe_call(lib().GPB_GetVecchiaFactor(self.handle, _dp(cp), _dp(dinv), _dp(b)))
         return dinv, b
 
+    def vif_factor(self, cov_pars):
+        """The residual Vecchia factor of a "full_scale_vecchia" model at cov_pars in the model order
+        (GPB_GetVifFactor): perm, nbr (n x num_neighbors), D (n), B (n x num_neighbors values), dD (2 x n) and
+        dB (2 x n x num_neighbors), the derivatives with respect to log var and log phi on the transformed scale."""
+        cp = self._check_cov_pars(cov_pars)
+        n, m = self.num_data, min(self.num_neighbors, self.num_data - 1)
+        perm, nbr = np.zeros(n, dtype=np.int32), np.zeros((n, m), dtype=np.int32)
+        d, b = np.zeros(n), np.zeros((n, m))
+        dd, db = np.zeros((2, n)), np.zeros((2, n, m))
+        _safe_call(lib().GPB_GetVifFactor(self.handle, _dp(cp), _ip(perm), _ip(nbr), _dp(d), _dp(b), _dp(dd), _dp(db)))
+        return dict(perm=perm, nbr=nbr, D=d, B=b, dD=dd, dB=db)
+
     def vecchia_rows_info(self):
         """Stored pair distances of the exact Vecchia row kernel: stored (0/1), bytes, rows, build_ms."""
         out = np.zeros(4)

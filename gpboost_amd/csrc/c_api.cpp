@@ -19,6 +19,7 @@
 #include "latent_test.h"
 #include "re_model.h"
 #include "sparse_chol.h"
+#include "vif_test.h"
 
 using gpb_amd::GroupedModel;
 using gpb_amd::REModelAMD;
@@ -917,6 +918,46 @@ int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, double delta, int pm
   if (block_len != (int64_t)c->n() * t)
     gpb_amd::Fatal("%s: the blocks hold %lld entries, n t = %lld", fn, (long long)block_len, (long long)c->n() * t);
   c->lv().TestPcg(t, n_single, delta, pmax_single, pmax_block, RHS, U, its, flags);
+  API_END();
+}
+
+int GPB_TestVifRows(int n_total, int d, int i0, int nn, int m, const double* X, int64_t x_len, const int32_t* nbr,
+                    int64_t nbr_len, const double* V, const double* P0, const double* P1, int64_t mat_len, int cov_type,
+                    double var, double phi, double nugget, double cjit, int grad, int form, int order, double pad_fill,
+                    double* D, double* Bv, double* dD0, double* dD1, double* dBv0, double* dBv1, int64_t rows_len,
+                    int* guard_flag) {
+  API_BEGIN();
+  const gpb_amd::VifRowsTest t{n_total, d,   i0,     nn,   m,    X,     nbr,      V, P0, P1,  cov_type, var,
+                               phi,     nugget, cjit, grad, form, order, pad_fill, D, Bv, dD0, dD1,      dBv0, dBv1};
+  gpb_amd::test_vif_rows(t, x_len, nbr_len, mat_len, rows_len, guard_flag);
+  API_END();
+}
+
+int GPB_TestVifApply(int op, int n, int nn, int m, const int32_t* nbr, int64_t nbr_len, const double* coef,
+                     int64_t coef_len, const double* D, const double* in, int64_t in_len, double self, int div,
+                     int want_div, const double* X, int d, int order, double pad_fill, double* out, double* out2,
+                     int64_t out_len, int* guard_flag) {
+  API_BEGIN();
+  gpb_amd::test_vif_apply(op, n, nn, m, nbr, nbr_len, coef, coef_len, D, in, in_len, self, div, want_div, X, d, order,
+                          pad_fill, out, out2, out_len, guard_flag);
+  API_END();
+}
+
+int GPB_TestVifVector(int op, int n, int m, int d, int cov_type, double var, double phi, double pad_fill,
+                      const double* const* arrays, const int64_t* lens, int n_arrays, const int32_t* sum_ops, int nt,
+                      double* out, int64_t out_len, int* guard_flag) {
+  API_BEGIN();
+  gpb_amd::test_vif_vector(op, n, m, d, cov_type, var, phi, pad_fill, arrays, lens, n_arrays, sum_ops, nt, out, out_len,
+                           guard_flag);
+  API_END();
+}
+
+int GPB_GetVifFactor(REModelHandle handle, const double* cov_pars, int32_t* perm, int32_t* neighbors, double* D,
+                     double* B_vals, double* dD, double* dB_vals) {
+  API_BEGIN();
+  if (cov_pars == nullptr || D == nullptr || B_vals == nullptr || dD == nullptr || dB_vals == nullptr)
+    gpb_amd::Fatal("GPB_GetVifFactor: an argument is NULL");
+  model(handle)->GetVifFactor(cov_pars, perm, neighbors, D, B_vals, dD, dB_vals);
   API_END();
 }
 

@@ -1634,6 +1634,19 @@ void REModelAMD::GetVecchiaFactor(const double* cov_pars_orig, double* Dinv, dou
   HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
+void REModelAMD::GetVifFactor(const double* cov_pars_orig, int* perm, int* nbr, double* D, double* Bvals, double* dD,
+                              double* dBvals) {
+  if (!vif_) Fatal("model does not use gp_approx = 'full_scale_vecchia'");
+  if (cfg_.latent) Fatal("GetVifFactor is only available for the Gaussian likelihood");
+  UseDevice();
+  double trafo[3];
+  TransformCovPars(cov_pars_orig, trafo);
+  const size_t n = cfg_.n, nb = n * cfg_.num_neighbors;
+  if (perm) std::copy(perm_.begin(), perm_.end(), perm);
+  if (nbr) std::copy(vif_nbr_.begin(), vif_nbr_.end(), nbr);
+  vif_->Factor(cfg_.cov_type, trafo[1], trafo[2], D, Bvals, dD, dD + n, dBvals, dBvals + nb);
+}
+
 void combine_partials(const double* s, int n, double sigma2_in, int profile, double* nll, double* grad,
                       double* sigma2_out) {
   // s = [logdet, q, s1_var, s1_range, s2_var, s2_range]

@@ -131,6 +131,9 @@ class REModelAMD {
 
   void GetVecchiaStructure(int* perm, int* nbr) const;
   void GetVecchiaFactor(const double* cov_pars_orig, double* Dinv, double* Bvals);
+  // full_scale_vecchia: model order, neighbour lists (nullable), D, B values and their two derivatives (EXTENSION)
+  void GetVifFactor(const double* cov_pars_orig, int* perm, int* nbr, double* D, double* Bvals, double* dD,
+                    double* dBvals);
   // [stored (0/1), bytes, rows, build ms] of the 16-lane row kernel's stored pair distances (EXTENSION)
   void GetVecchiaRowsInfo(double* out);
   // Latent factor with range derivatives (EXTENSION, latent models only).

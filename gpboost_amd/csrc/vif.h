@@ -22,6 +22,7 @@
 // Cholesky and solves in LDS / registers of that wave; sparse B / B^T products over contiguous m-vectors
 // (one wave per point; B^T vectors from the factor values gathered into column order); every m x n /
 // m x m product on the fp64 MFMA GEMM (split-K for the m x m Woodbury Gram).
+// A row whose residual matrix is not positive definite gets D_i = NaN (VifRowsLaunch below), so the sums are NaN.
 //
 // HBM layout: every m x n matrix column-major with leading dimension ldm = round_up(m, 64) (point i's m
 // entries contiguous), the B / D factor and its derivatives as n x nn value rows beside the neighbour lists.
@@ -37,6 +38,84 @@
 
 namespace gpb_amd {
 
+// ---- host launch code of the row-factor, product and vector kernels (vif_kernels.hip): the one way these kernels
+// are launched, by VifSolver and by the test entries (vif_test.cpp) alike.
+
+// One launch of the residual row factor for the rows i0 .. n_total - 1 (device pointers; vif_kernels.hip states the
+// formulas). form 0: the production dispatch (the MFMA Gram form for nn <= 31, else the LDS-staged form), 1: the
+// MFMA form (nn <= 31), 2: the LDS-staged form. Limits: nn <= 48 with derivatives, <= 64 without.
+// Non-positive-definite contract: a row whose residual matrix C has a pivot that is not > 0 or not finite gets
+// D_i = NaN (in both forms; its B / dB / dD entries are unspecified); every other row is unaffected, and the
+// evaluation's sums (log D) become NaN.
+struct VifRowsLaunch {
+  const double* X = nullptr;     // n_total x d
+  const int* nbr = nullptr;      // (n_total - i0) x nn, row i - i0 holds min(i, nn) indices < i
+  int n_total = 0, d = 0, nn = 0, m = 0, ldm = 0, i0 = 0;
+  const double* V = nullptr;     // m x n_total (ldm)
+  const double* P0 = nullptr;    // with grad
+  const double* P1 = nullptr;
+  int cov_type = 0;
+  double var = 0., phi = 0., nugget = 1., cjit = 1.;
+  bool grad = false;
+  int form = 0;
+  const int* ord = nullptr;      // nullable: the n_total - i0 rows in processing order (vif_morton_order)
+  double* Bv = nullptr;          // (n_total - i0) x nn
+  double* D = nullptr;           // n_total - i0
+  double* dBv0 = nullptr;
+  double* dBv1 = nullptr;
+  double* dD0 = nullptr;
+  double* dD1 = nullptr;
+};
+void vif_launch_rows(const VifRowsLaunch& L, hipStream_t s);
+constexpr int kVifMaxNn = 64, kVifMaxNnGrad = 48, kVifMaxNnMfma = 31;
+
+// the points along a Morton curve of their (first two) coordinates (X host row-major n x d)
+std::vector<int> vif_morton_order(const double* X, int n, int d);
+// B^T lists of the n x nn neighbour lists: for every column j the rows i (ascending) that hold j, with the slot
+// i nn + r of the value; returns the number of entries
+int vif_transpose_lists(int n, int nn, const int* nbr, std::vector<int>& tptr, std::vector<int>& trow,
+                        std::vector<int>& tslot);
+
+// the graph of the sparse products (device pointers); ord nullable
+struct VifGraph {
+  int n = 0, nn = 0, m = 0, ldm = 0;
+  const int* nbr = nullptr;
+  const int* tptr = nullptr;
+  const int* trow = nullptr;
+  const int* ord = nullptr;
+};
+// out[:, i] = self in[:, i] + sum_r coef[i nn + r] in[:, nbr[i nn + r]], div: then times 1 / D_i; out_div
+// (nullable): the same columns times 1 / D_i (D is read only with div or out_div)
+void vif_launch_brow(hipStream_t s, const VifGraph& g, const double* in, const double* coef, const double* D,
+                     double self, bool div, double* out, double* out_div);
+// out[:, j] = self in[:, j] + sum over column j's entries t of coefT[t] in[:, trow[t]]
+void vif_launch_bcol(hipStream_t s, const VifGraph& g, const double* in, const double* coefT, double self, double* out);
+// out_i = (self x_i + sum_r coef[i nn + r] x[nbr[i nn + r]]) (/ D_i with D)
+void vif_launch_bvec(hipStream_t s, const VifGraph& g, const double* x, const double* coef, const double* D,
+                     double self, double* out);
+void vif_launch_btvec(hipStream_t s, const VifGraph& g, const double* x, const double* coefT, double self, double* out);
+void vif_launch_gather(hipStream_t s, int nnz, const int* tslot, const double* coef, double* coefT);
+// out (m) = M x for the m x n matrix M (ldm); part: (n + 63) / 64 x ldm doubles
+void vif_launch_gemv(hipStream_t s, int n, int m, int ldm, const double* M, const double* x, double* part, double* out);
+// out_i = M[:, i] . w (w != nullptr) or M[:, i] . M2[:, i], i < cols
+void vif_launch_coldot(hipStream_t s, int cols, int m, int ldm, const double* M, const double* w, const double* M2,
+                       double* out);
+// z_i = (e_i - dD_i u_i) / D_i
+void vif_launch_zvec(hipStream_t s, int n, const double* dD, const double* u, const double* e, const double* D,
+                     double* z);
+// Sums over i < n of up to 8 elementwise terms; op 0: a (b) (c) (nullable factors), 1: log a, 2: a (b) / c,
+// 3: a b^2 / c^2, 4: a b / c^2. part: min(512, blocks) x nt doubles; out: nt sums.
+struct VifTerms {
+  const double* a[8];
+  const double* b[8];
+  const double* c[8];
+  int op[8];
+};
+void vif_launch_sum(hipStream_t s, int n, int nt, const VifTerms& T, double* part, double* out);
+// dK_mn / dlog(phi) (m x n, ldm) for the points X (n x d) and the inducing points Z (m x d)
+void vif_launch_dkmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
+                     double var, double phi, double* dK);
+
 class VifSolver {
  public:
   // d_X: device row-major n x d coordinates in the model order; Z: host row-major m x d inducing points;
@@ -49,8 +128,14 @@ class VifSolver {
   // y_aux, s2_k = tr(Psi^-1 dPsi_k) with the reference's dPsi_k (un-jittered dK_mm, B_grad, D_grad). A
   // non-positive-definite factor gives NaN sums. kernel_ms[0] = factor part, [1] = whole evaluation.
   void Eval(int cov_type, double var, double phi, const double* d_y, bool want_grad, double* sums, double* kernel_ms);
-  // D (n) and B's values (n x nn, 0 past a row's neighbours) of the last Eval (host)
-  void GetFactor(double* D, double* Bv) const;
+  // D (n) and B's values (n x nn, 0 past a row's neighbours) of the last evaluation (host); nullable: their
+  // derivatives with respect to log var and log phi of the last evaluation with the gradient
+  void GetFactor(double* D, double* Bv, double* dD0 = nullptr, double* dD1 = nullptr, double* dBv0 = nullptr,
+                 double* dBv1 = nullptr) const;
+  // The residual factor with its derivatives at (var, phi): the likelihood-independent part of an evaluation with
+  // the gradient (the GEMM chain that makes V and P_k, then the rows), then GetFactor
+  void Factor(int cov_type, double var, double phi, double* D, double* Bv, double* dD0, double* dD1, double* dBv0,
+              double* dBv1);
   // Predictions for the Gaussian likelihood (CalcPredVecchiaObservedFirstOrder, full_scale_vecchia branches,
   // Vecchia_utils.cpp:1686-1707, 1826-1840, 1872-1873, 1901-1980) at (var, phi) on the transformed scale,
   // nugget 1 included: Xp host row-major np x d prediction points (after the n observed points); nbr host
@@ -74,6 +159,7 @@ class VifSolver {
   // K_mm,s, red[1] = log det M; M_copy (nullable, ldm x ldm): M before its factorization
   void Prepare(int cov_type, double var, double phi, bool grad, double* red, double* M_copy = nullptr);
   void Rows(int cov_type, double var, double phi, bool grad);
+  VifGraph graph() const;
   // Prepare's results are in place for (kept_cov_, kept_var_, kept_phi_, kept_grad_) with their sums in red_: set
   // by Gram, used once by the next Eval, cleared by Prepare (every other entry overwrites the buffers through it)
   bool kept_ = false, kept_grad_ = false;

@@ -29,8 +29,8 @@ namespace {
 
 constexpr int kT = 256;
 constexpr int kCh = 32;      // m-rows per LDS staging chunk in the row kernel
-constexpr int kMaxNn = 64;        // neighbours per row without derivatives (prediction rows; LDS of the row kernel)
-constexpr int kMaxNnGrad = 48;    // with the two derivative blocks (the likelihood's rows)
+constexpr int kMaxNn = kVifMaxNn;          // neighbours per row without derivatives (prediction rows; LDS of the row kernel)
+constexpr int kMaxNnGrad = kVifMaxNnGrad;  // with the two derivative blocks (the likelihood's rows)
 constexpr int kNv = 16;      // n-vector scratch slots
 constexpr int kMv = 12;      // m-vector scratch slots
 
@@ -81,11 +81,14 @@ __device__ __forceinline__ int vif_row_slot(const int* ord, int chunk, int nitem
 // In-place Cholesky of the k x k matrix C (row stride ld, lower) by one wave, row-oriented (left-looking):
 // step j forms L_jj from row j's dot product, then every lane t > j forms L_tj = (C_tj - L_t . L_j) / L_jj
 // from its own row; the dot products read rows written in earlier steps only, so their LDS loads pipeline.
-__device__ __forceinline__ void wave_chol(double* C, int ld, int k, int lane) {
+// Returns (in every lane) whether a pivot was not > 0 or not finite.
+__device__ __forceinline__ bool wave_chol(double* C, int ld, int k, int lane) {
+  bool bad = false;
   for (int j = 0; j < k; ++j) {
     if (lane == j) {
       double sacc = C[j * ld + j];
       for (int q = 0; q < j; ++q) sacc -= C[j * ld + q] * C[j * ld + q];
+      bad = !(sacc > 0.) || !isfinite(sacc);
       C[j * ld + j] = sqrt(sacc);
     }
     wave_sync();
@@ -96,6 +99,7 @@ __device__ __forceinline__ void wave_chol(double* C, int ld, int k, int lane) {
     }
     wave_sync();
   }
+  return __any(bad) != 0;
 }
 
 // dK_mn / dlog(phi) (m x n, ld ldm)
@@ -271,7 +275,7 @@ __global__ void __launch_bounds__(kT) vif_rows_kernel(VifRowsArgs a) {
   // the pivot entries broadcast by lane shuffles; wave-scope ordering instead of workgroup barriers.
   if (tid >= 64) return;
   const int lane = tid;
-  wave_chol(C, k, k, lane);
+  const bool npd = wave_chol(C, k, k, lane);   // a pivot not > 0 or not finite: D_i = NaN (vif.h)
   // L L^T x = b for the lane-distributed right-hand sides x[0 .. NR)
   auto solve = [&](double* x, int nr) {
     for (int j = 0; j < k; ++j) {
@@ -337,7 +341,7 @@ __global__ void __launch_bounds__(kT) vif_rows_kernel(VifRowsArgs a) {
       }
     }
     if (p == 0) {
-      a.D[ir] = scal[0] - s0;
+      a.D[ir] = npd ? __builtin_nan("") : scal[0] - s0;
       if (GRAD) {
         a.dD0[ir] = scal[1] - s1;
         a.dD1[ir] = scal[2] - s2;
@@ -558,6 +562,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) vi
     if (lane < 32) C[lane * LD + c] = rw[c];
   if (lane < 32) rdg[lane] = yd;
   wave_sync();
+  // a pivot that is not > 0 or not finite leaves a y that is not finite (rsq of a negative number or NaN is NaN,
+  // rsq(0) = inf and rsq(inf) = 0 turn NaN in the Newton step's 0 * inf; the padding rows' pivots are 1): D_i = NaN (vif.h)
+  const bool npd = __any(!isfinite(yd)) != 0;
   // L L^T x = b for lane-distributed right-hand sides (lane p holds entry p; zero beyond k)
   auto solve = [&](double* x, int nr) {
 #pragma unroll
@@ -621,7 +628,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) vi
     }
   }
   if (lane == 0) {
-    a.D[ir] = d0 - s0;
+    a.D[ir] = npd ? __builtin_nan("") : d0 - s0;
     if (GRAD) {
       a.dD0[ir] = dd0 - s1;
       a.dD1[ir] = dd1 - s2;
@@ -806,14 +813,7 @@ __global__ void __launch_bounds__(kT) vif_sub_kernel(int n, const double* __rest
   if (i < n) out[i] = a[i] - b[i];
 }
 
-// Per-block partial sums of up to 8 elementwise terms; op 0: a (b) (c) (nullable factors), 1: log a,
-// 2: a (b) / c, 3: a b^2 / c^2, 4: a b / c^2
-struct VifTerms {
-  const double* a[8];
-  const double* b[8];
-  const double* c[8];
-  int op[8];
-};
+// Per-block partial sums of up to 8 elementwise terms (VifTerms, vif.h)
 
 __global__ void __launch_bounds__(kT) vif_sum_kernel(int n, int nt, VifTerms T, double* __restrict__ part) {
   __shared__ double red[kT / 64][8];
@@ -916,6 +916,168 @@ __global__ void __launch_bounds__(kT) vif_sum_parts_kernel(const double* __restr
 
 }  // namespace
 
+// ---------------------------------------------------------------- host launch code (vif.h)
+void vif_launch_rows(const VifRowsLaunch& L, hipStream_t s) {
+  const int rows = L.n_total - L.i0;
+  if (rows <= 0) return;
+  if (L.nn < 1 || L.nn > (L.grad ? kMaxNnGrad : kMaxNn))
+    Fatal("full-scale Vecchia rows: %d neighbours %s derivatives are not supported (1..%d)", L.nn,
+          L.grad ? "with" : "without", L.grad ? kMaxNnGrad : kMaxNn);
+  if (L.form < 0 || L.form > 2) Fatal("full-scale Vecchia rows: unknown form %d", L.form);
+  if (L.form == 1 && L.nn > kVifMaxNnMfma)
+    Fatal("full-scale Vecchia rows: the MFMA form takes at most %d neighbours, not %d", kVifMaxNnMfma, L.nn);
+  VifRowsArgs a{};
+  a.X = L.X;
+  a.nbr = L.nbr;
+  a.n = L.n_total; a.d = L.d; a.nn = L.nn; a.mi = L.m; a.ldm = L.ldm;
+  a.V = L.V; a.P0 = L.P0; a.P1 = L.P1;
+  a.var = L.var; a.phi = L.phi;
+  a.nugget = L.nugget;
+  a.cjit = L.cjit;
+  a.r1 = rows_r1(L.nn, L.grad);
+  a.i0 = L.i0;
+  a.Bv = L.Bv; a.D = L.D; a.dBv0 = L.dBv0; a.dBv1 = L.dBv1; a.dD0 = L.dD0; a.dD1 = L.dD1;
+  a.ord = L.ord;
+  a.chunk = (rows + 7) / 8;
+  const int grid = a.ord ? 8 * a.chunk : rows;
+  const size_t lds = rows_lds_bytes(L.nn, L.grad);
+  const bool mfma = L.form == 1 || (L.form == 0 && L.nn <= kVifMaxNnMfma);   // sets of <= 32 points: the MFMA Gram form
+  const bool grad = L.grad;
+  dispatch_cov_vif(L.cov_type, [&](auto c) {
+    constexpr int COV = decltype(c)::value;
+    if (mfma) {
+      if (grad) hipLaunchKernelGGL((vif_rows_mfma_kernel<COV, true>), dim3(grid), dim3(64), 0, s, a);
+      else hipLaunchKernelGGL((vif_rows_mfma_kernel<COV, false>), dim3(grid), dim3(64), 0, s, a);
+    } else if (grad) {
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vif_rows_kernel<COV, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((vif_rows_kernel<COV, true>), dim3(grid), dim3(kT), lds, s, a);
+    } else {
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vif_rows_kernel<COV, false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((vif_rows_kernel<COV, false>), dim3(grid), dim3(kT), lds, s, a);
+    }
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+std::vector<int> vif_morton_order(const double* hx, int n, int d) {
+  const int dd = std::min(d, 2);
+  double lo[2] = {0., 0.}, hi[2] = {0., 0.};
+  for (int q = 0; q < dd; ++q) {
+    lo[q] = hi[q] = hx[q];
+    for (int i = 0; i < n; ++i) {
+      lo[q] = std::min(lo[q], hx[(size_t)i * d + q]);
+      hi[q] = std::max(hi[q], hx[(size_t)i * d + q]);
+    }
+  }
+  std::vector<std::pair<uint64_t, int>> key(n);
+  for (int i = 0; i < n; ++i) {
+    uint64_t code = 0;
+    uint32_t c[2] = {0, 0};
+    for (int q = 0; q < dd; ++q) {
+      const double w = hi[q] > lo[q] ? (hx[(size_t)i * d + q] - lo[q]) / (hi[q] - lo[q]) : 0.;
+      c[q] = (uint32_t)std::min(65535., std::max(0., w * 65536.));
+    }
+    for (int bit = 15; bit >= 0; --bit)
+      for (int q = 0; q < dd; ++q) code = (code << 1) | ((c[q] >> bit) & 1u);
+    key[i] = {code, i};
+  }
+  std::sort(key.begin(), key.end());
+  std::vector<int> ord(n);
+  for (int i = 0; i < n; ++i) ord[i] = key[i].second;
+  return ord;
+}
+
+int vif_transpose_lists(int n, int nn, const int* nbr, std::vector<int>& tptr, std::vector<int>& trow,
+                        std::vector<int>& tslot) {
+  tptr.assign(n + 1, 0);
+  for (int i = 0; i < n; ++i)
+    for (int r = 0; r < std::min(i, nn); ++r) ++tptr[nbr[(size_t)i * nn + r] + 1];
+  for (int j = 0; j < n; ++j) tptr[j + 1] += tptr[j];
+  const int nnz = tptr[n];
+  trow.assign(std::max(nnz, 1), 0);
+  tslot.assign(std::max(nnz, 1), 0);
+  std::vector<int> fill(tptr.begin(), tptr.end() - 1);
+  for (int i = 0; i < n; ++i)
+    for (int r = 0; r < std::min(i, nn); ++r) {
+      const int j = nbr[(size_t)i * nn + r];
+      trow[fill[j]] = i;
+      tslot[fill[j]] = i * nn + r;
+      ++fill[j];
+    }
+  return nnz;
+}
+
+void vif_launch_brow(hipStream_t s, const VifGraph& g, const double* in, const double* coef, const double* D,
+                     double self, bool div, double* out, double* out_div) {
+  const int nb = (g.n + 3) / 4, chunk = (nb + 7) / 8;
+  hipLaunchKernelGGL(vif_brow_kernel, dim3(g.ord ? 8 * chunk : nb), dim3(kT), 0, s, in, g.nbr, coef, D, g.n, g.nn, g.m,
+                     g.ldm, self, div ? 1 : 0, out, out_div, g.ord, chunk);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_bcol(hipStream_t s, const VifGraph& g, const double* in, const double* coefT, double self, double* out) {
+  const int nb = (g.n + 3) / 4, chunk = (nb + 7) / 8;
+  hipLaunchKernelGGL(vif_bcol_kernel, dim3(g.ord ? 8 * chunk : nb), dim3(kT), 0, s, in, g.tptr, g.trow, coefT, g.n, g.m,
+                     g.ldm, self, out, g.ord, chunk);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_bvec(hipStream_t s, const VifGraph& g, const double* x, const double* coef, const double* D,
+                     double self, double* out) {
+  hipLaunchKernelGGL(vif_bvec_kernel, dim3((g.n + kT - 1) / kT), dim3(kT), 0, s, x, g.nbr, coef, D, g.n, g.nn, self, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_btvec(hipStream_t s, const VifGraph& g, const double* x, const double* coefT, double self, double* out) {
+  hipLaunchKernelGGL(vif_btvec_kernel, dim3((g.n + kT / 16 - 1) / (kT / 16)), dim3(kT), 0, s, x, g.tptr, g.trow, coefT,
+                     g.n, self, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_gather(hipStream_t s, int nnz, const int* tslot, const double* coef, double* coefT) {
+  if (nnz <= 0) return;
+  hipLaunchKernelGGL(vif_gather_kernel, dim3((nnz + kT - 1) / kT), dim3(kT), 0, s, nnz, tslot, coef, coefT);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_gemv(hipStream_t s, int n, int m, int ldm, const double* M, const double* x, double* part, double* out) {
+  const int nb = (n + 63) / 64;
+  hipLaunchKernelGGL(vif_gemv_part_kernel, dim3(nb), dim3(kT), 0, s, M, x, n, m, ldm, part);
+  hipLaunchKernelGGL(vif_gemv_reduce_kernel, dim3((m + 3) / 4), dim3(kT), 0, s, part, nb, m, ldm, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_coldot(hipStream_t s, int cols, int m, int ldm, const double* M, const double* w, const double* M2,
+                       double* out) {
+  hipLaunchKernelGGL(vif_coldot_kernel, dim3((cols + 3) / 4), dim3(kT), 0, s, M, w, M2, cols, m, ldm, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_zvec(hipStream_t s, int n, const double* dD, const double* u, const double* e, const double* D,
+                     double* z) {
+  hipLaunchKernelGGL(vif_zvec_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, s, n, dD, u, e, D, z);
+  HIP_CHECK(hipGetLastError());
+}
+
+void vif_launch_sum(hipStream_t s, int n, int nt, const VifTerms& T, double* part, double* out) {
+  const int nbs = std::min(512, (n + kT - 1) / kT);
+  hipLaunchKernelGGL(vif_sum_kernel, dim3(nbs), dim3(kT), 0, s, n, nt, T, part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nbs, nt, out, s);
+}
+
+void vif_launch_dkmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
+                     double var, double phi, double* dK) {
+  dispatch_cov_vif(cov_type, [&](auto c) {
+    constexpr int COV = decltype(c)::value;
+    hipLaunchKernelGGL((vif_dkmn_kernel<COV>), dim3((m + 63) / 64, (n + 3) / 4), dim3(kT), 0, s, X, Z, n, m, d, ldm, var,
+                       phi, dK);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 VifSolver::VifSolver(int n, int d, const double* d_X, const std::vector<double>& Z, const std::vector<int>& nbr, int nn,
                      hipStream_t stream)
     : n_(n), d_(d), nn_(nn), s_(stream), d_X_(d_X) {
@@ -940,19 +1102,8 @@ VifSolver::VifSolver(int n, int d, const double* d_X, const std::vector<double>&
   nbr_.alloc((size_t)n * nn);
   HIP_CHECK(hipMemcpyAsync(nbr_.get(), nbr.data(), sizeof(int) * nbr.size(), hipMemcpyHostToDevice, stream));
   // B^T lists: for every column j the rows i (ascending) that hold j among their neighbours, with the slot
-  std::vector<int> tptr(n + 1, 0);
-  for (int i = 0; i < n; ++i)
-    for (int r = 0; r < std::min(i, nn); ++r) ++tptr[nbr[(size_t)i * nn + r] + 1];
-  for (int j = 0; j < n; ++j) tptr[j + 1] += tptr[j];
-  const int nnz = tptr[n];
-  std::vector<int> trow(std::max(nnz, 1)), tslot(std::max(nnz, 1)), fill(tptr.begin(), tptr.end() - 1);
-  for (int i = 0; i < n; ++i)
-    for (int r = 0; r < std::min(i, nn); ++r) {
-      const int j = nbr[(size_t)i * nn + r];
-      trow[fill[j]] = i;
-      tslot[fill[j]] = i * nn + r;
-      ++fill[j];
-    }
+  std::vector<int> tptr, trow, tslot;
+  const int nnz = vif_transpose_lists(n, nn, nbr.data(), tptr, trow, tslot);
   nnz_ = nnz;
   for (DevBuf<double>* b : {&BvT_, &dBvT0_, &dBvT1_}) b->alloc(std::max(nnz, 1));
   tptr_.alloc(n + 1);
@@ -969,42 +1120,11 @@ VifSolver::VifSolver(int n, int d, const double* d_X, const std::vector<double>&
     std::vector<double> hx((size_t)n * d);
     HIP_CHECK(hipMemcpyAsync(hx.data(), d_X, sizeof(double) * hx.size(), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    const int dd = std::min(d, 2);
-    double lo[2] = {0., 0.}, hi[2] = {0., 0.};
-    for (int q = 0; q < dd; ++q) {
-      lo[q] = hi[q] = hx[q];
-      for (int i = 0; i < n; ++i) {
-        lo[q] = std::min(lo[q], hx[(size_t)i * d + q]);
-        hi[q] = std::max(hi[q], hx[(size_t)i * d + q]);
-      }
-    }
-    std::vector<std::pair<uint64_t, int>> key(n);
-    for (int i = 0; i < n; ++i) {
-      uint64_t code = 0;
-      uint32_t c[2] = {0, 0};
-      for (int q = 0; q < dd; ++q) {
-        const double w = hi[q] > lo[q] ? (hx[(size_t)i * d + q] - lo[q]) / (hi[q] - lo[q]) : 0.;
-        c[q] = (uint32_t)std::min(65535., std::max(0., w * 65536.));
-      }
-      for (int bit = 15; bit >= 0; --bit)
-        for (int q = 0; q < dd; ++q) code = (code << 1) | ((c[q] >> bit) & 1u);
-      key[i] = {code, i};
-    }
-    std::sort(key.begin(), key.end());
-    std::vector<int> ord(n);
-    for (int i = 0; i < n; ++i) ord[i] = key[i].second;
+    const std::vector<int> ord = vif_morton_order(hx.data(), n, d);
     ord_.alloc(n);
     HIP_CHECK(hipMemcpyAsync(ord_.get(), ord.data(), sizeof(int) * n, hipMemcpyHostToDevice, stream));
   }
   lds_bytes_ = rows_lds_bytes(nn, true);
-  for (int cov : {kMatern05, kMatern15, kMatern25, kGaussian})
-    dispatch_cov_vif(cov, [&](auto c) {
-      constexpr int COV = decltype(c)::value;
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vif_rows_kernel<COV, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds_bytes(nn, true)));
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vif_rows_kernel<COV, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds_bytes(nn, false)));
-    });
   for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
   HIP_CHECK(hipStreamSynchronize(stream));
 }
@@ -1014,71 +1134,49 @@ VifSolver::~VifSolver() {
   for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
 }
 
+VifGraph VifSolver::graph() const {
+  VifGraph g;
+  g.n = n_; g.nn = nn_; g.m = m_; g.ldm = ldm_;
+  g.nbr = nbr_.get(); g.tptr = tptr_.get(); g.trow = trow_.get();
+  g.ord = ord_.size() ? ord_.get() : nullptr;
+  return g;
+}
+
 void VifSolver::Rows(int cov_type, double var, double phi, bool grad) {
-  VifRowsArgs a{};
-  a.X = d_X_;
-  a.nbr = nbr_.get();
-  a.n = n_; a.d = d_; a.nn = nn_; a.mi = m_; a.ldm = ldm_;
-  a.V = F_->V_.get(); a.P0 = P0_.get(); a.P1 = P1_.get();
-  a.var = var; a.phi = phi;
-  a.nugget = latent_ ? 0. : 1.;
-  a.cjit = latent_ ? 1. + 1e-10 : 1.;   // JITTER_MULT_VECCHIA (utils.h:36; Vecchia_utils.cpp:1546-1548)
-  a.r1 = rows_r1(nn_, grad);
-  a.Bv = Bv_.get(); a.D = D_.get(); a.dBv0 = dBv0_.get(); a.dBv1 = dBv1_.get(); a.dD0 = dD0_.get(); a.dD1 = dD1_.get();
-  a.ord = ord_.size() ? ord_.get() : nullptr;
-  a.chunk = (n_ + 7) / 8;
-  const int grid = a.ord ? 8 * a.chunk : n_;
-  const size_t lds = rows_lds_bytes(nn_, grad);
+  VifRowsLaunch L;
+  L.X = d_X_;
+  L.nbr = nbr_.get();
+  L.n_total = n_; L.d = d_; L.nn = nn_; L.m = m_; L.ldm = ldm_; L.i0 = 0;
+  L.V = F_->V_.get(); L.P0 = P0_.get(); L.P1 = P1_.get();
+  L.cov_type = cov_type; L.var = var; L.phi = phi;
+  L.nugget = latent_ ? 0. : 1.;
+  L.cjit = latent_ ? 1. + 1e-10 : 1.;   // JITTER_MULT_VECCHIA (utils.h:36; Vecchia_utils.cpp:1546-1548)
+  L.grad = grad;
   const char* form = std::getenv("GPBOOST_AMD_VIF_ROWS");   // "lds": the LDS-staged VALU form (A/B)
-  const bool lds_form = form != nullptr && std::string(form) == "lds";
-  const bool mfma = nn_ <= 31 && !lds_form;   // neighbour sets of <= 32 points: the MFMA Gram form
-  dispatch_cov_vif(cov_type, [&](auto c) {
-    constexpr int COV = decltype(c)::value;
-    if (mfma) {
-      if (grad) hipLaunchKernelGGL((vif_rows_mfma_kernel<COV, true>), dim3(grid), dim3(64), 0, s_, a);
-      else hipLaunchKernelGGL((vif_rows_mfma_kernel<COV, false>), dim3(grid), dim3(64), 0, s_, a);
-    } else if (grad) {
-      hipLaunchKernelGGL((vif_rows_kernel<COV, true>), dim3(grid), dim3(kT), lds, s_, a);
-    } else {
-      hipLaunchKernelGGL((vif_rows_kernel<COV, false>), dim3(grid), dim3(kT), lds, s_, a);
-    }
-  });
-  HIP_CHECK(hipGetLastError());
+  L.form = form != nullptr && std::string(form) == "lds" ? 2 : 0;
+  L.ord = ord_.size() ? ord_.get() : nullptr;
+  L.Bv = Bv_.get(); L.D = D_.get(); L.dBv0 = dBv0_.get(); L.dBv1 = dBv1_.get(); L.dD0 = dD0_.get(); L.dD1 = dD1_.get();
+  vif_launch_rows(L, s_);
 }
 
 void VifSolver::BRow(const double* in, const double* coef, double self, bool div, double* out, double* out_div) {
-  const int* ord = ord_.size() ? ord_.get() : nullptr;
-  const int nb = (n_ + 3) / 4, chunk = (nb + 7) / 8;
-  hipLaunchKernelGGL(vif_brow_kernel, dim3(ord ? 8 * chunk : nb), dim3(kT), 0, s_, in, nbr_.get(), coef, D_.get(), n_,
-                     nn_, m_, ldm_, self, div ? 1 : 0, out, out_div, ord, chunk);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_brow(s_, graph(), in, coef, D_.get(), self, div, out, out_div);
 }
 
 void VifSolver::BCol(const double* in, const double* coefT, double self, double* out) {
-  const int* ord = ord_.size() ? ord_.get() : nullptr;
-  const int nb = (n_ + 3) / 4, chunk = (nb + 7) / 8;
-  hipLaunchKernelGGL(vif_bcol_kernel, dim3(ord ? 8 * chunk : nb), dim3(kT), 0, s_, in, tptr_.get(), trow_.get(),
-                     coefT, n_, m_, ldm_, self, out, ord, chunk);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_bcol(s_, graph(), in, coefT, self, out);
 }
 
 void VifSolver::BVec(const double* x, const double* coef, double self, double* out) {
-  hipLaunchKernelGGL(vif_bvec_kernel, dim3((n_ + kT - 1) / kT), dim3(kT), 0, s_, x, nbr_.get(), coef,
-                     static_cast<const double*>(nullptr), n_, nn_, self, out);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_bvec(s_, graph(), x, coef, nullptr, self, out);
 }
 
 void VifSolver::BtVec(const double* x, const double* coefT, double self, double* out) {
-  hipLaunchKernelGGL(vif_btvec_kernel, dim3((n_ + kT / 16 - 1) / (kT / 16)), dim3(kT), 0, s_, x, tptr_.get(),
-                     trow_.get(), coefT, n_, self, out);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_btvec(s_, graph(), x, coefT, self, out);
 }
 
 void VifSolver::Gemv(const double* M, const double* x, double* out) {
-  const int nb = (n_ + 63) / 64;
-  hipLaunchKernelGGL(vif_gemv_part_kernel, dim3(nb), dim3(kT), 0, s_, M, x, n_, m_, ldm_, part_.get());
-  hipLaunchKernelGGL(vif_gemv_reduce_kernel, dim3((m_ + 3) / 4), dim3(kT), 0, s_, part_.get(), nb, m_, ldm_, out);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_gemv(s_, n_, m_, ldm_, M, x, part_.get(), out);
 }
 
 void VifSolver::PredBpo(int np, int mp, const int* dnb, const double* Bvp, const double* r, const double* M, double* mo,
@@ -1088,13 +1186,11 @@ void VifSolver::PredBpo(int np, int mp, const int* dnb, const double* Bvp, const
 }
 
 void VifSolver::ColDotN(const double* M, const double* w, const double* M2, int cols, double* out) {
-  hipLaunchKernelGGL(vif_coldot_kernel, dim3((cols + 3) / 4), dim3(kT), 0, s_, M, w, M2, cols, m_, ldm_, out);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_coldot(s_, cols, m_, ldm_, M, w, M2, out);
 }
 
 void VifSolver::ColDot(const double* M, const double* w, const double* M2, double* out) {
-  hipLaunchKernelGGL(vif_coldot_kernel, dim3((n_ + 3) / 4), dim3(kT), 0, s_, M, w, M2, n_, m_, ldm_, out);
-  HIP_CHECK(hipGetLastError());
+  vif_launch_coldot(s_, n_, m_, ldm_, M, w, M2, out);
 }
 
 void VifSolver::Prepare(int cov_type, double var, double phi, bool want_grad, double* red, double* M_copy) {
@@ -1106,12 +1202,7 @@ void VifSolver::Prepare(int cov_type, double var, double phi, bool want_grad, do
   // log det K_mm,s
   F.Prior(cov_type, var, phi, red);
   if (want_grad) {
-    dispatch_cov_vif(cov_type, [&](auto c) {
-      constexpr int COV = decltype(c)::value;
-      hipLaunchKernelGGL((vif_dkmn_kernel<COV>), dim3((m + 63) / 64, (n + 3) / 4), dim3(kT), 0, s_, d_X_, F.dZ_.get(),
-                         n, m, d_, ldm, var, phi, dK_.get());
-    });
-    HIP_CHECK(hipGetLastError());
+    vif_launch_dkmn(s_, cov_type, d_X_, F.dZ_.get(), n, m, d_, ldm, var, phi, dK_.get());
     // A = L^-T V; P_0 = L^-1 (K_mn - 1/2 K_mm A), P_1 = L^-1 (dK_mn - 1/2 dK_mm A) (Kd_ as the staging)
     gemm_f64(s_, m, n, m, 1., F.Li_.get(), ldm, 1, F.V_.get(), ldm, 0, 0., F.A_.get(), ldm, 0, 0, 1, 0);
     HIP_CHECK(hipMemcpyAsync(F.Kd_.get(), F.Kmn_.get(), sizeof(double) * mn, hipMemcpyDeviceToDevice, s_));
@@ -1123,14 +1214,10 @@ void VifSolver::Prepare(int cov_type, double var, double phi, bool want_grad, do
   }
   // residual Vecchia factor (CalcCovFactorGradientVecchia), its values also in column order for B^T
   Rows(cov_type, var, phi, want_grad);
-  if (nnz_ > 0) {
-    const int nbt = (nnz_ + kT - 1) / kT;
-    hipLaunchKernelGGL(vif_gather_kernel, dim3(nbt), dim3(kT), 0, s_, nnz_, tslot_.get(), Bv_.get(), BvT_.get());
-    if (want_grad) {
-      hipLaunchKernelGGL(vif_gather_kernel, dim3(nbt), dim3(kT), 0, s_, nnz_, tslot_.get(), dBv0_.get(), dBvT0_.get());
-      hipLaunchKernelGGL(vif_gather_kernel, dim3(nbt), dim3(kT), 0, s_, nnz_, tslot_.get(), dBv1_.get(), dBvT1_.get());
-    }
-    HIP_CHECK(hipGetLastError());
+  vif_launch_gather(s_, nnz_, tslot_.get(), Bv_.get(), BvT_.get());
+  if (want_grad) {
+    vif_launch_gather(s_, nnz_, tslot_.get(), dBv0_.get(), dBvT0_.get());
+    vif_launch_gather(s_, nnz_, tslot_.get(), dBv1_.get(), dBvT1_.get());
   }
   // Woodbury matrix M = K_mm,s + BK^T D^-1 BK (CalcCovFactorFITC_FSA): BK_ = B K, Kd_ = D^-1 B K
   BRow(F.Kmn_.get(), Bv_.get(), 1., false, BK_.get(), F.Kd_.get());
@@ -1170,24 +1257,20 @@ void VifSolver::Eval(int cov_type, double var, double phi, const double* d_y, bo
   double* mt = mv;                    // K^T R^-1 y
   double* ms = mv + ldm;              // w = M^-1 K^T R^-1 y
   double* mtmp = mv + 2 * (size_t)ldm;
-  hipLaunchKernelGGL(vif_bvec_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, s_, d_y, nbr_.get(), Bv_.get(), D_.get(), n,
-                     nn_, 1., u);
+  vif_launch_bvec(s_, graph(), d_y, Bv_.get(), D_.get(), 1., u);
   BtVec(u, BvT_.get(), 1., ry);
   Gemv(F.Kmn_.get(), ry, mt);
   fitc_chol_solve(s_, F.Wi_.get(), F.WiT_.get(), mt, m, ldm, mtmp, ms);
   ColDot(F.Kmn_.get(), ms, nullptr, kw);
-  hipLaunchKernelGGL(vif_bvec_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, s_, kw, nbr_.get(), Bv_.get(), D_.get(), n,
-                     nn_, 1., t1);
+  vif_launch_bvec(s_, graph(), kw, Bv_.get(), D_.get(), 1., t1);
   BtVec(t1, BvT_.get(), 1., rk);
   hipLaunchKernelGGL(vif_sub_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, s_, n, ry, rk, yaux);
   HIP_CHECK(hipGetLastError());
-  const int nbs = std::min(512, (n + kT - 1) / kT);
   {
     VifTerms T{};
     T.a[0] = D_.get(); T.op[0] = 1;                      // sum log D
     T.a[1] = d_y; T.b[1] = yaux; T.op[1] = 0;            // y^T y_aux
-    hipLaunchKernelGGL(vif_sum_kernel, dim3(nbs), dim3(kT), 0, s_, n, 2, T, part_.get());
-    launch_sum_blocks(part_.get(), nbs, 2, red + 2, s_);
+    vif_launch_sum(s_, n, 2, T, part_.get(), red + 2);
   }
   double* mv_a = mv + 3 * (size_t)ldm;    // a = K_mm,s^-1 K^T y_aux
   double* mv_g[2] = {mv + 4 * (size_t)ldm, mv + 5 * (size_t)ldm};   // dK_k^T y_aux
@@ -1224,7 +1307,7 @@ void VifSolver::Eval(int cov_type, double var, double phi, const double* d_y, bo
       double* cf = v + 14 * (size_t)n;
       // vecchia_grad_y = dB^T u - B^T D^-1 (dD o u) + B^T D^-1 dB y (:2084-2085)
       BVec(d_y, dBv, 0., dby);
-      hipLaunchKernelGGL(vif_zvec_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, s_, n, dD, u, dby, D_.get(), zp);
+      vif_launch_zvec(s_, n, dD, u, dby, D_.get(), zp);
       BtVec(zp, BvT_.get(), 1., btz);
       BtVec(u, p == 0 ? dBvT0_.get() : dBvT1_.get(), 0., vgy);
       hipLaunchKernelGGL(vif_add_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, s_, n, vgy, btz, vgy);
@@ -1242,8 +1325,7 @@ void VifSolver::Eval(int cov_type, double var, double phi, const double* d_y, bo
       T.a[4] = cxw; T.op[4] = 0;                                     // tr(M^-1 E)
       T.a[5] = cf; T.c[5] = D_.get(); T.op[5] = 2;                  // tr(M^-1 F)
       T.a[6] = dD; T.b[6] = cg; T.c[6] = D_.get(); T.op[6] = 4;     // tr(M^-1 G)
-      hipLaunchKernelGGL(vif_sum_kernel, dim3(nbs), dim3(kT), 0, s_, n, 7, T, part_.get());
-      launch_sum_blocks(part_.get(), nbs, 7, red + 20 + 8 * p, s_);
+      vif_launch_sum(s_, n, 7, T, part_.get(), red + 20 + 8 * p);
     }
   }
   HIP_CHECK(hipMemcpyAsync(h_red_, red, sizeof(double) * 36, hipMemcpyDeviceToHost, s_));
@@ -1320,10 +1402,24 @@ void VifSolver::Gram(int cov_type, double var, double phi, bool grad, const doub
   kept_phi_ = phi;
 }
 
-void VifSolver::GetFactor(double* D, double* Bv) const {
-  HIP_CHECK(hipMemcpyAsync(D, D_.get(), sizeof(double) * n_, hipMemcpyDeviceToHost, s_));
-  HIP_CHECK(hipMemcpyAsync(Bv, Bv_.get(), sizeof(double) * n_ * nn_, hipMemcpyDeviceToHost, s_));
+void VifSolver::GetFactor(double* D, double* Bv, double* dD0, double* dD1, double* dBv0, double* dBv1) const {
+  auto get = [&](double* dst, const DevBuf<double>& src, size_t len) {
+    if (dst) HIP_CHECK(hipMemcpyAsync(dst, src.get(), sizeof(double) * len, hipMemcpyDeviceToHost, s_));
+  };
+  const size_t nb = (size_t)n_ * nn_;
+  get(D, D_, n_);
+  get(Bv, Bv_, nb);
+  get(dD0, dD0_, n_);
+  get(dD1, dD1_, n_);
+  get(dBv0, dBv0_, nb);
+  get(dBv1, dBv1_, nb);
   HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+void VifSolver::Factor(int cov_type, double var, double phi, double* D, double* Bv, double* dD0, double* dD1,
+                       double* dBv0, double* dBv1) {
+  Prepare(cov_type, var, phi, true, red_.get());
+  GetFactor(D, Bv, dD0, dD1, dBv0, dBv1);
 }
 
 // The prediction points' residual Vecchia rows (Vecchia_utils.cpp:1807-1896, no derivatives): KP = K_mp (m x np),
@@ -1351,29 +1447,17 @@ void VifSolver::PredRows(int cov_type, double var, double phi, const double* Xp,
   HIP_CHECK(hipMemcpyAsync(Va.get(), F.V_.get(), sizeof(double) * (size_t)ldm * n, hipMemcpyDeviceToDevice, s_));
   HIP_CHECK(hipMemsetAsync(Va.get() + (size_t)ldm * n, 0, sizeof(double) * (size_t)ldm * np, s_));
   gemm_f64(s_, m, np, m, 1., F.Li_.get(), ldm, 0, KP.get(), ldm, 0, 0., Va.get() + (size_t)ldm * n, ldm, 0, 1, 0, 0);
-  VifRowsArgs a{};
-  a.X = Xa.get();
-  a.nbr = dnb.get();
-  a.n = na; a.d = d; a.nn = mp; a.mi = m; a.ldm = ldm;
-  a.V = Va.get(); a.P0 = nullptr; a.P1 = nullptr;
-  a.var = var; a.phi = phi;
-  a.nugget = latent_ ? 0. : 1.;
-  a.cjit = latent_ ? 1. + 1e-10 : 1.;
-  a.r1 = rows_r1(mp, false);
-  a.i0 = n;
-  a.Bv = Bvp.get(); a.D = Dp.get();
-  const size_t lds = rows_lds_bytes(mp, false);
-  dispatch_cov_vif(cov_type, [&](auto c) {
-    constexpr int COV = decltype(c)::value;
-    if (mp <= 31) {
-      hipLaunchKernelGGL((vif_rows_mfma_kernel<COV, false>), dim3(np), dim3(64), 0, s_, a);
-    } else {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vif_rows_kernel<COV, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((vif_rows_kernel<COV, false>), dim3(np), dim3(kT), lds, s_, a);
-    }
-  });
-  HIP_CHECK(hipGetLastError());
+  VifRowsLaunch L;
+  L.X = Xa.get();
+  L.nbr = dnb.get();
+  L.n_total = na; L.d = d; L.nn = mp; L.m = m; L.ldm = ldm; L.i0 = n;
+  L.V = Va.get();
+  L.cov_type = cov_type; L.var = var; L.phi = phi;
+  L.nugget = latent_ ? 0. : 1.;
+  L.cjit = latent_ ? 1. + 1e-10 : 1.;
+  L.grad = false;
+  L.Bv = Bvp.get(); L.D = Dp.get();
+  vif_launch_rows(L, s_);
 }
 
 void VifSolver::Predict(int cov_type, double var, double phi, const double* d_y, const double* Xp, int np,

@@ -539,6 +539,57 @@ GPBOOST_AMD_EXPORT int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, d
                                             int pmax_block, const double* RHS, double* U, int64_t block_len,
                                             int* its, int* flags);
 
+/* The full-scale Vecchia ("VIF") row factor, sparse products and vector kernels on host arrays, launched by the
+ * host launch functions VifSolver uses (csrc/vif.h). No reference counterpart (tests). Everything is checked on
+ * the host before any device call, a violation being an error return. Matrices that the device holds as m x n
+ * with leading dimension ldm = round_up(m, 64) are host arrays n x m row-major (point i's m entries contiguous);
+ * the hook fills the ldm - m padding entries of every input column with pad_fill. Outputs and scratch start as
+ * NaN between 64 guard doubles on either side; guard_flag = 1 when a guard word changed.
+ *
+ * GPB_TestVifRows: the residual rows i0 .. n_total - 1 of the points X (n_total x d, x_len = n_total d, d in
+ * 1..3, finite). nbr: (n_total - i0) x nn, the row of point i holding min(i, nn) distinct indices in [0, i) and
+ * -1 after them (nbr_len). V, P0, P1: n_total x m (mat_len = n_total m; P0 and P1 given exactly when grad = 1).
+ * nn in 1..48 with grad, 1..64 without; m in 1..4096; cov_type 0..3 (CovType of csrc/cov.h); var, phi > 0;
+ * nugget >= 0; cjit > 0. form 0: the production dispatch, 1: the MFMA form (refused for nn > 31), 2: the
+ * LDS-staged form; order 1: the rows in Morton order, XCD-chunked, as VifSolver processes them (with more than
+ * one row), 0: in index order. Outputs (rows_len = n_total - i0): D, Bv (rows x nn) and with grad dD0, dD1,
+ * dBv0, dBv1 (NULL otherwise). */
+GPBOOST_AMD_EXPORT int GPB_TestVifRows(int n_total, int d, int i0, int nn, int m, const double* X, int64_t x_len,
+                                       const int32_t* nbr, int64_t nbr_len, const double* V, const double* P0,
+                                       const double* P1, int64_t mat_len, int cov_type, double var, double phi,
+                                       double nugget, double cjit, int grad, int form, int order, double pad_fill,
+                                       double* D, double* Bv, double* dD0, double* dD1, double* dBv0, double* dBv1,
+                                       int64_t rows_len, int* guard_flag);
+/* One sparse product on the graph nbr (n x nn, nbr_len = n nn, row i holding min(i, nn) distinct indices < i)
+ * with the coefficients coef (n x nn, coef_len). op 0 (BRow): out[i] = self in[i] + sum_r coef[i][r] in[nbr[i][r]]
+ * over m-vectors (in: n x m, in_len = n m), div = 1: times 1 / D_i; want_div = 1: out2 = the same times 1 / D_i.
+ * op 1 (BCol): out[j] = self in[j] + sum over the rows i that hold j of coef(i, j) in[i], the coefficients
+ * gathered into column order on the device. op 2 (BVec): out_i = (self x_i + sum_r coef[i][r] x[nbr[i][r]])
+ * (/ D_i with D), in: n entries. op 3 (BtVec): the transposed vector product. D: n entries or NULL. X (nullable,
+ * n x d) with order = 1: the columns in Morton order as VifSolver processes them. out / out2: n x ldm for ops 0
+ * and 1 (the padding entries are returned as they are left), n for ops 2 and 3 (out_len). n < 2^22, m in 1..4096. */
+GPBOOST_AMD_EXPORT int GPB_TestVifApply(int op, int n, int nn, int m, const int32_t* nbr, int64_t nbr_len,
+                                        const double* coef, int64_t coef_len, const double* D, const double* in,
+                                        int64_t in_len, double self, int div, int want_div, const double* X, int d,
+                                        int order, double pad_fill, double* out, double* out2, int64_t out_len,
+                                        int* guard_flag);
+/* The small kernels (ops: VifVecOp in csrc/vif_test.h): 0 gemv (arrays M n x m, x n; out m), 1 column dots with
+ * a vector (M, w m; out n), 2 column dots of two matrices (M, M2; out n), 3 z = (e - dD u) / D (dD, u, e, D; out
+ * n), 4 sums of nt in 1..8 terms (arrays a_t, b_t, c_t for each term, b / c nullable; sum_ops[t] in 0..4: a b c,
+ * log a, a b / c, a b^2 / c^2, a b / c^2; out nt), 5 dK_mn / dlog phi (X n x d, Z m x d; out n x ldm, padding as
+ * left). lens[k]: the entries of arrays[k] (0 for NULL). */
+GPBOOST_AMD_EXPORT int GPB_TestVifVector(int op, int n, int m, int d, int cov_type, double var, double phi,
+                                         double pad_fill, const double* const* arrays, const int64_t* lens,
+                                         int n_arrays, const int32_t* sum_ops, int nt, double* out, int64_t out_len,
+                                         int* guard_flag);
+/* The residual factor of a gp_approx = "full_scale_vecchia" model at cov_pars (original scale) in the model
+ * order: perm (n, nullable: perm[i] = original index of the i-th point), neighbors (n x num_neighbors, nullable),
+ * D (n), B_vals (n x num_neighbors, B(i, nbr) = -A_i, 0-padded) and their derivatives with respect to log var and
+ * log phi on the transformed scale (dD: 2 x n, dB_vals: 2 x n x num_neighbors). Runs the GEMM chain of an
+ * evaluation with the gradient (V, P_k), then the rows. */
+GPBOOST_AMD_EXPORT int GPB_GetVifFactor(REModelHandle handle, const double* cov_pars, int32_t* perm,
+                                        int32_t* neighbors, double* D, double* B_vals, double* dD, double* dB_vals);
+
 /* ---------------------------------------------------------------- prediction */
 
 /* replaces GPB_SetPredictionData (include/LightGBM/c_api.h:1578; c_api.cpp). Only the settings
