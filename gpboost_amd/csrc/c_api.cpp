@@ -19,6 +19,7 @@
 #include "latent_test.h"
 #include "re_model.h"
 #include "sparse_chol.h"
+#include "lik_test.h"
 #include "vif_test.h"
 
 using gpb_amd::GroupedModel;
@@ -949,6 +950,25 @@ int GPB_TestVifVector(int op, int n, int m, int d, int cov_type, double var, dou
   API_BEGIN();
   gpb_amd::test_vif_vector(op, n, m, d, cov_type, var, phi, pad_fill, arrays, lens, n_arrays, sum_ops, nt, out, out_len,
                            guard_flag);
+  API_END();
+}
+
+int GPB_TestLikPoint(int lik, double aux, int n, const double* y, const double* loc, double* loglik, double* d1,
+                     double* info, double* dinfo, double* dinfo_lowrank, int* guard_flag) {
+  API_BEGIN();
+  gpb_amd::test_lik_point(lik, aux, n, y, loc, loglik, d1, info, dinfo, dinfo_lowrank, guard_flag);
+  API_END();
+}
+
+int GPB_TestLikPath(int path, int kernel, int n, int lik, double aux, const double* y, const double* mode,
+                    const double* offset, const double* const* vecs, int n_vecs, const int32_t* idx, int64_t idx_len,
+                    const double* arr0, const double* arr1, int64_t arr_len, const double* mats, int64_t mats_len,
+                    double lam, const int32_t* opts, int n_opts, double* const* outs, int n_outs, double* scalars,
+                    int n_scalars, int* guard_flag) {
+  API_BEGIN();
+  const gpb_amd::LikPathTest t{path, kernel, n,       lik,  aux,      y,   mode, offset, vecs,   n_vecs, idx,     idx_len,
+                               arr0, arr1,   arr_len, mats, mats_len, lam, opts, n_opts, outs,   n_outs, scalars, n_scalars};
+  gpb_amd::test_lik_path(t, guard_flag);
   API_END();
 }
 

@@ -16,6 +16,7 @@
 #include "dense_laplace.h"
 #include "kernels.h"
 #include "lik_device.h"
+#include "lik_test.h"
 
 namespace gpb_amd {
 namespace {
@@ -624,6 +625,31 @@ void DenseLaplace::Predict(int cov_type, double var, double phi, const double* X
     if (InfoFailed()) Fatal("I + W^1/2 Sigma W^1/2 is not positive definite (Cholesky failed)");
   }
   HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+// ---- test launchers (lik_test.h): the launches of FindMode / Eval on their production grids and the block sums
+int test_dl_blocks(int n) { return nb_red(n); }
+
+void test_dl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, double* d1,
+                  double* w, double* ws, double* rhs, hipStream_t s) {
+  hipLaunchKernelGGL(dl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s, n, lik, aux, y, off, mode, d1, w, ws, rhs);
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_dl_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
+                   const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
+                   double* sums, hipStream_t s) {
+  const int nbr = nb_red(n);
+  hipLaunchKernelGGL(dl_trial_kernel, dim3(nbr), dim3(kT), 0, s, n, lik, aux, lam, mode, a, mupd, aupd, y, off, mnew, anew,
+                     part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nbr, 2, sums, s);
+}
+
+void test_dl_dmll(const double* C, const double* S, int n, int ld, int lik, double aux, const double* y, const double* off,
+                  const double* mode, double* dmll, double* dg, hipStream_t s) {
+  hipLaunchKernelGGL(dl_dmll_kernel, dim3((n + 3) / 4), dim3(kT), 0, s, C, S, n, ld, lik, aux, y, off, mode, dmll, dg);
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpb_amd

@@ -21,6 +21,7 @@
 #include "fitc_laplace.h"
 #include "kernels.h"
 #include "lik_device.h"
+#include "lik_test.h"
 
 namespace gpb_amd {
 namespace {
@@ -915,6 +916,34 @@ void FitcLaplace::Predict(int cov_type, double var, double phi, const double* Xp
       g0 = g1;
     }
   }
+}
+
+// ---- test launchers (lik_test.h): the launches of FindMode on nb_thread(n) / nb_red(n) blocks and their block sums
+int test_fl_blocks(int n) { return nb_red(n); }
+
+void test_fl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* dvec,
+                  int w_update, double* d1, double* w, double* wdw, double* DW, double* rhs, hipStream_t s) {
+  hipLaunchKernelGGL(fl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s, n, lik, aux, y, off, mode, dvec, w_update, d1, w,
+                     wdw, DW, rhs);
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_fl_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
+                   const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
+                   double* sums, hipStream_t s) {
+  const int nbr = nb_red(n);
+  hipLaunchKernelGGL(fl_trial_kernel, dim3(nbr), dim3(kT), 0, s, n, lik, aux, lam, mode, a, mupd, aupd, y, off, mnew, anew,
+                     part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nbr, 2, sums, s);
+}
+
+void test_fl_final(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* dvec,
+                   double* d1, double* w, double* DW, double* dpwi, double* part, double* sums, hipStream_t s) {
+  const int nbr = nb_red(n);
+  hipLaunchKernelGGL(fl_final_kernel, dim3(nbr), dim3(kT), 0, s, n, lik, aux, y, off, mode, dvec, d1, w, DW, dpwi, part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nbr, 3, sums, s);
 }
 
 }  // namespace gpb_amd

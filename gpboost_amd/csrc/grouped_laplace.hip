@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "lik_device.h"
+#include "lik_test.h"
 #include "slq_host.h"
 #include "wave_ops.h"
 
@@ -230,6 +231,8 @@ __global__ void __launch_bounds__(256) glp_grad_f_kernel(int n, int K, const int
 }
 
 inline int blocks_of(int count) { return (count + 255) / 256; }
+// blocks of an observation pass (nb_)
+inline int obs_blocks(int n) { return std::max(1, std::min(blocks_of(n), kMaxBlocks)); }
 
 }  // namespace
 
@@ -240,7 +243,7 @@ GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>
     Fatal("non-Gaussian likelihoods with grouped random effects: at most %d grouping variables are supported by "
           "gpboost_amd", kGlpMaxK);
   const std::vector<int>& cum = *v_.cum;
-  nb_ = std::max(1, std::min(blocks_of(n), kMaxBlocks));
+  nb_ = obs_blocks(n);
   std::vector<int> glev((size_t)K * n);
   for (int k = 0; k < K; ++k)
     for (int i = 0; i < n; ++i) glev[(size_t)k * n + i] = cum[k] + levels[k][i];
@@ -660,6 +663,18 @@ void GroupedLaplace::GetZtWZ(double* diag, double* vals) {
   if (v_.nnz > 0)
     HIP_CHECK(hipMemcpyAsync(vals, d_ztwz_.get() + v_.M, sizeof(double) * v_.nnz, hipMemcpyDeviceToHost, s_));
   HIP_CHECK(hipStreamSynchronize(s_));
+}
+
+// ---- test launchers (lik_test.h): the launches of Objective / Deriv on nb_ blocks, then the finish of Objective
+int test_glp_blocks(int n) { return obs_blocks(n); }
+
+void test_glp_obs(int n, int K, const int* glev, const double* y, const double* F, const double* b, int lik, double aux,
+                  bool deriv, double* d1, double* W, double* dW, double* partial, double* ll, hipStream_t s) {
+  const int nb = obs_blocks(n);
+  if (deriv) glp_obs_kernel<true><<<nb, 256, 0, s>>>(n, K, glev, y, F, b, lik, aux, d1, W, dW, partial);
+  else glp_obs_kernel<false><<<nb, 256, 0, s>>>(n, K, glev, y, F, b, lik, aux, nullptr, nullptr, nullptr, partial);
+  glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial, ll);
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpb_amd

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "latent_kernels.h"
+#include "lik_device.h"
 
 namespace gpb_amd {
 namespace {
@@ -71,12 +72,6 @@ __global__ void __launch_bounds__(256) pred_samples_kernel(int n_pred, int mp, i
     if (b != 0.) s = fma(b, Z[(size_t)nbr[(size_t)p * mp + r] * t + c], s);
   }
   V[(size_t)p + (size_t)(col0 + c) * ldv] = s;
-}
-
-__device__ __forceinline__ double sigmoid_stable(double x) {   // DF_utils.h:37-46
-  if (x >= 0.) return 1. / (1. + exp(-x));
-  const double t = exp(x);
-  return t / (1. + t);
 }
 
 // Response mean of bernoulli_logit at latent N(mean, var) by the reference's adaptive

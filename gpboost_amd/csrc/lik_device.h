@@ -4,7 +4,10 @@
 //   bernoulli_logit likelihoods.h :8724, 9226, 9896, 10187; sigmoid_stable / softplus DF_utils.h:37-60
 //   bernoulli_probit :8708, 9208, 9871, 10171;  poisson :8730, 9230, 9904, 10200
 //   gamma           :8740, 9234, 9908, 10228 (aux = shape; log link, the normalizing constant on the host)
-// Shared by the Vecchia (sparse_kernels.hip) and FITC (fitc_laplace.hip) Laplace paths.
+// Shared by every Laplace path: sparse Vecchia (sparse_kernels.hip, lowrank_precond.hip), sparse Cholesky
+// (sparse_chol.hip), FITC (fitc_laplace.hip), full-scale Vecchia (vif_laplace.hip), dense (dense_laplace.hip) and
+// grouped (grouped_laplace.hip), and by the logit response mean of latent_pred.hip. Tested point by point through
+// GPB_TestLikPoint / GPB_TestLikPath (lik_test.cpp) against the bounds of tests/lik_cases.py.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,12 +28,17 @@ __device__ __forceinline__ double softplus(double x) { return log1p(exp(-fabs(x)
 
 // DF_utils.h:62-104: normal log-CDF with its tails, inverse Mills ratios phi / Phi and phi / (1 - Phi)
 __device__ __forceinline__ double normal_log_pdf(double x) { return -x * x / 2. - 0.91893853320467274178; }
+// Left tail: erfc up to u = -x = kProbitSeriesFrom, where erfc(u / sqrt 2) ~ 6e-300 is still a normal number (it is
+// a denormal with a few bits left from u ~ 37.6 on, and whether a libm returns, flushes or zeroes those differs);
+// past it the asymptotic series Phi(-u) = phi(u) / u (1 - 1/u^2 + 3/u^4 - ... + 10395/u^12), whose first dropped
+// term 135135 / u^14 is below 2e-17 there. The threshold is a constant, so host and device take the same branch.
+constexpr double kProbitSeriesFrom = 37.;
 __device__ __forceinline__ double normal_log_cdf(double x) {
   if (x < 0.) {
-    const double e = erfc(-x * 0.70710678118654752440);
-    if (e > 0.) return -0.69314718055994530942 + log(e);
-    const double u = -x, u2 = u * u;   // extreme left tail: asymptotic series
-    const double series = 1. - 1. / u2 + 3. / (u2 * u2);
+    const double u = -x;
+    if (u <= kProbitSeriesFrom) return -0.69314718055994530942 + log(erfc(u * 0.70710678118654752440));
+    const double u2 = u * u, v = 1. / u2;
+    const double series = 1. + v * (-1. + v * (3. + v * (-15. + v * (105. + v * (-945. + v * 10395.)))));
     return -0.5 * u2 - log(u) - 0.5 * log(2. * 3.14159265358979323846) + log(series);
   }
   const double Q = 0.5 * erfc(x * 0.70710678118654752440);
@@ -49,6 +57,9 @@ __device__ __forceinline__ double lik_loglik(int lik, double aux, double y, doub
   if (lik == kLikBernoulliProbit) return y == 0. ? normal_log_cdf(-l) : normal_log_cdf(l);   // :8708-8715
   if (lik == kLikPoisson) return y * l - exp(l);                                              // :8730-8737
   if (lik == kLikGamma) return -aux * (l + y * exp(-l));                                      // :8740-8748
+  // bernoulli_logit: y l - softplus(l) cancels for y = 1, l >> 0; log p and log (1 - p) directly do not
+  if (y == 1.) return -softplus(-l);
+  if (y == 0.) return -softplus(l);
   return y * l - softplus(l);
 }
 __device__ __forceinline__ double lik_d1(int lik, double aux, double y, double l) {
@@ -56,6 +67,7 @@ __device__ __forceinline__ double lik_d1(int lik, double aux, double y, double l
   if (lik == kLikBernoulliProbit) return y == 0. ? -mills_one_minus_phi(l) : mills_phi(l);    // :9208-9215
   if (lik == kLikPoisson) return y - exp(l);                                                  // :9230-9232
   if (lik == kLikGamma) return aux * (y * exp(-l) - 1.);                                      // :9234-9236
+  if (y == 1.) return sigmoid_stable(-l);   // 1 - p without the cancellation at l >> 0
   return y - sigmoid_stable(l);
 }
 // information (negative second derivative), likelihoods.h:9871-9906
@@ -71,8 +83,9 @@ __device__ __forceinline__ double lik_info(int lik, double aux, double y, double
   }
   if (lik == kLikPoisson) return exp(l);
   if (lik == kLikGamma) return aux * y * exp(-l);   // :9908-9910
-  const double p = sigmoid_stable(l);
-  return p * (1. - p);
+  // p q with q = 1 - p = sigmoid(-l) computed on its own: p (1. - p) loses q's digits for l >> 0 (it is 0 from
+  // l = 37 on) and is not even in l
+  return sigmoid_stable(l) * sigmoid_stable(-l);
 }
 // derivative of the information wrt the location parameter, likelihoods.h:10165-10195
 __device__ __forceinline__ double lik_dinfo(int lik, double aux, double y, double l) {
@@ -88,8 +101,8 @@ __device__ __forceinline__ double lik_dinfo(int lik, double aux, double y, doubl
     return -r * (x2 - 1. + r * (3. * l + 2. * r));
   }
   if (lik == kLikPoisson) return exp(l);
-  const double p = sigmoid_stable(l);
-  return -p * (1. - p) * (2. * p - 1.);
+  const double p = sigmoid_stable(l), q = sigmoid_stable(-l);
+  return -p * q * (p - q);
 }
 
 }  // namespace gpb_amd

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "latent_kernels.h"
 #include "lik_device.h"
+#include "lik_test.h"
 #include "vif_laplace.h"
 
 namespace gpb_amd {
@@ -1041,6 +1042,26 @@ void VifLaplace::Predict(int cov_type, double var, double phi, const double* Xp,
       for (int p = 0; p < np; ++p) pcov[(size_t)p * np + p] += hD[p];
     }
   }
+}
+
+// ---- test launchers (lik_test.h): the launches of NewtonStep / Trial on nblk(n) blocks and their block sums
+int test_vl_blocks(int n) { return nblk(n); }
+
+void test_vl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, double* d1,
+                  double* W, double* dW, double* rhs, double* part, double* sum, hipStream_t s) {
+  const int nb = nblk(n);
+  hipLaunchKernelGGL(vl_prep_kernel, dim3(nb), dim3(kT), 0, s, n, lik, aux, y, off, mode, d1, W, dW, rhs, part);
+  HIP_CHECK(hipGetLastError());
+  if (part) launch_sum_blocks(part, nb, 1, sum, s);
+}
+
+void test_vl_trial(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* upd,
+                   double lam, int first, int cap, double* trial, double* part, double* sum, hipStream_t s) {
+  const int nb = nblk(n);
+  hipLaunchKernelGGL(vl_trial_kernel, dim3(nb), dim3(kT), 0, s, n, lik, aux, y, off, mode, upd, lam, first, cap, trial,
+                     part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nb, 1, sum, s);
 }
 
 }  // namespace gpb_amd

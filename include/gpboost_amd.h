@@ -582,6 +582,44 @@ GPBOOST_AMD_EXPORT int GPB_TestVifVector(int op, int n, int m, int d, int cov_ty
                                          double pad_fill, const double* const* arrays, const int64_t* lens,
                                          int n_arrays, const int32_t* sum_ops, int nt, double* out, int64_t out_len,
                                          int* guard_flag);
+/* The likelihood layer of the Laplace paths (csrc/lik_device.h) on host arrays. No reference counterpart (tests).
+ * Everything is checked on the host before any device call, a violation being an error return; outputs and
+ * scratch start as NaN between 64 guard doubles on either side; guard_flag = 1 when a guard word changed or a
+ * scalar that was not asked for was written. lik: LatentLik of csrc/latent_kernels.h (0 gaussian, 1
+ * bernoulli_logit, 2 bernoulli_probit, 3 poisson, 4 gamma); aux finite and > 0; n < 2^22.
+ *
+ * GPB_TestLikPoint: log-likelihood, first derivative, information and the information's derivative at (y_i,
+ * loc_i), i < n, from a kernel that calls the four device functions and nothing else; dinfo_lowrank: the same
+ * derivative from the low-rank preconditioner's launch_lik_dinfo. */
+GPBOOST_AMD_EXPORT int GPB_TestLikPoint(int lik, double aux, int n, const double* y, const double* loc, double* loglik,
+                                        double* d1, double* info, double* dinfo, double* dinfo_lowrank,
+                                        int* guard_flag);
+/* One production kernel (set) of a Laplace path on its production grid (LikPath / LikKernel of csrc/lik_test.h).
+ * y, mode, offset (nullable), every vecs[k] and every outs[k]: n entries; an output is given exactly when its
+ * option asks for it (NULL otherwise). lam in (0, 1]. idx / arr0 / arr1 / mats are NULL (lengths 0) unless named.
+ *   path 0 grouped (mode NULL, offset = F; idx = glev, K x n with entries in [0, arr_len), arr0 = b; opts = {K,
+ *     want_dW}): kernel 0 glp_obs_kernel<true>, outs = {d1, W, dW}; kernel 1 glp_obs_kernel<false>, no outs; both
+ *     followed by glp_finish_kernel, scalars = {sum loglik}.
+ *   path 1 full-scale Vecchia: kernel 0 vl_prep_kernel (opts = {want_dW, want_rhs, want_count}, outs = {d1, W,
+ *     dW, rhs}, scalars = {#(W == 0)} with want_count); kernel 1 vl_trial_kernel (vecs = {upd}, opts = {first,
+ *     cap}, outs = {trial}, scalars = {sum loglik}).
+ *   path 2 FITC: kernel 0 fl_prep_kernel (vecs = {dvec, stored W (nullable with w_update)}, opts = {w_update,
+ *     want_rhs}, outs = {d1, W, wdw, DW, rhs}); kernel 1 fl_trial_kernel (vecs = {a, mupd, aupd}, outs = {mnew,
+ *     anew}, scalars = {a^T mode, sum loglik}); kernel 2 fl_final_kernel (vecs = {dvec}, outs = {d1, W, DW, dpwi},
+ *     scalars = {sum log dpwi, sum log W, #(W == 0)}).
+ *   path 3 dense: kernel 0 dl_prep_kernel (opts = {want_rhs}, outs = {d1, W, sqrt W, rhs}); kernel 1
+ *     dl_trial_kernel (as FITC's); kernel 2 dl_dmll_kernel (n <= 2048, opts = {ld >= n, want_dg}, mats = C then S,
+ *     ld x n column-major each, mats_len = 2 ld n, outs = {dmll, dg}).
+ *   path 4 sparse Vecchia: kernel 0 newton_prep_kernel (vecs = {Dinv, stored W (nullable with W_update)}, opts =
+ *     {W_update, want_rhs, want_dw, want_sdw}, outs = {d1, W, rhs, dw, sdw}; with an ObsMap idx = ptr (n + 1
+ *     entries, 0 .. arr_len ascending), arr0 = the observations' y, arr1 = their offset or NULL).
+ * The stored W is what a kernel reads with (w / W)_update = 0; outs[1] returns the block as the kernel left it. */
+GPBOOST_AMD_EXPORT int GPB_TestLikPath(int path, int kernel, int n, int lik, double aux, const double* y,
+                                       const double* mode, const double* offset, const double* const* vecs, int n_vecs,
+                                       const int32_t* idx, int64_t idx_len, const double* arr0, const double* arr1,
+                                       int64_t arr_len, const double* mats, int64_t mats_len, double lam,
+                                       const int32_t* opts, int n_opts, double* const* outs, int n_outs,
+                                       double* scalars, int n_scalars, int* guard_flag);
 /* The residual factor of a gp_approx = "full_scale_vecchia" model at cov_pars (original scale) in the model
  * order: perm (n, nullable: perm[i] = original index of the i-th point), neighbors (n x num_neighbors, nullable),
  * D (n), B_vals (n x num_neighbors, B(i, nbr) = -A_i, 0-padded) and their derivatives with respect to log var and
