@@ -600,9 +600,17 @@ class GPModel:
 
     def vecchia_rows_info(self):
         """Stored pair distances of the exact Vecchia row kernel: stored (0/1), bytes, rows, build_ms."""
-        out = np.zeros(4)
+        out = np.zeros(6)
         _safe_call(lib().GPB_GetVecchiaRowsInfo(self.handle, _dp(out)))
         return dict(stored=int(out[0]), bytes=int(out[1]), rows=int(out[2]), build_ms=float(out[3]))
+
+    def vecchia_rows_launch_info(self):
+        """The model's last likelihood or partial-sum launch of the 16-lane row kernel: trips (problem sets per
+        wave) and prio (1: the waves of a SIMD took turns at the issue priority; 0: GPBOOST_AMD_ROWS16_PRIO=0)
+        (GPB_GetVecchiaRowsInfo, values 4 and 5)."""
+        out = np.zeros(6)
+        _safe_call(lib().GPB_GetVecchiaRowsInfo(self.handle, _dp(out)))
+        return dict(trips=int(out[4]), prio=int(out[5]))
 
     def last_kernel_ms(self):
         out = np.zeros(2)

@@ -30,6 +30,12 @@ struct VecchiaRowsArgs {
                          // 2 = as 0 with G = ceil(sets / rounds) (every wave the same count)
   const double* R;       // 16-lane kernel, optional: the pair distances of phase 1, kRows16DistDoubles per row,
                          // indexed from row_base as nbr is (layout: vecchia_rows16.hip); null: computed per launch
+  int prio;              // 16-lane kernel: 1 = the two waves of a SIMD take turns at the higher issue priority, trip by
+                         // trip, and every wave lowers its own for the elimination (vecchia_rows16.hip); set by
+                         // the launcher, whatever the caller puts here is ignored
+#ifdef GPBOOST_AMD_ROWS16_PHASE
+  unsigned long long* phase;   // instrumented variant only: per-wave clock records (vecchia_rows16.hip)
+#endif
 };
 
 // Stored pair distances of the 16-lane row kernel: 15 deltas x 16 lanes x 2 slots per row (3840 bytes)
@@ -39,6 +45,8 @@ int vecchia_rows_blocks(int rows, int m);   // upper bound of the grid (block-pa
 int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);   // returns the grid size
 // 16-lane form for m <= 30 (vecchia_rows16.hip; DPP broadcasts, four rows per wave), same contract
 int launch_vecchia_rows16(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);
+// The last 16-lane launch of this process: trips per wave R and VecchiaRowsArgs::prio as launched
+void vecchia_rows16_last_launch(int* trips, int* prio);
 // True when launch_vecchia_rows would run the 16-lane form for this m (the A/B environment switches included)
 bool vecchia_rows16_selected(int m);
 // The distances of rows a.r0..a.r1 (a.X, a.nbr, a.d, a.m, a.row_base) into R, indexed as VecchiaRowsArgs::R

@@ -1348,6 +1348,8 @@ void REModelAMD::GetVecchiaRowsInfo(double* out) {
   out[1] = (double)(d_rows_dist_.size() * sizeof(double));
   out[2] = stored ? (double)(d_rows_dist_.size() / kRows16DistDoubles) : 0.;
   out[3] = stored ? rows_dist_ms_ : 0.;
+  out[4] = rows_trips_;
+  out[5] = rows_prio_;
 }
 
 void REModelAMD::LaunchVecchiaRows(const double* trafo, int r0, int r1, double* sums, bool allreduce) {
@@ -1381,6 +1383,7 @@ void REModelAMD::LaunchVecchiaRows(const double* trafo, int r0, int r1, double* 
   if (timing) HIP_CHECK(hipEventRecord(ev_[0], stream_));
   nblocks = launch_vecchia_rows(cfg_.cov_type, a, stream_);
   if (timing) HIP_CHECK(hipEventRecord(ev_[1], stream_));
+  if (vecchia_rows16_selected(a.m)) vecchia_rows16_last_launch(&rows_trips_, &rows_prio_);
   static const bool sync_wait = std::getenv("GPBOOST_AMD_EVAL_SYNC") != nullptr;   // A/B: stream sync
   if (sync_wait && !(allreduce && coll_ != nullptr)) {
     launch_sum_blocks(d_block_sums_.get(), nblocks, kVecchiaSums, h_sums_dev_, stream_);

@@ -134,7 +134,9 @@ class REModelAMD {
   // full_scale_vecchia: model order, neighbour lists (nullable), D, B values and their two derivatives (EXTENSION)
   void GetVifFactor(const double* cov_pars_orig, int* perm, int* nbr, double* D, double* Bvals, double* dD,
                     double* dBvals);
-  // [stored (0/1), bytes, rows, build ms] of the 16-lane row kernel's stored pair distances (EXTENSION)
+  // [stored (0/1), bytes, rows, build ms] of the 16-lane row kernel's stored pair distances, then of this
+  // model's last likelihood or partial-sum launch of that kernel [trips per wave, wave priorities on (0/1)]
+  // (EXTENSION; 6 values)
   void GetVecchiaRowsInfo(double* out);
   // Latent factor with range derivatives (EXTENSION, latent models only).
   void GetLatentVecchiaFactor(const double* cov_pars_orig, double* Dinv, double* Bvals, double* dD, double* dBvals);
@@ -336,6 +338,7 @@ class REModelAMD {
   // construction on (dist_obs_neighbors / dist_between_neighbors, Vecchia_utils.h).
   DevBuf<double> d_rows_dist_;
   double rows_dist_ms_ = 0.;   // the one-time distance kernel, by HIP events
+  int rows_trips_ = 0, rows_prio_ = 0;   // the last LaunchVecchiaRows through the 16-lane kernel (0: none yet)
   double* h_sums_ = nullptr;  // pinned
   double* h_sums_dev_ = nullptr;  // device address of h_sums_ (the single-rank sum kernel writes it directly)
   unsigned long long sum_seq_ = 0;  // completion flag value of the last single-rank evaluation (h_sums_[8])

@@ -39,8 +39,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "cov.h"
@@ -86,12 +88,54 @@ constexpr int kD3 = 3;   // coordinate dimension bound (VecchiaRowsArgs.d <= 3)
 // (6198 and 6304 vs 6338: slower the earlier they go); the own lane zeroing its entry of column j and
 // keeping the pivot right after the broadcast, beside the reciprocal, with the two reciprocals back at the end
 // (10 instructions more, a shorter dependent chain per pivot: 6320 vs 6372).
+//   - the waves' issue priorities (profiles/rows16_phase/RESULTS.md): 2 or 3 outside the elimination, 0 or 1
+//     inside it, the higher of each to the even-slot and the odd-slot wave of a SIMD by turns, trip by trip.
+//     Left alone the older wave (slot 0) is preferred and done after 208 k cycles, its partner after 284 k, a
+//     quarter of the kernel at one wave per SIMD. Figures in the record.
+// Rejected with it: a start delay of the odd-slot waves (s_sleep, 20 to 320 units of 64 cycles; the supposition
+// was that the two waves wait in phase: the clock records show their offsets spread over the whole half trip
+// without it): 6763, 6799, 6795, 6776, 6682 vs 6731 without and 6812 for the parent, the parent's spread 84;
+// the priority by turns alone, and the lower priority in the elimination alone (same level for both waves): each
+// about half of the two together (6428 and 6439 vs 6537 with both, ties to the older wave, 6263 without, a
+// session with a spread of 230).
 // Rejected: the next pivot's broadcast, reciprocal and multipliers issued after the step's first three
 // columns and left to the compiler to schedule under the rest of the step's fmacs (it did interleave
 // them): 5616 with vs 5628 without, inside the noise; round 4 had measured the hand-pinned form slower.
 
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void cfence() { asm volatile("" ::: "memory"); }
+
+// s_getreg operands (size - 1 << 11 | offset << 6 | register): HW_ID is register 4 on gfx9, WAVE_ID (the wave's
+// slot of its SIMD) its bits 3:0, SIMD_ID 5:4, CU_ID 11:8, SH_ID 12, SE_ID 14:13; XCC_ID is register 20, bits 3:0
+constexpr int kHwWaveSlot = 3 << 11 | 4;
+
+// Instrumented variant (GPBOOST_AMD_DEFS=-DGPBOOST_AMD_ROWS16_PHASE=1 builds; never in the default library):
+// every wave writes, by lane 0's ordinary stores, kPhaseStride 64-bit words to a.phase: HW_ID, XCC_ID, the
+// shader clock at entry, the trips it ran, then for each of its first kPhaseTrips trips the clock at the top of
+// the trip, after the covariances (the records' vmcnt wait is behind it) and after the elimination (a mark
+// after the row load, where every register is live, spilled). With GPBOOST_AMD_ROWS16_PHASE_DUMP=<file> the launcher waits for the kernel and writes the
+// records of that launch to the file (scripts/rows16_phase_offsets.py reads it).
+#ifdef GPBOOST_AMD_ROWS16_PHASE
+constexpr int kHwId = 31 << 11 | 4, kHwXcc = 3 << 11 | 20;
+constexpr int kPhaseTrips = 16, kPhaseMarks = 3, kPhaseHead = 4;
+constexpr int kPhaseStride = kPhaseHead + kPhaseTrips * kPhaseMarks;
+#define PHASE_ID()                                                      \
+  unsigned long long* const phase_rec = a.phase + (size_t)blockIdx.x * kPhaseStride; \
+  if (threadIdx.x == 0) {                                               \
+    phase_rec[0] = __builtin_amdgcn_s_getreg(kHwId);                    \
+    phase_rec[1] = __builtin_amdgcn_s_getreg(kHwXcc);                   \
+    phase_rec[2] = clock64();                                           \
+  }
+#define PHASE_MARK(IT, K)                                               \
+  asm volatile("" ::: "memory");                                        \
+  if (threadIdx.x == 0 && (IT) < kPhaseTrips) phase_rec[kPhaseHead + (IT) * kPhaseMarks + (K)] = clock64()
+#define PHASE_END(IT) \
+  if (threadIdx.x == 0) phase_rec[3] = (IT)
+#else
+#define PHASE_ID()
+#define PHASE_MARK(IT, K)
+#define PHASE_END(IT)
+#endif
 
 template <int CTRL>
 __device__ __forceinline__ double dpp32x2(double v) {   // all controls used have a source lane for every lane
@@ -387,6 +431,12 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
       for (int q = 0; q < 15; ++q) rr[q] = rp[q * 16];
     }
   };
+  // The two waves of a SIMD hold wave slots 0 and 1 (HW_ID's WAVE_ID, bits 3:0; the instrumented variant's
+  // records show it on every SIMD) and the issue arbiter prefers the older one, slot 0: left alone it runs its
+  // trips in 17 k cycles, its partner in 24 k, and the partner then runs its last third alone at one wave per
+  // SIMD (profiles/rows16_phase/RESULTS.md). a.prio shares the SIMD out by s_setprio, see the loop.
+  PHASE_ID();
+  const int odd = __builtin_amdgcn_s_getreg(kHwWaveSlot) & 1;
   if (set_at(0) < nsets) prefetch(set_at(0));
   // log(D) leaves the set loop: lane (it & 15) of each 16-lane row keeps trip it's D (1 where the slot has
   // no row), and every 16th trip, and once after the loop, all lanes take the log of theirs at once and
@@ -404,6 +454,17 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
   for (int it = 0; it < R; ++it) {
     const int set = set_at(it);
     if (set >= nsets) break;
+    // Priority 2 or 3 outside the elimination, 0 or 1 inside it, the higher of each to the waves in even and in odd
+    // slots by turns (trip parity): a wave at one of the trip's waits or LDS round trips is served before a wave
+    // that has 986 independent instructions to issue, and neither wave of a SIMD is the preferred one for longer
+    // than a trip, so both finish together. Issue order only: no result depends on it.
+    const bool turn = (it ^ odd) & 1;
+    if (a.prio) {
+      if (turn) __builtin_amdgcn_s_setprio(3);
+      else __builtin_amdgcn_s_setprio(2);
+    }
+    PHASE_MARK(it, 0);
+    PHASE_END(it + 1);
     const int base = set * 4;
     int h = lane & 15;
     asm volatile("" : "+v"(h));   // lane-dependent addresses / masks recomputed per problem (not hoisted)
@@ -469,6 +530,7 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
       });
     }
     lds_sync();
+    PHASE_MARK(it, 1);
     // border row 31 (y_nbr); row 30 (c) came from the slot-30 pairs
     Cp[tri(kMK + 1) + h] = y0s;
     if (v1 < kMK) Cp[tri(kMK + 1) + v1] = y1s;
@@ -537,6 +599,10 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
         own_lane<jl>(i0, m0, rinv);
       }
     };
+    if (a.prio) {
+      if (turn) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+    }
     sfor<0, kMK>([&](auto J) {
       constexpr int j = decltype(J)::value;
       constexpr bool jhi = j >= 16;
@@ -579,6 +645,7 @@ __device__ __forceinline__ void rows16_body(const VecchiaRowsArgs& a) {
         fmac_bcast16<j>(r0[kMK + 1], r0[kMK + 1], r0[j]);
       });
     }
+    PHASE_MARK(it, 2);
     if constexpr (STORED) {   // the row registers are dead: the next set's loads go out here
       cfence();
       // no branch around the loads (the records just consumed would stay live through the elimination on the
@@ -715,8 +782,32 @@ __global__ void __launch_bounds__(64) vecchia_rows16_dist_kernel(VecchiaRowsArgs
 
 constexpr int kMaxGrid = 2048;   // vecchia_rows_blocks' bound (kernels.h)
 
+int g_last_trips = 0, g_last_prio = 0;   // vecchia_rows16_last_launch
+
+#ifdef GPBOOST_AMD_ROWS16_PHASE
+unsigned long long* phase_buffer() {   // kMaxGrid records, allocated once and kept
+  static unsigned long long* buf = nullptr;
+  if (buf == nullptr) HIP_CHECK(hipMalloc(&buf, sizeof(unsigned long long) * kMaxGrid * kPhaseStride));
+  return buf;
+}
+
+void phase_dump(int blocks, int prio, hipStream_t s) {
+  const char* path = std::getenv("GPBOOST_AMD_ROWS16_PHASE_DUMP");
+  if (path == nullptr) return;
+  std::vector<unsigned long long> h((size_t)blocks * kPhaseStride + 4);
+  h[0] = blocks; h[1] = kPhaseStride; h[2] = kPhaseTrips | kPhaseMarks << 16; h[3] = prio;
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipMemcpy(h.data() + 4, phase_buffer(), sizeof(unsigned long long) * blocks * kPhaseStride, hipMemcpyDeviceToHost));
+  if (FILE* f = std::fopen(path, "wb")) {
+    std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+    std::fclose(f);
+  }
+}
+#endif
+
 template <auto KERN>
-int launch16_at(size_t lds, const VecchiaRowsArgs& a, hipStream_t s) {
+int launch16_at(size_t lds, const VecchiaRowsArgs& args, hipStream_t s) {
+  VecchiaRowsArgs a = args;
   static int cap = 0;   // per kernel instance
   if (cap == 0) {
     int dev = 0, cus = 0, per_cu = 0;
@@ -734,10 +825,30 @@ int launch16_at(size_t lds, const VecchiaRowsArgs& a, hipStream_t s) {
     const int rounds = (need + blocks - 1) / blocks;
     blocks = (need + rounds - 1) / rounds;
   }
+  g_last_trips = (need + blocks - 1) / blocks;
+  // GPBOOST_AMD_ROWS16_PRIO=0 (read at every launch) leaves every wave at the default priority: A/B and tests
+  const char* pe = std::getenv("GPBOOST_AMD_ROWS16_PRIO");
+  g_last_prio = a.prio = (pe == nullptr || std::atoi(pe) != 0) ? 1 : 0;
+#ifdef GPBOOST_AMD_ROWS16_PHASE
+  a.phase = phase_buffer();
+  HIP_CHECK(hipMemsetAsync(a.phase, 0, sizeof(unsigned long long) * blocks * kPhaseStride, s));
+#endif
   hipLaunchKernelGGL(KERN, dim3(blocks), dim3(64), lds, s, a);
   HIP_CHECK(hipGetLastError());
+#ifdef GPBOOST_AMD_ROWS16_PHASE
+  phase_dump(blocks, a.prio, s);
+#endif
   return blocks;
 }
+
+}  // namespace
+
+void vecchia_rows16_last_launch(int* trips, int* prio) {
+  *trips = g_last_trips;
+  *prio = g_last_prio;
+}
+
+namespace {
 
 template <int COV, int DIM>
 int launch16(const VecchiaRowsArgs& a, hipStream_t s) {

@@ -331,7 +331,10 @@ GPBOOST_AMD_EXPORT int GPB_GetVecchiaFactor(REModelHandle handle, const double* 
 
 /* Stored pair distances of the exact Vecchia row kernel (num_neighbors 17..30; built at the first
  * evaluation): out[0] 1 if this model holds them, out[1] their bytes of device memory, out[2] the
- * rows they cover (this rank's), out[3] the milliseconds the one-time distance kernel took. */
+ * rows they cover (this rank's), out[3] the milliseconds the one-time distance kernel took. Then the
+ * model's last likelihood or partial-sum launch of that kernel: out[4] the problem sets (4 rows) each wave
+ * ran, out[5] 1 if the waves took turns at the issue priority (the default), 0 if
+ * GPBOOST_AMD_ROWS16_PRIO=0 switched that off. out holds 6 doubles. */
 GPBOOST_AMD_EXPORT int GPB_GetVecchiaRowsInfo(REModelHandle handle, double* out);
 
 /* Latent Vecchia factor at cov_pars = (sigma1^2, rho) (latent models): D^-1 (n), B values
