@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "grouped_model.h"
+#include "laplace_newton.h"
 #include "latent_test.h"
 #include "re_model.h"
 #include "sparse_chol.h"
@@ -688,6 +690,26 @@ int GPB_PivotedCholeskyHost(const double* coords, int n, int d, int cov_type, do
   API_BEGIN();
   if (n < 1 || d < 1 || rank < 1 || cov_type < 0 || cov_type > 3) gpb_amd::Fatal("GPB_PivotedCholeskyHost: invalid argument");
   *out_rank = gpb_amd::pivoted_cholesky_host(cov_type, coords, n, d, var, phi, rank, tol, L, pivots);
+  API_END();
+}
+
+int GPB_TestNewtonLineSearch(int it, double obj, double gdd, double delta, int max_shrink, const double* trial_objs,
+                             int n_trials, double* out) {
+  API_BEGIN();
+  if (it < 0 || max_shrink < 1 || n_trials < 0 || out == nullptr || (n_trials > 0 && trial_objs == nullptr))
+    gpb_amd::Fatal("GPB_TestNewtonLineSearch: invalid argument");
+  for (int k = 0; k < n_trials; ++k) out[5 + k] = std::numeric_limits<double>::quiet_NaN();
+  const gpb_amd::LineSearchResult r =
+      gpb_amd::newton_line_search(it, obj, gdd, delta, max_shrink, [&](double lam, int ih) {
+        if (ih >= n_trials) gpb_amd::Fatal("GPB_TestNewtonLineSearch: trial %d asked for, %d scripted", ih, n_trials);
+        out[5 + ih] = lam;
+        return trial_objs[ih];
+      });
+  out[0] = r.obj_new;
+  out[1] = r.lam;
+  out[2] = r.trials;
+  out[3] = r.terminate ? 1. : 0.;
+  out[4] = r.nan ? 1. : 0.;
   API_END();
 }
 

@@ -8,9 +8,25 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "common.h"
+
 namespace gpb_amd {
 
 enum CovType : int { kMatern05 = 0, kMatern15 = 1, kMatern25 = 2, kGaussian = 3 };
+
+// f(std::integral_constant<int, cov>{}): the host's switch from a runtime covariance type to a template argument
+template <typename F>
+void dispatch_cov(int cov, F&& f) {
+  switch (cov) {
+    case kMatern05: f(std::integral_constant<int, kMatern05>{}); break;
+    case kMatern15: f(std::integral_constant<int, kMatern15>{}); break;
+    case kMatern25: f(std::integral_constant<int, kMatern25>{}); break;
+    case kGaussian: f(std::integral_constant<int, kGaussian>{}); break;
+    default: Fatal("unsupported covariance type %d", cov);
+  }
+}
 
 template <int COV>
 __host__ __device__ __forceinline__ void cov_dcov(double r, double var, double phi, double& c, double& dc) {

@@ -922,17 +922,6 @@ void gemm(hipStream_t s, int M, int N, int K, double alpha, const double* A, int
   HIP_CHECK(hipGetLastError());
 }
 
-template <typename F>
-void dispatch_cov(int cov, F&& f) {
-  switch (cov) {
-    case kMatern05: f(std::integral_constant<int, kMatern05>{}); break;
-    case kMatern15: f(std::integral_constant<int, kMatern15>{}); break;
-    case kMatern25: f(std::integral_constant<int, kMatern25>{}); break;
-    case kGaussian: f(std::integral_constant<int, kGaussian>{}); break;
-    default: Fatal("unsupported covariance type %d", cov);
-  }
-}
-
 }  // namespace
 
 void gemm_f64(hipStream_t s, int M, int N, int K, double alpha, const double* A, int lda, int transA, const double* B,

@@ -15,7 +15,8 @@
 // Every n x n step runs on the dense path's MFMA kernels (dense.h: chol_lower, trtri_lower, gemm_f64):
 // one Cholesky and one triangular inverse of B per Newton step, every matrix-vector product as an MFMA
 // GEMM with one column, (W^-1 + Sigma)^-1 = Q^T Q and L^-1 W^1/2 Sigma = Q Sigma (Q = L^-1 W^1/2) for the
-// gradient; the host runs the Newton / Armijo logic on reduced scalars.
+// gradient; the host runs the Newton / Armijo logic on reduced scalars (newton_line_search, laplace_newton.h; the
+// trial, slope and product kernels are those of laplace_kernels.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,15 +26,12 @@
 
 namespace gpb_amd {
 
-class DenseLaplace : public LatentSolverBase {
+class DenseLaplace : public ObsLaplaceBase {
  public:
   // d_X: device coordinates, row-major n x d (distinct points), owned by the caller
   DenseLaplace(int n, int d, const double* d_X, hipStream_t stream);
   ~DenseLaplace() override;
 
-  void SetY(const double* y) override;
-  void SetOffset(const double* off) override;
-  void GetMode(double* mode) override;
   // trafo = (sigma1^2, phi); grad = [d/dlog sigma1^2, d/dlog phi] of the negative approximate marginal
   // log-likelihood (+ d/dlog shape for likelihood 'gamma' with want_aux_grad: CalcGradNegLogLikAuxPars +
   // 1/2 sum dW/dlog shape o diag((Sigma^-1 + W)^-1) + the implicit term, likelihoods.h:3379-3411, 10508-10524,
@@ -57,17 +55,15 @@ class DenseLaplace : public LatentSolverBase {
   void Gemv(const double* M, bool lower, bool trans, const double* x, double* y);
   bool InfoFailed();
 
-  int n_, d_, ld_;
+  int d_, ld_;
   const double* d_X_;
-  hipStream_t s_;
-  bool y_set_ = false, has_off_ = false, prev_valid_ = false, evaluated_ = false;
+  bool prev_valid_ = false, evaluated_ = false;
   double cached_obj_ = 0.;
   double aux_ = 1.;   // the likelihood's auxiliary parameter (gamma: shape)
-  double sum_log_y_ = 0.;
   int cov_type_ = 0;
   double var_ = 0., phi_ = 0.;
   DevBuf<double> Sig_, B_, Li_, X_, R_, C_;   // n x n (ld); X_: trtri scratch
-  DevBuf<double> y_, off_, mode_, a_, mode_prev_, a_prev_, mode_upd_, a_upd_, d1_, w_, ws_, rhs_, t1_, t2_, t3_, t4_;
+  DevBuf<double> a_, mode_prev_, a_prev_, mode_upd_, a_upd_, d1_, w_, ws_, rhs_, t1_, t2_, t3_, t4_;
   DevBuf<double> dmll_, dg_, uv_, ur_, rec_, cols_, red_;
   DevBuf<int> info_;
   double* h_red_ = nullptr;

@@ -3,7 +3,8 @@
 //   d1, W, W^1/2, rhs = W mode + d1                     one thread per observation
 //   B = I + W^1/2 Sigma W^1/2, B = L L^T, L^-1             POTRF + TRTRI (MFMA trailing updates)
 //   a_upd = rhs - W^1/2 L^-T L^-1 (W^1/2 Sigma rhs)        four one-column GEMMs, mode_upd = Sigma a_upd
-//   Armijo line search on -1/2 a^T mode + sum log p(y | mode + F)
+//   Armijo line search on -1/2 a^T mode + sum log p(y | mode + F)   newton_line_search (laplace_newton.h) on the
+//                                                               shared trial / slope kernels (laplace_kernels.h)
 // and for the gradient Q = L^-1 W^1/2, R = Q^T Q = (W^-1 + Sigma)^-1, C = Q Sigma (two MFMA GEMMs), one fused
 // pass over the columns of Sigma / R with the range derivative of Sigma recomputed from the coordinates.
 #include <hip/hip_runtime.h>
@@ -15,31 +16,15 @@
 #include "dense.h"
 #include "dense_laplace.h"
 #include "kernels.h"
+#include "laplace_kernels.h"
 #include "lik_device.h"
 #include "lik_test.h"
+#include "reduce.h"
 
 namespace gpb_amd {
 namespace {
 
 constexpr int kT = 256;
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = kT / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  const double s = red[0];
-  __syncthreads();
-  return s;
-}
 
 __device__ __forceinline__ double sqdist(const double* X, const double* Y, int i, int j, int d) {
   double s = 0.;
@@ -111,62 +96,12 @@ __global__ void __launch_bounds__(kT) dl_prep_kernel(int n, int lik, double aux,
   if (rhs) rhs[i] = wi * mi + g;
 }
 
-__global__ void __launch_bounds__(kT) dl_mul_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
-                                                   double* __restrict__ out) {
-  const int i = blockIdx.x * kT + threadIdx.x;
-  if (i < n) out[i] = a[i] * b[i];
-}
-
 // SigmaI_mode_update = rhs - W^1/2 B^-1 rhs2 (likelihoods.h:1900-1902)
 __global__ void __launch_bounds__(kT) dl_aupd_kernel(int n, const double* __restrict__ rhs, const double* __restrict__ ws,
                                                     const double* __restrict__ t, double* __restrict__ aupd) {
   const int i = blockIdx.x * kT + threadIdx.x;
   if (i >= n) return;
   aupd[i] = (-t[i]) * ws[i] + rhs[i];
-}
-
-// Armijo slope: sum_i dir_i (aupd_i - a_i + W_i dir_i), dir = mupd - mode (likelihoods.h:1906-1909)
-__global__ void __launch_bounds__(kT) dl_gdd_kernel(int n, const double* __restrict__ mode, const double* __restrict__ a,
-                                                   const double* __restrict__ mupd, const double* __restrict__ aupd,
-                                                   const double* __restrict__ w, double* __restrict__ part) {
-  __shared__ double red[kT];
-  double acc = 0.;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
-    const double dir = mupd[i] - mode[i];
-    acc += dir * (aupd[i] - a[i] + w[i] * dir);
-  }
-  const double s = block_sum(acc, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// one line-search trial (likelihoods.h:1910-1928) at learning rate lam; partials of [a^T mode, sum log p]
-__global__ void __launch_bounds__(kT) dl_trial_kernel(int n, int lik, double aux, double lam, const double* __restrict__ mode,
-                                                     const double* __restrict__ a, const double* __restrict__ mupd,
-                                                     const double* __restrict__ aupd, const double* __restrict__ y,
-                                                     const double* __restrict__ off, double* __restrict__ mnew,
-                                                     double* __restrict__ anew, double* __restrict__ part) {
-  __shared__ double red[kT];
-  double sq = 0., sl = 0.;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
-    double mi, ai;
-    if (lam == 1.) {
-      mi = mupd[i];
-      ai = aupd[i];
-    } else {
-      ai = (1. - lam) * a[i] + lam * aupd[i];
-      mi = (1. - lam) * mode[i] + lam * mupd[i];
-    }
-    mnew[i] = mi;
-    anew[i] = ai;
-    sq += ai * mi;
-    sl += lik_loglik(lik, aux, y[i], off ? mi + off[i] : mi);
-  }
-  const double s0 = block_sum(sq, red);
-  const double s1 = block_sum(sl, red);
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = s0;
-    part[2 * blockIdx.x + 1] = s1;
-  }
 }
 
 // Q = L^-1 diag(W^1/2) in place (L_inv_Wsqrt, likelihoods.h:3298-3301): lower triangle, column scaling
@@ -196,7 +131,7 @@ __global__ void __launch_bounds__(kT) dl_dmll_kernel(const double* __restrict__ 
     const double c = C[(size_t)k + (size_t)j * ld];
     s += c * c;
   }
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) {
     const double dg = S[(size_t)j + (size_t)j * ld] - s;
     const double l = off ? mode[j] + off[j] : mode[j];
@@ -230,12 +165,12 @@ __global__ void __launch_bounds__(kT) dl_grad_cols_kernel(const double* __restri
     s4 += r * c;
     s5 += r * dc;
   }
-  s0 = wsum(s0);
-  s1 = wsum(s1);
-  s2 = wsum(s2);
-  s3 = wsum(s3);
-  s4 = wsum(s4);
-  s5 = wsum(s5);
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  s3 = wave_sum(s3);
+  s4 = wave_sum(s4);
+  s5 = wave_sum(s5);
   if (lane == 0) {
     cols[j] = s0;
     cols[(size_t)ld + j] = s1;
@@ -298,28 +233,14 @@ __global__ void __launch_bounds__(kT) dl_predvar_kernel(const double* __restrict
     const double x = M[(size_t)i + (size_t)p * ld];
     s += x * x;
   }
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) out[p] = var - s;
 }
-
-template <typename F>
-void dispatch_cov(int cov, F&& f) {
-  switch (cov) {
-    case kMatern05: f(std::integral_constant<int, kMatern05>{}); break;
-    case kMatern15: f(std::integral_constant<int, kMatern15>{}); break;
-    case kMatern25: f(std::integral_constant<int, kMatern25>{}); break;
-    case kGaussian: f(std::integral_constant<int, kGaussian>{}); break;
-    default: Fatal("unsupported covariance type %d", cov);
-  }
-}
-
-inline int nb_thread(int n) { return std::max(1, (n + kT - 1) / kT); }
-inline int nb_red(int n) { return std::min(1024, nb_thread(n)); }
 
 }  // namespace
 
 DenseLaplace::DenseLaplace(int n, int d, const double* d_X, hipStream_t stream)
-    : n_(n), d_(d), ld_(((n + 63) / 64) * 64), d_X_(d_X), s_(stream) {
+    : ObsLaplaceBase(n, stream), d_(d), ld_(((n + 63) / 64) * 64), d_X_(d_X) {
   const size_t nn = (size_t)ld_ * ld_;
   for (DevBuf<double>* b : {&Sig_, &B_, &Li_, &R_, &C_}) {
     b->alloc(nn);
@@ -331,7 +252,7 @@ DenseLaplace::DenseLaplace(int n, int d, const double* d_X, hipStream_t stream)
     b->alloc(ld_);
     HIP_CHECK(hipMemsetAsync(b->get(), 0, sizeof(double) * ld_, s_));
   }
-  rec_.alloc(std::max<size_t>((size_t)6 * ld_, (size_t)2 * nb_red(n)));
+  rec_.alloc(std::max<size_t>((size_t)6 * ld_, (size_t)2 * laplace_blocks(n)));
   cols_.alloc((size_t)6 * ld_);
   red_.alloc(32);
   info_.alloc(1);
@@ -344,27 +265,6 @@ DenseLaplace::~DenseLaplace() {
   if (h_red_) (void)hipHostFree(h_red_);
   for (auto& e : ev_)
     if (e) (void)hipEventDestroy(e);
-}
-
-void DenseLaplace::SetY(const double* y) {
-  sum_log_y_ = 0.;   // aux_log_normalizing_constant_ of likelihood 'gamma' (likelihoods.h:8181-8191)
-  for (int i = 0; i < n_; ++i) sum_log_y_ += y[i] > 0. ? std::log(y[i]) : 0.;
-  HIP_CHECK(hipMemcpyAsync(y_.get(), y, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-  HIP_CHECK(hipStreamSynchronize(s_));
-  y_set_ = true;
-}
-
-void DenseLaplace::SetOffset(const double* off) {
-  has_off_ = off != nullptr;
-  if (has_off_) {
-    HIP_CHECK(hipMemcpyAsync(off_.get(), off, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-    HIP_CHECK(hipStreamSynchronize(s_));
-  }
-}
-
-void DenseLaplace::GetMode(double* mode) {
-  HIP_CHECK(hipMemcpyAsync(mode, mode_.get(), sizeof(double) * n_, hipMemcpyDeviceToHost, s_));
-  HIP_CHECK(hipStreamSynchronize(s_));
 }
 
 void DenseLaplace::ResetModeToPrevious() {
@@ -420,11 +320,9 @@ LatentResult DenseLaplace::Eval(int cov_type, int lik, const double* trafo, doub
   double* red = red_.get();
   HIP_CHECK(hipEventRecord(ev_[0], s_));
   BuildSigma(cov_type, var, phi);
-  const int nbr = nb_red(n);
+  const int nbr = laplace_blocks(n);
   auto objective = [&](double lam, const double* mu, const double* au, double* mnew, double* anew) {
-    hipLaunchKernelGGL(dl_trial_kernel, dim3(nbr), dim3(kT), 0, s_, n, lik, aux_, lam, mode_.get(), a_.get(), mu, au, y_.get(),
-                       off, mnew, anew, rec_.get());
-    HIP_CHECK(hipGetLastError());
+    launch_laplace_trial(n, lik, aux_, lam, mode_.get(), a_.get(), mu, au, y_.get(), off, mnew, anew, rec_.get(), s_);
     launch_sum_blocks(rec_.get(), nbr, 2, red + 4, s_);
     HIP_CHECK(hipMemcpyAsync(h_red_ + 4, red + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, s_));
     HIP_CHECK(hipStreamSynchronize(s_));
@@ -443,24 +341,22 @@ LatentResult DenseLaplace::Eval(int cov_type, int lik, const double* trafo, doub
     Gemv(Sig_.get(), false, false, a_.get(), mode_.get());
   }
   double* logdet_B = red + 1;
-  int it = 0;
   if (start != ModeStart::kKeep || !evaluated_) {
     double obj = objective(1., mode_.get(), a_.get(), mode_upd_.get(), a_upd_.get());
-    const int maxit = 1000;                              // maxit_mode_newton_ (likelihoods.h:12721)
-    const double delta = cfg.delta_conv_mode_finding;    // :12723
-    bool terminate = false, has_nan = false;
-    for (it = 0; it < maxit; ++it) {
+    const double delta = cfg.delta_conv_mode_finding;    // likelihoods.h:12723
+    bool has_nan = false;
+    for (int it = 0; it < kMaxItModeNewton; ++it) {
       // the information changes in every step for the supported likelihoods (information_changes_during_mode_finding_)
-      hipLaunchKernelGGL(dl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(),
+      hipLaunchKernelGGL(dl_prep_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(),
                          d1_.get(), w_.get(), ws_.get(), rhs_.get());
       HIP_CHECK(hipGetLastError());
       FactorB(logdet_B, true);
       // rhs2 = W^1/2 Sigma rhs; a_upd = rhs - W^1/2 L^-T L^-1 rhs2; mode_upd = Sigma a_upd (:1897-1903)
       Gemv(Sig_.get(), false, false, rhs_.get(), t1_.get());
-      hipLaunchKernelGGL(dl_mul_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, ws_.get(), t1_.get(), t2_.get());
+      launch_laplace_mul(n, ws_.get(), t1_.get(), t2_.get(), s_);
       Gemv(Li_.get(), true, false, t2_.get(), t3_.get());
       Gemv(Li_.get(), true, true, t3_.get(), t4_.get());
-      hipLaunchKernelGGL(dl_aupd_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, rhs_.get(), ws_.get(), t4_.get(),
+      hipLaunchKernelGGL(dl_aupd_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, rhs_.get(), ws_.get(), t4_.get(),
                          a_upd_.get());
       HIP_CHECK(hipGetLastError());
       Gemv(Sig_.get(), false, false, a_upd_.get(), mode_upd_.get());
@@ -468,44 +364,30 @@ LatentResult DenseLaplace::Eval(int cov_type, int lik, const double* trafo, doub
         has_nan = true;
         break;
       }
-      hipLaunchKernelGGL(dl_gdd_kernel, dim3(nbr), dim3(kT), 0, s_, n, mode_.get(), a_.get(), mode_upd_.get(),
-                         a_upd_.get(), w_.get(), rec_.get());
+      launch_laplace_gdd(n, mode_.get(), a_.get(), mode_upd_.get(), a_upd_.get(), w_.get(), rec_.get(), s_);
       launch_sum_blocks(rec_.get(), nbr, 1, red + 6, s_);
       HIP_CHECK(hipMemcpyAsync(h_red_ + 6, red + 6, sizeof(double), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
       const double gdd = h_red_[6];
-      // backtracking (:1910-1928); the last trial is kept when none is accepted
-      double lam = 1., obj_new = obj;
-      for (int ih = 0; ih < 20; ++ih) {   // max_number_lr_shrinkage_steps_newton_ (:12725)
-        obj_new = objective(lam, mode_upd_.get(), a_upd_.get(), t1_.get(), t2_.get());
-        if (obj_new < obj + 1e-4 * lam * gdd || std::isnan(obj_new) || std::isinf(obj_new)) lam *= 0.5;   // c_armijo_
-        else break;
-      }
+      // backtracking (:1910-1928) and the convergence rule
+      const LineSearchResult ls = newton_line_search(it, obj, gdd, delta, kMaxShrinkNewton, [&](double lam, int) {
+        return objective(lam, mode_upd_.get(), a_upd_.get(), t1_.get(), t2_.get());
+      });
       std::swap(mode_, t1_);   // mode_ = mode_new, SigmaI_mode_ = SigmaI_mode_new
       std::swap(a_, t2_);
-      // CheckConvergenceModeFinding (:11820-11870)
-      if (std::isnan(obj_new) || std::isinf(obj_new)) {
-        has_nan = true;
-        obj = obj_new;
-        break;
-      }
-      if (it == 0) terminate = std::abs(obj_new - obj) < delta * std::abs(obj);
-      else terminate = (obj_new - obj) < delta * std::abs(obj);
-      obj = obj_new;
-      if (terminate) {
-        ++it;
-        break;
-      }
+      res.newton_its = it + 1;
+      obj = ls.obj_new;
+      has_nan = ls.nan;
+      if (ls.nan || ls.terminate) break;
     }
     if (has_nan) throw LatentNan("NaN or Inf occurred in the dense mode finding");
-    res.newton_its = it;
     cached_obj_ = obj;
   }
   evaluated_ = true;
   // at the mode (:1941-1953): d1, W, B = I + W^1/2 Sigma W^1/2 = L L^T; mll = obj - sum log L_ii
   const bool need_inv = want_grad || want_aux_grad || grad_f != nullptr;
-  hipLaunchKernelGGL(dl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(), d1_.get(),
-                     w_.get(), ws_.get(), nullptr);
+  hipLaunchKernelGGL(dl_prep_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(),
+                     d1_.get(), w_.get(), ws_.get(), nullptr);
   HIP_CHECK(hipGetLastError());
   FactorB(logdet_B, need_inv);
   HIP_CHECK(hipMemcpyAsync(h_red_, red, 2 * sizeof(double), hipMemcpyDeviceToHost, s_));
@@ -538,7 +420,7 @@ LatentResult DenseLaplace::Eval(int cov_type, int lik, const double* trafo, doub
       Gemv(Sig_.get(), false, false, t1_.get(), uv_.get());
       Gemv(R_.get(), false, false, cb + 3 * (size_t)ld, t1_.get());
       Gemv(Sig_.get(), false, false, t1_.get(), ur_.get());
-      hipLaunchKernelGGL(dl_grad_rec_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, ld, a_.get(), cb, dmll_.get(),
+      hipLaunchKernelGGL(dl_grad_rec_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, ld, a_.get(), cb, dmll_.get(),
                          uv_.get(), ur_.get(), recs);
       HIP_CHECK(hipGetLastError());
       launch_sum_blocks(recs, n, 6, red + 8, s_);
@@ -556,20 +438,17 @@ LatentResult DenseLaplace::Eval(int cov_type, int lik, const double* trafo, doub
     if (want_aux_grad) {
       // gamma shape on the log scale: a [sum (l + y e^-l) - n (log a + 1 - digamma(a)) - sum log y]
       // + 1/2 sum W_i diag_i + sum d1_i (Sigma dmll - C^T C dmll)_i  (dW/dlog a = W, d2 ll / dl dlog a = d1)
-      hipLaunchKernelGGL(dl_aux_rec_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, y_.get(), off, mode_.get(), w_.get(),
+      hipLaunchKernelGGL(dl_aux_rec_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, y_.get(), off, mode_.get(), w_.get(),
                          dg_.get(), d1_.get(), t1_.get(), t3_.get(), rec_.get());
       HIP_CHECK(hipGetLastError());
       launch_sum_blocks(rec_.get(), n, 3, red + 16, s_);
       HIP_CHECK(hipMemcpyAsync(h_red_ + 16, red + 16, 3 * sizeof(double), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
-      const double a = aux_;
-      double neg = h_red_[16] - n * (std::log(a) + 1. - digamma_asa103(a)) - sum_log_y_;
-      neg *= a;
       if (res.grad.empty()) res.grad = {0., 0.};
-      res.grad.push_back(neg + 0.5 * h_red_[17] + h_red_[18]);
+      res.grad.push_back(gamma_shape_grad(aux_, n, h_red_[16], h_red_[17], h_red_[18], sum_log_y_));
     }
     if (grad_f != nullptr) {
-      hipLaunchKernelGGL(dl_gradf_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, d1_.get(), dmll_.get(), w_.get(),
+      hipLaunchKernelGGL(dl_gradf_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, d1_.get(), dmll_.get(), w_.get(),
                          t1_.get(), t3_.get(), t4_.get());
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipMemcpyAsync(grad_f, t4_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
@@ -628,22 +507,10 @@ void DenseLaplace::Predict(int cov_type, double var, double phi, const double* X
 }
 
 // ---- test launchers (lik_test.h): the launches of FindMode / Eval on their production grids and the block sums
-int test_dl_blocks(int n) { return nb_red(n); }
-
 void test_dl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, double* d1,
                   double* w, double* ws, double* rhs, hipStream_t s) {
-  hipLaunchKernelGGL(dl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s, n, lik, aux, y, off, mode, d1, w, ws, rhs);
+  hipLaunchKernelGGL(dl_prep_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s, n, lik, aux, y, off, mode, d1, w, ws, rhs);
   HIP_CHECK(hipGetLastError());
-}
-
-void test_dl_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
-                   const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
-                   double* sums, hipStream_t s) {
-  const int nbr = nb_red(n);
-  hipLaunchKernelGGL(dl_trial_kernel, dim3(nbr), dim3(kT), 0, s, n, lik, aux, lam, mode, a, mupd, aupd, y, off, mnew, anew,
-                     part);
-  HIP_CHECK(hipGetLastError());
-  launch_sum_blocks(part, nbr, 2, sums, s);
 }
 
 void test_dl_dmll(const double* C, const double* S, int n, int ld, int lik, double aux, const double* y, const double* off,

@@ -28,27 +28,12 @@
 #include "dense.h"
 #include "fitc.h"
 #include "kernels.h"
+#include "reduce.h"
 
 namespace gpb_amd {
 namespace {
 
 constexpr double kJitterMult = 1. + 1e-6;   // JITTER_MULT_IP_FITC_FSA (utils.h:39)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double block4_sum(double v, double* red) {
-  // v: wave-uniform value of each of the 4 waves; fixed order ((w0 + w1) + (w2 + w3))
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  const double s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
-}
 
 template <int COV>
 __global__ void __launch_bounds__(256) fitc_kmn_kernel(const double* __restrict__ X, const double* __restrict__ Z, int n,
@@ -598,17 +583,6 @@ __global__ void __launch_bounds__(256) kmeans_cmp_kernel(const double* __restric
   }
 }
 
-template <typename F>
-void dispatch_cov_fitc(int cov, F&& f) {
-  switch (cov) {
-    case kMatern05: f(std::integral_constant<int, kMatern05>{}); break;
-    case kMatern15: f(std::integral_constant<int, kMatern15>{}); break;
-    case kMatern25: f(std::integral_constant<int, kMatern25>{}); break;
-    case kGaussian: f(std::integral_constant<int, kGaussian>{}); break;
-    default: Fatal("unsupported covariance type %d", cov);
-  }
-}
-
 // closest_distance (GP_utils.cpp:190-201) on the host: the reference's arithmetic
 double host_dist(const double* x, const double* mu, int d) {
   double t = x[0] - mu[0];
@@ -746,7 +720,7 @@ void FitcSolver::Prior(int cov_type, double var, double phi, double* red) {
   const int n = n_, m = m_, ldm = ldm_, d = d_;
   kept_ = false;
   HIP_CHECK(hipMemsetAsync(info_.get(), 0, sizeof(int), stream_));
-  dispatch_cov_fitc(cov_type, [&](auto c) {
+  dispatch_cov(cov_type, [&](auto c) {
     constexpr int COV = decltype(c)::value;
     hipLaunchKernelGGL((fitc_kmn_kernel<COV>), dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, stream_, d_X_, dZ_.get(),
                        n, m, d, ldm, var, phi, Kmn_.get());
@@ -865,7 +839,7 @@ void FitcSolver::Eval(int cov_type, double var, double phi, const double* d_y, b
     hipLaunchKernelGGL(fitc_gemv_reduce_kernel, dim3((m + 3) / 4), dim3(256), 0, stream_, part_.get(), nbg, m, ldm, a);
     const int nb4 = (n + 3) / 4;
     const double delta = var * kJitterMult - var;
-    dispatch_cov_fitc(cov_type, [&](auto c) {
+    dispatch_cov(cov_type, [&](auto c) {
       hipLaunchKernelGGL((fitc_grad_kernel<decltype(c)::value>), dim3(nb4), dim3(256), 0, stream_, d_X_, dZ_.get(), n, m,
                          d, ldm, var, phi, delta, Kmn_.get(), A_.get(), Kd_.get(), V_.get(), a, dvec, yaux, part_.get());
     });
@@ -920,7 +894,7 @@ void FitcSolver::Predict(int cov_type, double var, double phi, const double* d_y
   const double* w = yaux + n + ldm;
   DevBuf<double> dXp((size_t)np * d), Kmp((size_t)ldm * np), out((size_t)3 * np);
   HIP_CHECK(hipMemcpyAsync(dXp.get(), Xp, sizeof(double) * np * d, hipMemcpyHostToDevice, stream_));
-  dispatch_cov_fitc(cov_type, [&](auto c) {
+  dispatch_cov(cov_type, [&](auto c) {
     hipLaunchKernelGGL((fitc_kmn_kernel<decltype(c)::value>), dim3((m + 63) / 64, (np + 3) / 4), dim3(256), 0, stream_,
                        dXp.get(), dZ_.get(), np, m, d, ldm, var, phi, Kmp.get());
   });
@@ -1067,7 +1041,7 @@ void fitc_mm_terms(hipStream_t s, const double* Kinv, const double* Winv, const 
 
 void fitc_kmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm, double var,
               double phi, double* Kmn) {
-  dispatch_cov_fitc(cov_type, [&](auto c) {
+  dispatch_cov(cov_type, [&](auto c) {
     hipLaunchKernelGGL((fitc_kmn_kernel<decltype(c)::value>), dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, s, X, Z,
                        n, m, d, ldm, var, phi, Kmn);
   });

@@ -27,14 +27,11 @@
 
 namespace gpb_amd {
 
-class FitcLaplace : public LatentSolverBase {
+class FitcLaplace : public ObsLaplaceBase {
  public:
   FitcLaplace(FitcSolver* fitc, hipStream_t stream);
   ~FitcLaplace() override;
 
-  void SetY(const double* y) override;
-  void SetOffset(const double* off) override;
-  void GetMode(double* mode) override;
   // trafo = (sigma1^2, phi); aux: the shape of likelihood 'gamma' (want_aux_grad: its gradient appended to grad).
   // grad = [d/dlog sigma1^2, d/dlog phi] of the negative approximate marginal log-likelihood;
   // grad_f (nullable, host n): the gradient wrt the fixed effects F (booster).
@@ -64,14 +61,12 @@ class FitcLaplace : public LatentSolverBase {
   void Woodbury(const double* s, double* logdet_dev, bool full_inverse);
 
   FitcSolver* F_;
-  hipStream_t s_;
-  int n_, m_, ldm_;
-  bool y_set_ = false, has_off_ = false, prev_valid_ = false, evaluated_ = false;
+  int m_, ldm_;
+  bool prev_valid_ = false, evaluated_ = false;
   double cached_obj_ = 0.;     // -1/2 a^T mode + log p(y | mode + F) at the current mode
   double aux_ = 1.;            // the likelihood's auxiliary parameter (gamma: shape)
-  DevBuf<double> y_, off_, mode_, a_, mode_prev_, a_prev_, mode_upd_, a_upd_, d1_, w_, wdw_, dw_, rhs_, sig_, c_, z_;
+  DevBuf<double> a_, mode_prev_, a_prev_, mode_upd_, a_upd_, d1_, w_, wdw_, dw_, rhs_, sig_, c_, z_;
   DevBuf<double> sgv_, sgr_, dmll_, sdiag_, auxrec_;
-  double sum_log_y_ = 0.;
   DevBuf<double> mv_;          // m-vectors: 18 x ldm (fitc_laplace.hip kMv)
   DevBuf<double> part_, red_;  // partials and reduced scalars
   double* h_red_ = nullptr;    // pinned

@@ -3,7 +3,8 @@
 //   d1, W, DW = (W d + 1)^-1, rhs = W mode + d1          one thread per observation
 //   M = K_mm,s + K diag(W DW) K^T                        split-K MFMA Gram (2 m^2 n) + POTRF / TRTRI
 //   Sigma rhs, K^T M^-1 K (W DW Sigma rhs), Sigma a      five matrix-vector passes over K
-//   Armijo line search on -1/2 a^T mode + sum log p(y | mode + F)
+//   Armijo line search on -1/2 a^T mode + sum log p(y | mode + F)   newton_line_search (laplace_newton.h) on the
+//                                                           shared trial / slope kernels (laplace_kernels.h)
 // and for the gradient A = K_mm,s^-1 K, G = M^-1 K, dK_mm A (three MFMA GEMMs) and three fused passes
 // per observation (the range derivative of K recomputed from the coordinates).
 // Solves with K_mm,s and M apply the inverse Cholesky factor twice (L^-T (L^-1 x), fitc_chol_solve) rather
@@ -20,8 +21,10 @@
 #include "dense.h"
 #include "fitc_laplace.h"
 #include "kernels.h"
+#include "laplace_kernels.h"
 #include "lik_device.h"
 #include "lik_test.h"
+#include "reduce.h"
 
 namespace gpb_amd {
 namespace {
@@ -38,35 +41,6 @@ struct OutVec4 {
   double* p[4];
 };
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-order sum of the 4 waves' (wave-uniform) values of a 256-thread block
-__device__ __forceinline__ double block4(double v, double* red) {
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  const double s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
-}
-
-// fixed-order sum over the 256 threads of a block (per-thread values), written by thread 0
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = kT / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  const double s = red[0];
-  __syncthreads();
-  return s;
-}
-
 // d_i = sigma1^2 jitter - |V[:, i]|^2 (re_model_template.h:7358-7377, no nugget); one wave per observation
 __global__ void __launch_bounds__(kT) fl_diag_kernel(const double* __restrict__ V, int n, int m, int ldm, double dvar,
                                                     double* __restrict__ dvec) {
@@ -78,7 +52,7 @@ __global__ void __launch_bounds__(kT) fl_diag_kernel(const double* __restrict__ 
     const double v = V[(size_t)j + (size_t)i * ldm];
     s += v * v;
   }
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) dvec[i] = dvar - s;
 }
 
@@ -148,7 +122,7 @@ __global__ void __launch_bounds__(kT) fl_gemv_reduce_kernel(const double* __rest
   const int v = q / m, j = q - v * m;
   double s = 0.;
   for (int b = lane; b < nb; b += 64) s += part[((size_t)b * nv + v) * ldm + j];
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) out.p[v][j] = s;
 }
 
@@ -165,8 +139,8 @@ __global__ void __launch_bounds__(kT) fl_coldot_kernel(const double* __restrict_
     s += v ? x * v[j] : x * x;
     if (v2) s2 += x * v2[j];
   }
-  s = wsum(s);
-  if (v2) s2 = wsum(s2);
+  s = wave_sum(s);
+  if (v2) s2 = wave_sum(s2);
   if (lane == 0) {
     c[i] = s;
     if (v2) c2[i] = s2;
@@ -196,52 +170,6 @@ __global__ void __launch_bounds__(kT) fl_aupd_kernel(int n, const double* __rest
   aupd[i] = rhs[i] + (-t);
 }
 
-// Armijo slope: sum_i dir_i (aupd_i - a_i + W_i dir_i), dir = mupd - mode (likelihoods.h:3166-3169)
-__global__ void __launch_bounds__(kT) fl_gdd_kernel(int n, const double* __restrict__ mode,
-                                                   const double* __restrict__ a, const double* __restrict__ mupd,
-                                                   const double* __restrict__ aupd, const double* __restrict__ w,
-                                                   double* __restrict__ part) {
-  __shared__ double red[kT];
-  double acc = 0.;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
-    const double dir = mupd[i] - mode[i];
-    acc += dir * (aupd[i] - a[i] + w[i] * dir);
-  }
-  const double s = block_sum(acc, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// one line-search trial (likelihoods.h:3171-3190): the new state mixed at learning rate lam (lam = 1:
-// the update itself), partials of [a^T mode, sum log p(y | mode + F)]
-__global__ void __launch_bounds__(kT) fl_trial_kernel(int n, int lik, double aux, double lam, const double* __restrict__ mode,
-                                                     const double* __restrict__ a, const double* __restrict__ mupd,
-                                                     const double* __restrict__ aupd, const double* __restrict__ y,
-                                                     const double* __restrict__ off, double* __restrict__ mnew,
-                                                     double* __restrict__ anew, double* __restrict__ part) {
-  __shared__ double red[kT];
-  double sq = 0., sl = 0.;
-  for (int i = blockIdx.x * kT + threadIdx.x; i < n; i += gridDim.x * kT) {
-    double mi, ai;
-    if (lam == 1.) {
-      mi = mupd[i];
-      ai = aupd[i];
-    } else {
-      ai = (1. - lam) * a[i] + lam * aupd[i];
-      mi = (1. - lam) * mode[i] + lam * mupd[i];
-    }
-    mnew[i] = mi;
-    anew[i] = ai;
-    sq += ai * mi;
-    sl += lik_loglik(lik, aux, y[i], off ? mi + off[i] : mi);
-  }
-  const double s0 = block_sum(sq, red);
-  const double s1 = block_sum(sl, red);
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = s0;
-    part[2 * blockIdx.x + 1] = s1;
-  }
-}
-
 // after the mode finding (likelihoods.h:3200-3232): d1, W at the mode, DW = (W d + 1)^-1,
 // dpwi = (d + W^-1)^-1; partials of [sum log dpwi, sum log W, #(W == 0)]
 __global__ void __launch_bounds__(kT) fl_final_kernel(int n, int lik, double aux, const double* __restrict__ y,
@@ -265,9 +193,9 @@ __global__ void __launch_bounds__(kT) fl_final_kernel(int n, int lik, double aux
     s1 += log(wi);
     s2 += wi == 0. ? 1. : 0.;
   }
-  const double a0 = block_sum(s0, red);
-  const double a1 = block_sum(s1, red);
-  const double a2 = block_sum(s2, red);
+  const double a0 = block_tree_sum(s0, red);
+  const double a1 = block_tree_sum(s1, red);
+  const double a2 = block_tree_sum(s2, red);
   if (threadIdx.x == 0) {
     part[3 * blockIdx.x] = a0;
     part[3 * blockIdx.x + 1] = a1;
@@ -358,16 +286,16 @@ __global__ void __launch_bounds__(kT) fl_grad_p1_kernel(
       hur += dk * uj + av * (u2r[j] - u3r[j]);
     }
   }
-  c1v = wsum(c1v);
-  sa2 = wsum(sa2);
-  c1r = wsum(c1r);
-  c2r = wsum(c2r);
-  f = wsum(f);
-  er = wsum(er);
-  hbv = wsum(hbv);
-  hbr = wsum(hbr);
-  huv = wsum(huv);
-  hur = wsum(hur);
+  c1v = wave_sum(c1v);
+  sa2 = wave_sum(sa2);
+  c1r = wave_sum(c1r);
+  c2r = wave_sum(c2r);
+  f = wave_sum(f);
+  er = wave_sum(er);
+  hbv = wave_sum(hbv);
+  hbr = wave_sum(hbr);
+  huv = wave_sum(huv);
+  hur = wave_sum(hur);
   double ev = 0., erng = 0.;
   if (i < n) {
     const double fdv = var - 2. * c1v + (c1v - delta * sa2);
@@ -385,8 +313,8 @@ __global__ void __launch_bounds__(kT) fl_grad_p1_kernel(
       sdiag[i] = sw;
     }
   }
-  ev = block4(ev, red);
-  erng = block4(erng, red);
+  ev = block4_sum(ev, red);
+  erng = block4_sum(erng, red);
   if (threadIdx.x == 0) {
     part[2 * (size_t)blockIdx.x] = ev;
     part[2 * (size_t)blockIdx.x + 1] = erng;
@@ -410,16 +338,16 @@ __global__ void __launch_bounds__(kT) fl_grad_p3_kernel(const double* __restrict
       kv += x * vv[j];
       kr += x * vr[j];
     }
-  kv = wsum(kv);
-  kr = wsum(kr);
+  kv = wave_sum(kv);
+  kr = wave_sum(kr);
   double iv = 0., ir = 0.;
   if (i < n) {
     const double wi_inv = 1. / w[i], p = dpwi[i], dm = dmll[i];
     iv = dm * (wi_inv * (p * sgv[i] - p * kv));
     ir = dm * (wi_inv * (p * sgr[i] - p * kr));
   }
-  iv = block4(iv, red);
-  ir = block4(ir, red);
+  iv = block4_sum(iv, red);
+  ir = block4_sum(ir, red);
   if (threadIdx.x == 0) {
     part[2 * (size_t)blockIdx.x] = iv;
     part[2 * (size_t)blockIdx.x + 1] = ir;
@@ -457,12 +385,6 @@ __global__ void __launch_bounds__(kT) fl_aux_rec_kernel(int n, const double* __r
   rec[3 * (size_t)i + 2] = d1[i] * sv;
 }
 
-__global__ void __launch_bounds__(kT) fl_mul_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
-                                                   double* __restrict__ out) {
-  const int i = blockIdx.x * kT + threadIdx.x;
-  if (i < n) out[i] = a[i] * b[i];
-}
-
 // prediction correction per matched pair (prediction point p, training point o), CalcPredFITC_FSA
 // re_model_template.h:10681 and likelihoods.h:7196-7199: corr = sigma1^2 - (L^-1 K_mp)_p . (L^-1 K_mn)_o;
 // Maux[:, p] -= K_mn[:, o] (d_o + W_o^-1)^-1 corr (one wave per pair; a prediction point has at most one pair)
@@ -477,31 +399,17 @@ __global__ void __launch_bounds__(64) fl_pred_corr_kernel(const int* __restrict_
   const int lane = threadIdx.x;
   double s = 0.;
   for (int j = lane; j < m; j += 64) s += Vp[(size_t)j + (size_t)p * ldm] * V[(size_t)j + (size_t)o * ldm];
-  s = wsum(s);
+  s = wave_sum(s);
   const double c = sii - s;
   const double f = dpwi[o] * c;
   for (int j = lane; j < m; j += 64) Maux[(size_t)j + (size_t)p * ldm] -= K[(size_t)j + (size_t)o * ldm] * f;
   if (lane == 0) corr[q] = c;
 }
 
-template <typename F>
-void dispatch_cov(int cov, F&& f) {
-  switch (cov) {
-    case kMatern05: f(std::integral_constant<int, kMatern05>{}); break;
-    case kMatern15: f(std::integral_constant<int, kMatern15>{}); break;
-    case kMatern25: f(std::integral_constant<int, kMatern25>{}); break;
-    case kGaussian: f(std::integral_constant<int, kGaussian>{}); break;
-    default: Fatal("unsupported covariance type %d", cov);
-  }
-}
-
-inline int nb_thread(int n) { return std::max(1, (n + kT - 1) / kT); }
-inline int nb_red(int n) { return std::min(1024, nb_thread(n)); }
-
 }  // namespace
 
 FitcLaplace::FitcLaplace(FitcSolver* fitc, hipStream_t stream)
-    : F_(fitc), s_(stream), n_(fitc->n_), m_(fitc->m_), ldm_(fitc->ldm_) {
+    : ObsLaplaceBase(fitc->n_, stream), F_(fitc), m_(fitc->m_), ldm_(fitc->ldm_) {
   const int n = n_, ldm = ldm_;
   for (DevBuf<double>* b : {&y_, &off_, &mode_, &a_, &mode_prev_, &a_prev_, &mode_upd_, &a_upd_, &d1_, &w_, &wdw_, &dw_,
                             &rhs_, &sig_, &c_, &z_, &sgv_, &sgr_, &dmll_, &sdiag_})
@@ -510,7 +418,8 @@ FitcLaplace::FitcLaplace(FitcSolver* fitc, hipStream_t stream)
   mv_.alloc((size_t)kMv * ldm);
   HIP_CHECK(hipMemsetAsync(mv_.get(), 0, sizeof(double) * kMv * ldm, s_));
   const size_t nbg = (size_t)(n + kChunk - 1) / kChunk;
-  part_.alloc(std::max<size_t>({nbg * 4 * ldm, (size_t)((n + 3) / 4) * 2, (size_t)nb_red(n) * 3, (size_t)6 * ((m_ + 3) / 4)}));
+  part_.alloc(std::max<size_t>({nbg * 4 * ldm, (size_t)((n + 3) / 4) * 2, (size_t)laplace_blocks(n) * 3,
+                                (size_t)6 * ((m_ + 3) / 4)}));
   red_.alloc(32);
   HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_red_), 32 * sizeof(double), hipHostMallocDefault));
   HIP_CHECK(hipMemsetAsync(mode_.get(), 0, sizeof(double) * n, s_));
@@ -520,27 +429,6 @@ FitcLaplace::FitcLaplace(FitcSolver* fitc, hipStream_t stream)
 
 FitcLaplace::~FitcLaplace() {
   if (h_red_) (void)hipHostFree(h_red_);
-}
-
-void FitcLaplace::SetY(const double* y) {
-  sum_log_y_ = 0.;   // aux_log_normalizing_constant_ of likelihood 'gamma' (likelihoods.h:8181-8191)
-  for (int i = 0; i < n_; ++i) sum_log_y_ += y[i] > 0. ? std::log(y[i]) : 0.;
-  HIP_CHECK(hipMemcpyAsync(y_.get(), y, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-  HIP_CHECK(hipStreamSynchronize(s_));
-  y_set_ = true;
-}
-
-void FitcLaplace::SetOffset(const double* off) {
-  has_off_ = off != nullptr;
-  if (has_off_) {
-    HIP_CHECK(hipMemcpyAsync(off_.get(), off, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-    HIP_CHECK(hipStreamSynchronize(s_));
-  }
-}
-
-void FitcLaplace::GetMode(double* mode) {
-  HIP_CHECK(hipMemcpyAsync(mode, mode_.get(), sizeof(double) * n_, hipMemcpyDeviceToHost, s_));
-  HIP_CHECK(hipStreamSynchronize(s_));
 }
 
 void FitcLaplace::ResetModeToPrevious() {
@@ -577,7 +465,7 @@ void FitcLaplace::SigmaApply(const double* x, double* out) {
   hipLaunchKernelGGL(fl_coldot_kernel, dim3((n_ + 3) / 4), dim3(kT), 0, s_, F_->Kmn_.get(), t2, nullptr, n_, m_, ldm_,
                      c_.get(), nullptr);
   const double* dvec = F_->vec_.get();
-  hipLaunchKernelGGL(fl_sigma_kernel, dim3(nb_thread(n_)), dim3(kT), 0, s_, n_, c_.get(), dvec, x, nullptr, out, nullptr);
+  hipLaunchKernelGGL(fl_sigma_kernel, dim3(laplace_grid(n_)), dim3(kT), 0, s_, n_, c_.get(), dvec, x, nullptr, out, nullptr);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -624,12 +512,10 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
     HIP_CHECK(hipStreamSynchronize(s_));
     return info != 0;
   };
-  const int nbr = nb_red(n);
+  const int nbr = laplace_blocks(n);
   // objective -1/2 a^T mode + log p(y | mode + F) of the state (mode_, a_)
   auto objective = [&](double lam, const double* mu, const double* au, double* mnew, double* anew) {
-    hipLaunchKernelGGL(fl_trial_kernel, dim3(nbr), dim3(kT), 0, s_, n, lik, aux_, lam, mode_.get(), a_.get(), mu, au, y_.get(),
-                       off, mnew, anew, part_.get());
-    HIP_CHECK(hipGetLastError());
+    launch_laplace_trial(n, lik, aux_, lam, mode_.get(), a_.get(), mu, au, y_.get(), off, mnew, anew, part_.get(), s_);
     launch_sum_blocks(part_.get(), nbr, 2, red + 4, s_);
     HIP_CHECK(hipMemcpyAsync(h_red_ + 4, red + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, s_));
     HIP_CHECK(hipStreamSynchronize(s_));
@@ -649,29 +535,27 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
     SigmaApply(a_.get(), mode_.get());
   }
   double* logdet_M = red + 1;
-  int it = 0;
   if (start != ModeStart::kKeep || !evaluated_) {
     double obj = objective(1., mode_.get(), a_.get(), mode_upd_.get(), a_upd_.get());
-    const int maxit = 1000;                                // maxit_mode_newton_ (likelihoods.h:12721)
-    const double delta = cfg.delta_conv_mode_finding;       // :12723
-    bool terminate = false, has_nan = false;
+    const double delta = cfg.delta_conv_mode_finding;       // likelihoods.h:12723
+    bool has_nan = false;
     double* vaux = mv_.get() + 2 * (size_t)ldm;
     double* vaux2 = mv_.get() + 3 * (size_t)ldm;
-    for (it = 0; it < maxit; ++it) {
+    for (int it = 0; it < kMaxItModeNewton; ++it) {
       // information changes in every step for the supported likelihoods (information_changes_during_mode_finding_)
-      hipLaunchKernelGGL(fl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(), dvec, 1,
-                         d1_.get(), w_.get(), wdw_.get(), dw_.get(), rhs_.get());
+      hipLaunchKernelGGL(fl_prep_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(), dvec,
+                         1, d1_.get(), w_.get(), wdw_.get(), dw_.get(), rhs_.get());
       HIP_CHECK(hipGetLastError());
       Woodbury(wdw_.get(), logdet_M, false);
       // Sigma rhs, vaux = K (W DW Sigma rhs), vaux2 = M^-1 vaux, K^T vaux2 (likelihoods.h:3152-3157)
       SigmaApply(rhs_.get(), sig_.get());
-      hipLaunchKernelGGL(fl_mul_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, wdw_.get(), sig_.get(), z_.get());
+      launch_laplace_mul(n, wdw_.get(), sig_.get(), z_.get(), s_);
       const double* zp = z_.get();
       Gemv(F.Kmn_.get(), 1, &zp, &vaux);
       fitc_chol_solve(s_, F.Wi_.get(), F.WiT_.get(), vaux, m, ldm, mv_.get() + 4 * (size_t)ldm, vaux2);
       hipLaunchKernelGGL(fl_coldot_kernel, dim3((n + 3) / 4), dim3(kT), 0, s_, F.Kmn_.get(), vaux2, nullptr, n, m, ldm,
                          c_.get(), nullptr);
-      hipLaunchKernelGGL(fl_aupd_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, rhs_.get(), w_.get(), dw_.get(),
+      hipLaunchKernelGGL(fl_aupd_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, rhs_.get(), w_.get(), dw_.get(),
                          sig_.get(), c_.get(), a_upd_.get());
       HIP_CHECK(hipGetLastError());
       SigmaApply(a_upd_.get(), mode_upd_.get());   // mode_update = Sigma SigmaI_mode_update
@@ -679,37 +563,23 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
         has_nan = true;
         break;
       }
-      hipLaunchKernelGGL(fl_gdd_kernel, dim3(nbr), dim3(kT), 0, s_, n, mode_.get(), a_.get(), mode_upd_.get(),
-                         a_upd_.get(), w_.get(), part_.get());
+      launch_laplace_gdd(n, mode_.get(), a_.get(), mode_upd_.get(), a_upd_.get(), w_.get(), part_.get(), s_);
       launch_sum_blocks(part_.get(), nbr, 1, red + 6, s_);
       HIP_CHECK(hipMemcpyAsync(h_red_ + 6, red + 6, sizeof(double), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
       const double gdd = h_red_[6];
-      // backtracking (:3171-3192); the last trial is kept when none is accepted
-      double lam = 1., obj_new = obj;
-      for (int ih = 0; ih < 20; ++ih) {   // max_number_lr_shrinkage_steps_newton_ (:12725)
-        obj_new = objective(lam, mode_upd_.get(), a_upd_.get(), sig_.get(), c_.get());
-        if (obj_new < obj + 1e-4 * lam * gdd || std::isnan(obj_new) || std::isinf(obj_new)) lam *= 0.5;   // c_armijo_ 1e-4
-        else break;
-      }
+      // backtracking (:3171-3192) and the convergence rule
+      const LineSearchResult ls = newton_line_search(it, obj, gdd, delta, kMaxShrinkNewton, [&](double lam, int) {
+        return objective(lam, mode_upd_.get(), a_upd_.get(), sig_.get(), c_.get());
+      });
       std::swap(mode_, sig_);   // mode_ = mode_new, SigmaI_mode_ = SigmaI_mode_new
       std::swap(a_, c_);
-      // CheckConvergenceModeFinding (:11820-11870)
-      if (std::isnan(obj_new) || std::isinf(obj_new)) {
-        has_nan = true;
-        obj = obj_new;
-        break;
-      }
-      if (it == 0) terminate = std::abs(obj_new - obj) < delta * std::abs(obj);
-      else terminate = (obj_new - obj) < delta * std::abs(obj);
-      obj = obj_new;
-      if (terminate) {
-        ++it;
-        break;
-      }
+      res.newton_its = it + 1;
+      obj = ls.obj_new;
+      has_nan = ls.nan;
+      if (ls.nan || ls.terminate) break;
     }
     if (has_nan) throw LatentNan("NaN or Inf occurred in the FITC mode finding");
-    res.newton_its = it;
     cached_obj_ = obj;
   }
   evaluated_ = true;
@@ -771,8 +641,8 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
     HIP_CHECK(hipGetLastError());
     launch_sum_blocks(part1, nb4, 2, red + 18, s_);
     // rhs_k = K (p o sg_k), vaux_k = M^-1 rhs_k
-    hipLaunchKernelGGL(fl_mul_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, wdw_.get(), sgv_.get(), z_.get());
-    hipLaunchKernelGGL(fl_mul_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, wdw_.get(), sgr_.get(), rhs_.get());
+    launch_laplace_mul(n, wdw_.get(), sgv_.get(), z_.get(), s_);
+    launch_laplace_mul(n, wdw_.get(), sgr_.get(), rhs_.get(), s_);
     const double* zx[2] = {z_.get(), rhs_.get()};
     double* zo[2] = {rv, rr};
     Gemv(F.Kmn_.get(), 2, zx, zo);
@@ -785,7 +655,7 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
     if (grad_f != nullptr || want_aux) {   // kq = K^T M^-1 K (DW o dmll) for (Sigma^-1 + W)^-1 dmll
       double* q = mv + 16 * (size_t)ldm;
       double* q2 = mv + 17 * (size_t)ldm;
-      hipLaunchKernelGGL(fl_mul_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, dw_.get(), dmll_.get(), z_.get());
+      launch_laplace_mul(n, dw_.get(), dmll_.get(), z_.get(), s_);
       const double* zp = z_.get();
       Gemv(F.Kmn_.get(), 1, &zp, &q);
       fitc_chol_solve(s_, F.Wi_.get(), F.WiT_.get(), q, m, ldm, mv + 4 * (size_t)ldm, q2);
@@ -793,13 +663,13 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
                          nullptr);
     }
     if (want_aux) {
-      hipLaunchKernelGGL(fl_aux_rec_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, y_.get(), off, mode_.get(), w_.get(),
+      hipLaunchKernelGGL(fl_aux_rec_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, y_.get(), off, mode_.get(), w_.get(),
                          sdiag_.get(), d1_.get(), dmll_.get(), dw_.get(), c_.get(), auxrec_.get());
       HIP_CHECK(hipGetLastError());
       launch_sum_blocks(auxrec_.get(), n, 3, red + 24, s_);
     }
     if (grad_f != nullptr) {
-      hipLaunchKernelGGL(fl_gradf_kernel, dim3(nb_thread(n)), dim3(kT), 0, s_, n, d1_.get(), dmll_.get(), w_.get(),
+      hipLaunchKernelGGL(fl_gradf_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s_, n, d1_.get(), dmll_.get(), w_.get(),
                          dw_.get(), c_.get(), z_.get());
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipMemcpyAsync(grad_f, z_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
@@ -813,9 +683,7 @@ LatentResult FitcLaplace::Eval(int cov_type, int lik, const double* trafo, doubl
     if (want_aux) {   // gamma shape on the log scale (likelihoods.h:10514-10524 + the two trace terms)
       HIP_CHECK(hipMemcpyAsync(h_red_ + 24, red + 24, 3 * sizeof(double), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
-      const double a = aux_;
-      const double neg = a * (h_red_[24] - n * (std::log(a) + 1. - digamma_asa103(a)) - sum_log_y_);
-      res.grad.push_back(neg + 0.5 * h_red_[25] + h_red_[26]);
+      res.grad.push_back(gamma_shape_grad(aux_, n, h_red_[24], h_red_[25], h_red_[26], sum_log_y_));
     }
   }
   HIP_CHECK(hipEventRecord(e1, s_));
@@ -918,29 +786,17 @@ void FitcLaplace::Predict(int cov_type, double var, double phi, const double* Xp
   }
 }
 
-// ---- test launchers (lik_test.h): the launches of FindMode on nb_thread(n) / nb_red(n) blocks and their block sums
-int test_fl_blocks(int n) { return nb_red(n); }
-
+// ---- test launchers (lik_test.h): the launches of FindMode on laplace_grid(n) / laplace_blocks(n) blocks and their sums
 void test_fl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* dvec,
                   int w_update, double* d1, double* w, double* wdw, double* DW, double* rhs, hipStream_t s) {
-  hipLaunchKernelGGL(fl_prep_kernel, dim3(nb_thread(n)), dim3(kT), 0, s, n, lik, aux, y, off, mode, dvec, w_update, d1, w,
+  hipLaunchKernelGGL(fl_prep_kernel, dim3(laplace_grid(n)), dim3(kT), 0, s, n, lik, aux, y, off, mode, dvec, w_update, d1, w,
                      wdw, DW, rhs);
   HIP_CHECK(hipGetLastError());
 }
 
-void test_fl_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
-                   const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
-                   double* sums, hipStream_t s) {
-  const int nbr = nb_red(n);
-  hipLaunchKernelGGL(fl_trial_kernel, dim3(nbr), dim3(kT), 0, s, n, lik, aux, lam, mode, a, mupd, aupd, y, off, mnew, anew,
-                     part);
-  HIP_CHECK(hipGetLastError());
-  launch_sum_blocks(part, nbr, 2, sums, s);
-}
-
 void test_fl_final(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* dvec,
                    double* d1, double* w, double* DW, double* dpwi, double* part, double* sums, hipStream_t s) {
-  const int nbr = nb_red(n);
+  const int nbr = laplace_blocks(n);
   hipLaunchKernelGGL(fl_final_kernel, dim3(nbr), dim3(kT), 0, s, n, lik, aux, y, off, mode, dvec, d1, w, DW, dpwi, part);
   HIP_CHECK(hipGetLastError());
   launch_sum_blocks(part, nbr, 3, sums, s);

@@ -8,7 +8,7 @@
 //   CalcGradNegMargLikelihoodLaplaceApproxGroupedRE, Cholesky branch     :3634-3740
 //   CalcGradNegMargLikelihoodLaplaceApproxOnlyOneGroupedRE...            :3761-3854
 // become
-//   mode:  Newton steps A delta = Z^T d1 - Sigma^-1 b with Armijo halving (c = 1e-4, at most 20 halvings) on
+//   mode:  Newton steps A delta = Z^T d1 - Sigma^-1 b with Armijo halving (newton_line_search, laplace_newton.h) on
 //          the objective ll(eta) - b^T Sigma^-1 b / 2, stopped on its relative change;
 //   nll  = -(objective - log|A| / 2 + sum log diag(Sigma^-1) / 2);
 //   grad (wrt log sigma_j^2) = -b_j^T b_j / (2 sigma_j^2) + sum_i W_i q_ij / 2 + v_j^T (Z^T d1)_j, where

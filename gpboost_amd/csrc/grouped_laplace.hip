@@ -20,9 +20,6 @@ namespace {
 constexpr int kMaxBlocks = 1024;      // blocks of an observation pass (grid-stride; fixed by n -> fixed sum order)
 constexpr int kShortLen = 32;         // destinations of at most this many observations: one thread each
 constexpr int kChunkLen = 512;        // chunk of a longer list: one wave, 8 observations per lane
-constexpr double kCArmijo = 1e-4;     // c_armijo_ (likelihoods.h:12737)
-constexpr int kMaxItNewton = 1000;    // maxit_mode_newton_ (:12721)
-constexpr int kMaxShrink = 20;        // max_number_lr_shrinkage_steps_newton_ (:12725)
 constexpr int kRed = 64;              // scalar slots
 
 struct EffArgs {   // per-effect constants, by value
@@ -489,7 +486,7 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
 
   // ---- mode finding (likelihoods.h:1995-2088 / 2224-2274)
   double mll = Objective(d_mode_.get(), aux, ea.sigi);
-  const int newton_its = start == Start::kKeep ? 0 : kMaxItNewton;
+  const int newton_its = start == Start::kKeep ? 0 : kMaxItModeNewton;
   for (int it = 0; it < newton_its; ++it) {
     if (timing) HIP_CHECK(hipEventRecord(ev_[2], s_));
     Deriv(d_mode_.get(), aux, false);
@@ -504,22 +501,16 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
     HIP_CHECK(hipStreamSynchronize(s_));
     double gdd = 0.;   // grad_dot_direction (rhs = gradient of the objective)
     for (int k = 0; k < K; ++k) gdd += h_red_[16 + k];
-    double lr = 1., mll_new = mll;
-    for (int ih = 0; ih < kMaxShrink; ++ih) {
+    const LineSearchResult ls = newton_line_search(it, mll, gdd, delta_conv, kMaxShrinkNewton, [&](double lr, int) {
       glp_vec_kernel<kVecAxpy><<<blocks_of(M), 256, 0, s_>>>(M, ea, lr, d_mode_.get(), d_upd_.get(), d_mode_new_.get());
-      mll_new = Objective(d_mode_new_.get(), aux, ea.sigi);
-      if (mll_new < mll + kCArmijo * lr * gdd || std::isnan(mll_new) || std::isinf(mll_new)) lr *= 0.5;
-      else break;
-    }
+      return Objective(d_mode_new_.get(), aux, ea.sigi);
+    });
     std::swap(d_mode_, d_mode_new_);
     if (timing) HIP_CHECK(hipEventRecord(ev_[3], s_));
     res.newton_its = it + 1;
-    if (std::isnan(mll_new) || std::isinf(mll_new)) return fail();
-    // CheckConvergenceModeFinding (:11820-11870)
-    const bool term = it == 0 ? std::fabs(mll_new - mll) < delta_conv * std::fabs(mll)
-                              : (mll_new - mll) < delta_conv * std::fabs(mll);
-    mll = mll_new;
-    if (term) break;
+    if (ls.nan) return fail();
+    mll = ls.obj_new;
+    if (ls.terminate) break;
   }
   // ---- derivatives, information and factor at the mode; the determinant (:2089-2193 / 2275-2289)
   Deriv(d_mode_.get(), aux, want_grad);

@@ -1,4 +1,5 @@
-// LatentVecchia implementation: host orchestration of the iterative latent-Vecchia path.
+// LatentVecchia implementation: host orchestration of the iterative latent-Vecchia path. NewtonPrep and
+// LineSearchAndCheck (newton_line_search, laplace_newton.h) serve its three evaluations (Eval, EvalPivChol, EvalChol).
 #include "latent.h"
 
 #include <algorithm>
@@ -16,7 +17,6 @@ namespace gpb_amd {
 
 namespace {
 constexpr double kJitterMultVecchia = 1. + 1e-10;   // JITTER_MULT_VECCHIA (utils.h)
-constexpr double kCArmijo = 1e-4;                   // c_armijo_ (likelihoods.h:12737)
 // ZERO_RHS_CG_THRESHOLD = 1e-100 on sum|rhs| (utils.h:45, CG_utils.cpp:42-45); tested here as
 // sum rhs^2 < 1e-200, which is implied by it and differs only below ~1e-100 magnitudes.
 constexpr double kZeroRhsSq = 1e-200;
@@ -746,6 +746,36 @@ void LatentVecchia::Scalars(const ScalarArgs& a, double* out) {
   out[kSqLogLik] += loglik_const_;   // log_normalizing_constant_ (likelihoods.h:8638)
 }
 
+void LatentVecchia::NewtonPrep(int lik, double aux, int w_update, double* rhs, double* dw, double* sdw) {
+  NewtonPrepArgs np{};
+  np.n = n_; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
+  np.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
+  np.obs = Obs();
+  np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get(); np.W_update = w_update;
+  np.rhs = rhs; np.dw = dw; np.sdw = sdw;
+  launch_newton_prep(np, s_);
+}
+
+bool LatentVecchia::LineSearchAndCheck(int it, double gdd, int max_shrink, double delta, ScalarArgs& sa, double& mll,
+                                       LatentResult& res) {
+  const int n = n_;
+  const bool cap = sa.lik == kLikPoisson || sa.lik == kLikGamma;   // cap_change_mode_newton_ (likelihoods.h:481-490)
+  const LineSearchResult ls = newton_line_search(it, mll, gdd, delta, max_shrink, [&](double lr, int ih) {
+    if (ih == 0) launch_copy(n, d_mode_upd_.get(), d_mode_new_.get(), s_);
+    else launch_axpby(n, 1. - lr, d_mode_.get(), lr, d_mode_upd_.get(), d_mode_new_.get(), s_);
+    if (cap) launch_cap_mode_change(n, d_mode_.get(), d_mode_new_.get(), s_);
+    sa.mode = d_mode_new_.get();
+    double sc[kLatentScalars];
+    Scalars(sa, sc);
+    return sc[kSqLogLik] - 0.5 * sc[kSqQuad];
+  });
+  std::swap(d_mode_, d_mode_new_);
+  res.newton_its = it + 1;
+  if (ls.nan) throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
+  mll = ls.obj_new;
+  return ls.terminate;
+}
+
 // Spin until the device's stopping check `seq` has landed in the host-coherent words (it is
 // written last, after a system-scope fence). A stream that drained without it is an error.
 void LatentVecchia::WaitCtl(int seq, int* out) {
@@ -898,13 +928,8 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
 
   Block& b1 = GetBlock(0, 1, std::max(cfg.cg_max_num_it, 1));
   if (std::getenv("GPBOOST_AMD_BENCH_PRECOND")) {   // diagnostics: preconditioner cost alone
-    NewtonPrepArgs np{};
-    np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
-    np.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
-    np.obs = Obs();
-    np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get(); np.W_update = 1; np.dw = d_dw_.get();
     HIP_CHECK(hipMemsetAsync(d_mode_.get(), 0, sizeof(double) * n, s_));
-    launch_newton_prep(np, s_);
+    NewtonPrep(lik, aux, 1, nullptr, d_dw_.get(), nullptr);
     SetDiag();
     for (int tt : {1, t}) {
       Block& bb = GetBlock(tt == 1 ? 0 : 1, tt, std::max(cfg.cg_max_num_it, 1));
@@ -944,35 +969,15 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
     Fatal("The matrix D in the Vecchia approximation contains negative or zero values. "
           "This likely results from numerical instabilities ");
   double mll = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
-  const bool info_changes = !gauss;              // information_changes_during/after_mode_finding_
-  const int maxit = gauss ? 1 : 1000;            // maxit_mode_newton_ (likelihoods.h:255, 12721)
-  const int max_shrink = gauss ? 1 : 20;         // max_number_lr_shrinkage_steps_newton_ (:256, 12725)
+  const bool info_changes = !gauss;                      // information_changes_during/after_mode_finding_
+  const int maxit = gauss ? 1 : kMaxItModeNewton;        // gaussian: likelihoods.h:255
+  const int max_shrink = gauss ? 1 : kMaxShrinkNewton;   // :256
+  const double delta = cfg.delta_conv_mode_finding;      // :12723
   const int pmax_tri = std::max(1, std::min(cfg.cg_max_num_it_tridiag, n));
   const int cg_max = std::max(0, cfg.cg_max_num_it);
   Block* bslq = nullptr;
   int n_lead = 0;   // leading non-probe columns of the SLQ block
   PcgResult slq;
-  auto line_search_and_check = [&](int it, double gdd) -> bool {   // likelihoods.h:2967-2995, 11820-11870
-    double lr = 1., mll_new = mll;
-    for (int ih = 0; ih < max_shrink; ++ih) {
-      if (ih == 0) launch_copy(n, d_mode_upd_.get(), d_mode_new_.get(), s_);
-      else launch_axpby(n, 1. - lr, d_mode_.get(), lr, d_mode_upd_.get(), d_mode_new_.get(), s_);
-      if (lik == kLikPoisson || lik == kLikGamma) launch_cap_mode_change(n, d_mode_.get(), d_mode_new_.get(), s_);
-      sa.mode = d_mode_new_.get();
-      Scalars(sa, sc);
-      mll_new = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
-      if (mll_new < mll + kCArmijo * lr * gdd || std::isnan(mll_new) || std::isinf(mll_new)) lr *= 0.5;
-      else break;
-    }
-    std::swap(d_mode_, d_mode_new_);
-    res.newton_its = it + 1;
-    if (std::isnan(mll_new) || std::isinf(mll_new))
-      throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
-    const double dc = cfg.delta_conv_mode_finding;
-    const bool term = (it == 0) ? std::fabs(mll_new - mll) < dc * std::fabs(mll) : (mll_new - mll) < dc * std::fabs(mll);
-    mll = mll_new;
-    return term;
-  };
   EnsureProbes(cfg);
   const int tw = probe_cols();          // this rank's probe block width (t at world 1)
   const int tl = c1_ - c0_;             // its real probe columns (the rest is padding)
@@ -982,13 +987,7 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
     // (Sigma^-1 + W)^-1 (y / aux) and the SLQ block solve the same system. Both run as one
     // PCG over 1 + t columns: column 0 keeps the single-vector stopping rule, columns 1..t
     // the block rule (each column's iterates are exactly those of a separate run).
-    NewtonPrepArgs np{};
-    np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
-    np.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
-    np.obs = Obs();
-    np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get(); np.W_update = 1;
-    np.rhs = d_rhs_.get(); np.dw = d_dw_.get(); np.sdw = d_sdw_.get();
-    launch_newton_prep(np, s_);
+    NewtonPrep(lik, aux, 1, d_rhs_.get(), d_dw_.get(), d_sdw_.get());
     SetDiag();
     n_lead = 1;
     const int tf = tw + 1;
@@ -1004,29 +1003,15 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
     res.cg_its = slq.its_single;
     launch_pack_columns(n, 1, d_Uf_.get(), tf, 0, d_mode_upd_.get(), 1, 0, s_);
     launch_pack_columns(n, tw, d_Uf_.get(), tf, 1, d_U_.get(), tw, 0, s_);
-    line_search_and_check(0, 0.);
-    {   // first derivative at the mode (likelihoods.h:3008; used by the gradient wrt F)
-      NewtonPrepArgs nd{};
-      nd.n = n; nd.lik = lik; nd.aux = aux; nd.y = d_y_.get(); nd.loc = d_mode_.get(); nd.mode = d_mode_.get();
-      nd.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
-      nd.obs = Obs();
-      nd.Dinv = d_Dinv_.get(); nd.d1 = d_d1_.get(); nd.W = d_W_.get(); nd.W_update = 0;
-      launch_newton_prep(nd, s_);
-    }
+    LineSearchAndCheck(0, 0., max_shrink, delta, sa, mll, res);
+    // first derivative at the mode (likelihoods.h:3008; used by the gradient wrt F)
+    NewtonPrep(lik, aux, 0, nullptr, nullptr, nullptr);
   } else {
     // ---- 2. mode finding (likelihoods.h:2780-3000)
     bool upd_zero = true;
     const int newton_its = start == ModeStart::kKeep ? 0 : maxit;   // kKeep: the mode as it stands
     for (int it = 0; it < newton_its; ++it) {
-      NewtonPrepArgs np{};
-      np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
-    np.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
-    np.obs = Obs();
-      np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get();
-      np.W_update = 1;
-      np.rhs = d_rhs_.get();
-      np.dw = d_dw_.get();
-      launch_newton_prep(np, s_);
+      NewtonPrep(lik, aux, 1, d_rhs_.get(), d_dw_.get(), nullptr);
       SetDiag();
       const PcgResult pr = Pcg(b1, d_rhs_.get(), d_mode_upd_.get(), 1, it == 0, upd_zero, cg_max, 0, cfg.cg_delta_conv);
       res.cg_its += pr.its_single;
@@ -1036,20 +1021,11 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
       launch_axpby(n, 1., d_mode_upd_.get(), -1., d_mode_.get(), d_dir_.get(), s_);
       ApplyA(d_dir_.get(), d_Adir_.get(), b1.G.get(), 1);
       const double gdd = Dot1(d_dir_.get(), d_Adir_.get());
-      if (line_search_and_check(it, gdd)) break;
+      if (LineSearchAndCheck(it, gdd, max_shrink, delta, sa, mll, res)) break;
     }
-    {   // derivative / information at the mode, VADU diagonal and its square root (:3000-3005, 12163-12166)
-      NewtonPrepArgs np{};
-      np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
-    np.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
-    np.obs = Obs();
-      np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get();
-      np.W_update = info_changes ? 1 : 0;
-      np.dw = d_dw_.get();
-      np.sdw = d_sdw_.get();
-      launch_newton_prep(np, s_);
-      SetDiag();
-    }
+    // derivative / information at the mode, VADU diagonal and its square root (:3000-3005, 12163-12166)
+    NewtonPrep(lik, aux, info_changes ? 1 : 0, nullptr, d_dw_.get(), d_sdw_.get());
+    SetDiag();
     // ---- 3. SLQ block (likelihoods.h:3018-3045, 12155-12212): z_i = B^T (D^-1 + W)^(1/2) r_i
     bslq = &GetBlock(1, tw, pmax_tri);
     launch_bt_apply(sp_, d_Bv_.get(), true, d_probes_.get(), tw, d_sdw_.get(), nullptr, nullptr, d_Zp_.get(), s_);
@@ -1198,8 +1174,7 @@ LatentResult LatentVecchia::Eval(int cov_type, int lik, const double* trafo, dou
       double h[3];
       HIP_CHECK(hipMemcpyAsync(h, red.get(), sizeof(h), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
-      const double neg = aux * (h[0] - n * (std::log(aux) + 1. - digamma_asa103(aux)) - sum_log_y_);
-      res.grad.push_back(neg + 0.5 * h[1] + h[2]);
+      res.grad.push_back(gamma_shape_grad(aux, n, h[0], h[1], h[2], sum_log_y_));
     }
     // gaussian error variance on the log scale (:5166-5200, 10586-10597, 12520-12546)
     if (gauss && want_aux_grad) {
@@ -1373,40 +1348,13 @@ LatentResult LatentVecchia::EvalPivChol(int cov_type, int lik, const double* tra
     Fatal("The matrix D in the Vecchia approximation contains negative or zero values. "
           "This likely results from numerical instabilities ");
   double mll = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
-  const int maxit = gauss ? 1 : 1000;
-  const int max_shrink = gauss ? 1 : 20;
+  const int maxit = gauss ? 1 : kMaxItModeNewton;
+  const int max_shrink = gauss ? 1 : kMaxShrinkNewton;
   const int pmax_tri = std::max(1, std::min(cfg.cg_max_num_it_tridiag, n));
   const int cg_max = std::max(0, cfg.cg_max_num_it);
-  auto line_search_and_check = [&](int it, double gdd) -> bool {   // likelihoods.h:2967-2995, 11820-11870
-    double lr = 1., mll_new = mll;
-    for (int ih = 0; ih < max_shrink; ++ih) {
-      if (ih == 0) launch_copy(n, d_mode_upd_.get(), d_mode_new_.get(), s_);
-      else launch_axpby(n, 1. - lr, d_mode_.get(), lr, d_mode_upd_.get(), d_mode_new_.get(), s_);
-      if (lik == kLikPoisson || lik == kLikGamma) launch_cap_mode_change(n, d_mode_.get(), d_mode_new_.get(), s_);
-      sa.mode = d_mode_new_.get();
-      Scalars(sa, sc);
-      mll_new = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
-      if (mll_new < mll + kCArmijo * lr * gdd || std::isnan(mll_new) || std::isinf(mll_new)) lr *= 0.5;
-      else break;
-    }
-    std::swap(d_mode_, d_mode_new_);
-    res.newton_its = it + 1;
-    if (std::isnan(mll_new) || std::isinf(mll_new))
-      throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
-    const double dc = cfg.delta_conv_mode_finding;
-    const bool term = (it == 0) ? std::fabs(mll_new - mll) < dc * std::fabs(mll) : (mll_new - mll) < dc * std::fabs(mll);
-    mll = mll_new;
-    return term;
-  };
-  auto prep = [&](int w_update, bool want_rhs) {
-    NewtonPrepArgs np{};
-    np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
-    np.offset = has_off_ ? d_off_.get() : nullptr;
-    np.obs = Obs();
-    np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get(); np.W_update = w_update;
-    np.rhs = want_rhs ? d_rhs_.get() : nullptr;
-    np.dw = d_dw_.get();
-    launch_newton_prep(np, s_);
+  const double delta = cfg.delta_conv_mode_finding;
+  auto prep = [&](int w_update, bool want_rhs) {   // has_obs_ is excluded above
+    NewtonPrep(lik, aux, w_update, want_rhs ? d_rhs_.get() : nullptr, d_dw_.get(), nullptr);
   };
   // I_k + L_k^T W L_k, its factor and inverse for the current W (likelihoods.h:11985-11990, 12099-12103)
   double logdet_G = 0.;
@@ -1432,7 +1380,7 @@ LatentResult LatentVecchia::EvalPivChol(int cov_type, int lik, const double* tra
                                             d_sig1_.get());
     res.cg_its += pr.its_single;
     if (pr.nan) throw LatentNan("NaN or Inf occurred in the conjugate gradient algorithm during mode finding");
-    line_search_and_check(0, 0.);
+    LineSearchAndCheck(0, 0., max_shrink, delta, sa, mll, res);
     prep(0, false);   // first derivative at the mode (likelihoods.h:3008)
   } else {
     bool upd_zero = true;
@@ -1448,7 +1396,7 @@ LatentResult LatentVecchia::EvalPivChol(int cov_type, int lik, const double* tra
       launch_axpby(n, 1., d_mode_upd_.get(), -1., d_mode_.get(), d_dir_.get(), s_);   // Armijo (:2957-2966)
       ApplyA(d_dir_.get(), d_Adir_.get(), b1.G.get(), 1);
       const double gdd = Dot1(d_dir_.get(), d_Adir_.get());
-      if (line_search_and_check(it, gdd)) break;
+      if (LineSearchAndCheck(it, gdd, max_shrink, delta, sa, mll, res)) break;
     }
     prep(1, false);   // derivative / information at the mode (:3008-3011)
     gram(false);
@@ -1561,8 +1509,7 @@ LatentResult LatentVecchia::EvalPivChol(int cov_type, int lik, const double* tra
       double h[3];
       HIP_CHECK(hipMemcpyAsync(h, red.get(), sizeof(h), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
-      const double neg = aux * (h[0] - n * (std::log(aux) + 1. - digamma_asa103(aux)) - sum_log_y_);
-      res.grad.push_back(neg + 0.5 * h[1] + h[2]);
+      res.grad.push_back(gamma_shape_grad(aux, n, h[0], h[1], h[2], sum_log_y_));
     }
     // gaussian error variance on the log scale (:12487-12506): dW / dlog aux = -W = -1 / aux on every row
     if (gauss && want_aux_grad) {

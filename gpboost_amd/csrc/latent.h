@@ -11,6 +11,8 @@
 // and "bernoulli_logit". Every O(n) / O(n m) / O(n m t) step is a HIP kernel on the
 // model's stream; the host runs the iteration logic (stopping tests, line search) and
 // the O(t k^2) tridiagonal eigenproblems, exactly where the reference branches.
+// Also here: LatentSolverBase, what REModelAMD needs from any Laplace solver, and ObsLaplaceBase, the part the
+// dense, FITC and full-scale Vecchia drivers share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +27,7 @@
 
 #include "common.h"
 #include "collective.h"
+#include "laplace_newton.h"
 #include "latent_kernels.h"
 #include "vadu_precond.h"
 #include "lowrank_precond.h"
@@ -45,25 +48,6 @@ struct IterativeConfig {
   bool piv_chol = false;
   int piv_chol_rank = 50;                  // default_piv_chol_preconditioner_rank_ (re_model_template.h:789-800)
 };
-
-// NaN / Inf in the mode finding or a CG solve of an evaluation. The reference sets the approximate
-// marginal log-likelihood to NaN and returns (likelihoods.h:2929-2933, 2997-3000), so an L-BFGS line
-// search shrinks the step (LineSearchBacktracking.h:78); REModelAMD turns this into nll = NaN when
-// its caller tolerates it and into a fatal error otherwise.
-// digamma by the asymptotic expansion after recurrence to x >= 8.5 (Bernardo 1976, Algorithm AS 103; the form the
-// reference's GPBoost::digamma uses, DF_utils.cpp:82-123)
-inline double digamma_asa103(double x) {
-  if (x <= 0.000001) return -0.57721566490153286060 - 1.0 / x + 1.6449340668482264365 * x;
-  double value = 0., x2 = x;
-  while (x2 < 8.5) {
-    value = value - 1.0 / x2;
-    x2 = x2 + 1.0;
-  }
-  double r = 1.0 / x2;
-  value = value + std::log(x2) - 0.5 * r;
-  r = r * r;
-  return value - r * (1.0 / 12.0 - r * (1.0 / 120.0 - r * (1.0 / 252.0 - r * (1.0 / 240.0 - r * (1.0 / 132.0)))));
-}
 
 // What TestInfo reports: the counts that show which kernel paths a structure reaches.
 enum LatentStat : int {
@@ -92,6 +76,10 @@ enum LatentStat : int {
   kTestLatentStats
 };
 
+// NaN / Inf in the mode finding or a CG solve of an evaluation. The reference sets the approximate
+// marginal log-likelihood to NaN and returns (likelihoods.h:2929-2933, 2997-3000), so an L-BFGS line
+// search shrinks the step (LineSearchBacktracking.h:78); REModelAMD turns this into nll = NaN when
+// its caller tolerates it and into a fatal error otherwise.
 struct LatentNan : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
@@ -131,6 +119,39 @@ class LatentSolverBase {
 
  protected:
   double loglik_const_ = 0.;
+};
+
+// The part DenseLaplace, FitcLaplace and VifLaplace share: one latent variable per observation in the model's
+// order, so y, the offsets and the mode pass through unpermuted. The derived constructor allocates y_ and off_
+// (>= n) with its other vectors and owns mode_.
+class ObsLaplaceBase : public LatentSolverBase {
+ public:
+  void SetY(const double* y) override {
+    sum_log_y_ = 0.;   // aux_log_normalizing_constant_ of likelihood 'gamma' (likelihoods.h:8181-8191)
+    for (int i = 0; i < n_; ++i) sum_log_y_ += y[i] > 0. ? std::log(y[i]) : 0.;
+    HIP_CHECK(hipMemcpyAsync(y_.get(), y, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+    y_set_ = true;
+  }
+  void SetOffset(const double* off) override {
+    has_off_ = off != nullptr;
+    if (has_off_) {
+      HIP_CHECK(hipMemcpyAsync(off_.get(), off, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
+      HIP_CHECK(hipStreamSynchronize(s_));
+    }
+  }
+  void GetMode(double* mode) override {
+    HIP_CHECK(hipMemcpyAsync(mode, mode_.get(), sizeof(double) * n_, hipMemcpyDeviceToHost, s_));
+    HIP_CHECK(hipStreamSynchronize(s_));
+  }
+
+ protected:
+  ObsLaplaceBase(int n, hipStream_t stream) : n_(n), s_(stream) {}
+  int n_;
+  hipStream_t s_;
+  DevBuf<double> y_, off_, mode_;
+  bool y_set_ = false, has_off_ = false;
+  double sum_log_y_ = 0.;
 };
 
 // Structure and plan choices of a LatentVecchia. An entry < 0 takes the environment's value
@@ -301,6 +322,14 @@ class LatentVecchia : public LatentSolverBase {
   void AllReduceHost(double* v, int count);
   int probe_cols() const { return world_ > 1 ? (t_all_ + world_ - 1) / world_ : t_all_; }
   void Scalars(const ScalarArgs& a, double* out);
+  // newton_prep at d_mode_ on the members: d1, W (rewritten when w_update) and the nullable outputs
+  // rhs = W mode + d1, dw = D^-1 + W, sdw = sqrt(dw)
+  void NewtonPrep(int lik, double aux, int w_update, double* rhs, double* dw, double* sdw);
+  // The line search of Newton step it (newton_line_search, laplace_newton.h; likelihoods.h:2967-2995): trial modes
+  // between d_mode_ and d_mode_upd_ (capped for poisson / gamma) into d_mode_new_, objective from Scalars(sa).
+  // Swaps the kept trial into d_mode_, sets res.newton_its and mll, throws LatentNan; true: converged.
+  bool LineSearchAndCheck(int it, double gdd, int max_shrink, double delta, ScalarArgs& sa, double& mll,
+                          LatentResult& res);
   double Dot1(const double* x, const double* y);   // single-vector dot, synchronous
   void WaitCtl(int seq, int* out);
 

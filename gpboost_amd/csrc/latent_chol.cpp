@@ -9,8 +9,9 @@
 //                     (the reference's CalcLtLGivenSparsityPattern over L^-1), d_mll_d_mode = 0.5 diag(S) dW,
 //                     the implicit term through one more solve, the aux / F gradients (:5281-5336, 5337-5369)
 //   predictions       PredictLaplaceApproxVecchia, Cholesky branch (:6751-6811): Maux = L \ (Bpo^T [Bp^-T])
-// Reused from the iterative path: the latent factor kernel, the Newton record (newton_prep), the row
-// scalars (quadratic forms, log-likelihood, implicit terms) and the A operator for the Armijo slope.
+// Reused from the iterative path: the latent factor kernel, the Newton record (NewtonPrep), the line search
+// (LineSearchAndCheck), the row scalars (quadratic forms, log-likelihood, implicit terms) and the A operator
+// for the Armijo slope.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -24,7 +25,6 @@ namespace gpb_amd {
 
 namespace {
 constexpr double kJitterMultVecchiaC = 1. + 1e-10;   // JITTER_MULT_VECCHIA (utils.h)
-constexpr double kCArmijoC = 1e-4;                   // c_armijo_ (likelihoods.h:12737)
 }  // namespace
 
 void LatentVecchia::SetCholesky(bool on) { use_chol_ = on; }
@@ -88,16 +88,6 @@ LatentResult LatentVecchia::EvalChol(int cov_type, int lik, const double* trafo,
   sa.nbr = d_nbr_.get(); sa.Bv = d_Bv_.get(); sa.Dinv = d_Dinv_.get(); sa.y = d_y_.get();
   sa.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
   sa.obs = Obs();
-  auto newton_prep = [&](int W_update, bool with_rhs) {
-    NewtonPrepArgs np{};
-    np.n = n; np.lik = lik; np.aux = aux; np.y = d_y_.get(); np.loc = d_mode_.get(); np.mode = d_mode_.get();
-    np.offset = has_off_ && !has_obs_ ? d_off_.get() : nullptr;
-    np.obs = Obs();
-    np.Dinv = d_Dinv_.get(); np.d1 = d_d1_.get(); np.W = d_W_.get(); np.W_update = W_update;
-    np.rhs = with_rhs ? d_rhs_.get() : nullptr;
-    np.dw = d_dw_.get();
-    launch_newton_prep(np, s_);
-  };
   auto factor = [&]() {
     chol_->Factor(d_W_.get());
     if (chol_->Info() > 0)
@@ -121,34 +111,14 @@ LatentResult LatentVecchia::EvalChol(int cov_type, int lik, const double* trafo,
     Fatal("The matrix D in the Vecchia approximation contains negative or zero values. "
           "This likely results from numerical instabilities ");
   double mll = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
-  const bool info_changes = !gauss;              // information_changes_during/after_mode_finding_
-  const int maxit = gauss ? 1 : 1000;            // maxit_mode_newton_ (likelihoods.h:255, 12721)
-  const int max_shrink = gauss ? 1 : 20;         // max_number_lr_shrinkage_steps_newton_ (:256, 12725)
-  auto line_search_and_check = [&](int it, double gdd) -> bool {   // likelihoods.h:2967-2995, 11820-11870
-    double lr = 1., mll_new = mll;
-    for (int ih = 0; ih < max_shrink; ++ih) {
-      if (ih == 0) launch_copy(n, d_mode_upd_.get(), d_mode_new_.get(), s_);
-      else launch_axpby(n, 1. - lr, d_mode_.get(), lr, d_mode_upd_.get(), d_mode_new_.get(), s_);
-      if (lik == kLikPoisson || lik == kLikGamma) launch_cap_mode_change(n, d_mode_.get(), d_mode_new_.get(), s_);
-      sa.mode = d_mode_new_.get();
-      Scalars(sa, sc);
-      mll_new = sc[kSqLogLik] - 0.5 * sc[kSqQuad];
-      if (mll_new < mll + kCArmijoC * lr * gdd || std::isnan(mll_new) || std::isinf(mll_new)) lr *= 0.5;
-      else break;
-    }
-    std::swap(d_mode_, d_mode_new_);
-    res.newton_its = it + 1;
-    if (std::isnan(mll_new) || std::isinf(mll_new))
-      throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
-    const double dc = cfg.delta_conv_mode_finding;
-    const bool term = (it == 0) ? std::fabs(mll_new - mll) < dc * std::fabs(mll) : (mll_new - mll) < dc * std::fabs(mll);
-    mll = mll_new;
-    return term;
-  };
+  const bool info_changes = !gauss;                      // information_changes_during/after_mode_finding_
+  const int maxit = gauss ? 1 : kMaxItModeNewton;        // gaussian: likelihoods.h:255
+  const int max_shrink = gauss ? 1 : kMaxShrinkNewton;   // :256
+  const double delta = cfg.delta_conv_mode_finding;      // :12723
   const int newton_its = start == ModeStart::kKeep ? 0 : maxit;   // kKeep: the mode as it stands
   for (int it = 0; it < newton_its; ++it) {
     // rhs = W mode + d1 (:2920-2924); W changes with the mode for non-Gaussian likelihoods
-    newton_prep(1, true);
+    NewtonPrep(lik, aux, 1, d_rhs_.get(), d_dw_.get(), nullptr);
     if (it == 0 || info_changes) factor();
     chol_->Solve(d_rhs_.get(), d_mode_upd_.get());
     double gdd = 0.;
@@ -157,10 +127,10 @@ LatentResult LatentVecchia::EvalChol(int cov_type, int lik, const double* trafo,
       ApplyA(d_dir_.get(), d_Adir_.get(), b1.G.get(), 1);
       gdd = Dot1(d_dir_.get(), d_Adir_.get());
     }
-    if (line_search_and_check(it, gdd)) break;
+    if (LineSearchAndCheck(it, gdd, max_shrink, delta, sa, mll, res)) break;
   }
   // derivatives / information at the mode, refactor when the information changed (:3008-3011, 3052-3066)
-  newton_prep(1, false);
+  NewtonPrep(lik, aux, 1, nullptr, d_dw_.get(), nullptr);
   if (info_changes || newton_its == 0) factor();
   const double two_sum_log_l = chol_->LogDet();
   sa.mode = d_mode_.get();
@@ -219,8 +189,7 @@ LatentResult LatentVecchia::EvalChol(int cov_type, int lik, const double* trafo,
       double h[3];
       HIP_CHECK(hipMemcpyAsync(h, red.get(), sizeof(h), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
-      const double neg = aux * (h[0] - n * (std::log(aux) + 1. - digamma_asa103(aux)) - sum_log_y_);
-      res.grad.push_back(neg + 0.5 * h[1] + h[2]);
+      res.grad.push_back(gamma_shape_grad(aux, n, h[0], h[1], h[2], sum_log_y_));
     }
     // gaussian error variance on the log scale: dW / dlog aux = -W, d_detmll = sum dW_i S_ii (:5304-5335)
     if (gauss && want_aux_grad) {

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "grouped_laplace.h"
 #include "kernels.h"
+#include "laplace_kernels.h"
 #include "latent_kernels.h"
 #include "lik_test.h"
 #include "lowrank_precond.h"
@@ -247,11 +248,11 @@ void test_lik_path(const LikPathTest& t, int* guard) {
         }
         test_fl_prep(n, t.lik, t.aux, dy.get(), off, dmode.get(), dv[0].get(), opt[0], o[0], o[1], o[2], o[3], o[4], s);
       } else if (t.kernel == kLikKernelTrial) {
-        gpart.make((size_t)3 * test_fl_blocks(n));
-        test_fl_trial(n, t.lik, t.aux, t.lam, dmode.get(), dv[0].get(), dv[1].get(), dv[2].get(), dy.get(), off, o[0], o[1],
+        gpart.make((size_t)2 * laplace_blocks(n));
+        test_laplace_trial(n, t.lik, t.aux, t.lam, dmode.get(), dv[0].get(), dv[1].get(), dv[2].get(), dy.get(), off, o[0], o[1],
                       gpart.p(), gsum.p(), s);
       } else {
-        gpart.make((size_t)3 * test_fl_blocks(n));
+        gpart.make((size_t)3 * laplace_blocks(n));
         test_fl_final(n, t.lik, t.aux, dy.get(), off, dmode.get(), dv[0].get(), o[0], o[1], o[2], o[3], gpart.p(), gsum.p(),
                       s);
       }
@@ -260,8 +261,8 @@ void test_lik_path(const LikPathTest& t, int* guard) {
       if (t.kernel == kLikKernelPrep) {
         test_dl_prep(n, t.lik, t.aux, dy.get(), off, dmode.get(), o[0], o[1], o[2], o[3], s);
       } else if (t.kernel == kLikKernelTrial) {
-        gpart.make((size_t)2 * test_dl_blocks(n));
-        test_dl_trial(n, t.lik, t.aux, t.lam, dmode.get(), dv[0].get(), dv[1].get(), dv[2].get(), dy.get(), off, o[0], o[1],
+        gpart.make((size_t)2 * laplace_blocks(n));
+        test_laplace_trial(n, t.lik, t.aux, t.lam, dmode.get(), dv[0].get(), dv[1].get(), dv[2].get(), dy.get(), off, o[0], o[1],
                       gpart.p(), gsum.p(), s);
       } else {
         test_dl_dmll(dmats.get(), dmats.get() + (size_t)ld * n, n, ld, t.lik, t.aux, dy.get(), off, dmode.get(), o[0], o[1],

@@ -2,7 +2,7 @@
 // (GPB_TestLikPoint / GPB_TestLikPath, include/gpboost_amd.h; lik_test.cpp). Host arrays in and out; every extent
 // and index is checked on the host before any device call. The production kernels sit in anonymous namespaces, so
 // each .hip file ends in small test_* launchers (below) with exactly the grid and block arithmetic of its
-// production caller; no kernel body is copied.
+// production caller; no kernel body is copied. The fitc and dense paths share one trial kernel and one launcher.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@ namespace gpb_amd {
 enum LikPath : int { kLikPathGrouped = 0, kLikPathVif, kLikPathFitc, kLikPathDense, kLikPathVecchia, kNumLikPaths };
 enum LikKernel : int {
   kLikKernelPrep = 0,   // grouped: glp_obs_kernel<true>; vif / fitc / dense: *_prep_kernel; vecchia: newton_prep_kernel
-  kLikKernelTrial,      // grouped: glp_obs_kernel<false>; vif / fitc / dense: *_trial_kernel
+  kLikKernelTrial,      // grouped: glp_obs_kernel<false>; vif: vl_trial_kernel; fitc / dense: laplace_trial_kernel
   kLikKernelFinal,      // fitc: fl_final_kernel; dense: dl_dmll_kernel
   kNumLikKernels
 };
@@ -65,22 +65,18 @@ void test_vl_prep(int n, int lik, double aux, const double* y, const double* off
                   double* W, double* dW, double* rhs, double* part, double* sum, hipStream_t s);
 void test_vl_trial(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* upd,
                    double lam, int first, int cap, double* trial, double* part, double* sum, hipStream_t s);
-// fitc_laplace.hip: part holds 3 test_fl_blocks(n) doubles; sums: 2 (trial) or 3 (final) doubles
-int test_fl_blocks(int n);
+// laplace_kernels.hip: the trial of the fitc and dense paths; part holds 2 laplace_blocks(n) doubles, sums: 2
+void test_laplace_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
+                        const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
+                        double* sums, hipStream_t s);
+// fitc_laplace.hip: part holds 3 laplace_blocks(n) doubles; sums: 3 doubles
 void test_fl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* dvec,
                   int w_update, double* d1, double* w, double* wdw, double* DW, double* rhs, hipStream_t s);
-void test_fl_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
-                   const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
-                   double* sums, hipStream_t s);
 void test_fl_final(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* dvec,
                    double* d1, double* w, double* DW, double* dpwi, double* part, double* sums, hipStream_t s);
-// dense_laplace.hip: part holds 2 test_dl_blocks(n) doubles; C, S: n x n column-major with leading dimension ld
-int test_dl_blocks(int n);
+// dense_laplace.hip: C, S: n x n column-major with leading dimension ld
 void test_dl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, double* d1,
                   double* w, double* ws, double* rhs, hipStream_t s);
-void test_dl_trial(int n, int lik, double aux, double lam, const double* mode, const double* a, const double* mupd,
-                   const double* aupd, const double* y, const double* off, double* mnew, double* anew, double* part,
-                   double* sums, hipStream_t s);
 void test_dl_dmll(const double* C, const double* S, int n, int ld, int lik, double aux, const double* y, const double* off,
                   const double* mode, double* dmll, double* dg, hipStream_t s);
 

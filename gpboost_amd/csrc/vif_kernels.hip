@@ -22,6 +22,7 @@
 #include "fitc.h"
 #include "latent_kernels.h"
 #include "kernels.h"
+#include "reduce.h"
 #include "vif.h"
 
 namespace gpb_amd {
@@ -33,23 +34,6 @@ constexpr int kMaxNn = kVifMaxNn;          // neighbours per row without derivat
 constexpr int kMaxNnGrad = kVifMaxNnGrad;  // with the two derivative blocks (the likelihood's rows)
 constexpr int kNv = 16;      // n-vector scratch slots
 constexpr int kMv = 12;      // m-vector scratch slots
-
-template <class F>
-void dispatch_cov_vif(int cov, F&& f) {
-  switch (cov) {
-    case kMatern05: f(std::integral_constant<int, kMatern05>{}); break;
-    case kMatern15: f(std::integral_constant<int, kMatern15>{}); break;
-    case kMatern25: f(std::integral_constant<int, kMatern25>{}); break;
-    case kGaussian: f(std::integral_constant<int, kGaussian>{}); break;
-    default: Fatal("unsupported covariance type %d", cov);
-  }
-}
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // LDS ordering among the lanes of one wave (its LDS operations execute in order; the fences keep the
 // compiler from moving them across)
@@ -327,10 +311,10 @@ __global__ void __launch_bounds__(kT) vif_rows_kernel(VifRowsArgs a) {
         s2 = xd[1] * vecs[0][p] + xa[0] * vecs[2][p];
       }
     }
-    s0 = wsum(s0);
+    s0 = wave_sum(s0);
     if (GRAD) {
-      s1 = wsum(s1);
-      s2 = wsum(s2);
+      s1 = wave_sum(s1);
+      s2 = wave_sum(s2);
     }
     const size_t row = (size_t)ir * nn;
     if (p < nn) {
@@ -614,10 +598,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) vi
       s2 = xd[1] * vecs[0][lane] + xa[0] * vecs[2][lane];
     }
   }
-  s0 = wsum(s0);
+  s0 = wave_sum(s0);
   if (GRAD) {
-    s1 = wsum(s1);
-    s2 = wsum(s2);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
   }
   const size_t row = (size_t)ir * nn;
   if (lane < nn) {
@@ -775,7 +759,7 @@ __global__ void __launch_bounds__(kT) vif_gemv_reduce_kernel(const double* __res
   if (j >= m) return;
   double s = 0.;
   for (int b = lane; b < nb; b += 64) s += part[(size_t)b * ldm + j];
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) out[j] = s;
 }
 
@@ -788,7 +772,7 @@ __global__ void __launch_bounds__(kT) vif_coldot_kernel(const double* __restrict
   if (i >= n) return;
   double s = 0.;
   for (int q = lane; q < m; q += 64) s = fma(M[(size_t)i * ldm + q], w ? w[q] : M2[(size_t)i * ldm + q], s);
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) out[i] = s;
 }
 
@@ -842,7 +826,7 @@ __global__ void __launch_bounds__(kT) vif_sum_kernel(int n, int nt, VifTerms T, 
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     if (t >= nt) break;
-    const double s = wsum(acc[t]);
+    const double s = wave_sum(acc[t]);
     if (lane == 0) red[w][t] = s;
   }
   __syncthreads();
@@ -875,7 +859,7 @@ __global__ void __launch_bounds__(64) vif_pred_bpo_kernel(int np, int n, int mp,
   double s = 0.;
   for (int j = lane; j < mp; j += 64)
     if (nb[j] >= 0 && nb[j] < n) s = fma(bv[j], r[nb[j]], s);
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) mo[p] = s;
   for (int q = lane; q < m; q += 64) {
     double t = 0.;
@@ -900,7 +884,7 @@ __global__ void __launch_bounds__(kT) vif_pred_var_kernel(int np, int m, int ldm
     const double kp = KP[o + q], pv = PPV[o + q], qq = Q[o + q];
     s += (kp - pv + 2. * qq) * Sig[o + q] + (pv - 2. * qq) * S2[o + q] + qq * S3[o + q];
   }
-  s = wsum(s);
+  s = wave_sum(s);
   if (lane == 0) out[p] = s;
 }
 
@@ -943,7 +927,7 @@ void vif_launch_rows(const VifRowsLaunch& L, hipStream_t s) {
   const size_t lds = rows_lds_bytes(L.nn, L.grad);
   const bool mfma = L.form == 1 || (L.form == 0 && L.nn <= kVifMaxNnMfma);   // sets of <= 32 points: the MFMA Gram form
   const bool grad = L.grad;
-  dispatch_cov_vif(L.cov_type, [&](auto c) {
+  dispatch_cov(L.cov_type, [&](auto c) {
     constexpr int COV = decltype(c)::value;
     if (mfma) {
       if (grad) hipLaunchKernelGGL((vif_rows_mfma_kernel<COV, true>), dim3(grid), dim3(64), 0, s, a);
@@ -1070,7 +1054,7 @@ void vif_launch_sum(hipStream_t s, int n, int nt, const VifTerms& T, double* par
 
 void vif_launch_dkmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
                      double var, double phi, double* dK) {
-  dispatch_cov_vif(cov_type, [&](auto c) {
+  dispatch_cov(cov_type, [&](auto c) {
     constexpr int COV = decltype(c)::value;
     hipLaunchKernelGGL((vif_dkmn_kernel<COV>), dim3((m + 63) / 64, (n + 3) / 4), dim3(kT), 0, s, X, Z, n, m, d, ldm, var,
                        phi, dK);

@@ -34,14 +34,12 @@
 
 namespace gpb_amd {
 
-class VifLaplace : public LatentSolverBase {
+class VifLaplace : public ObsLaplaceBase {
  public:
   // nbr: host n x nn neighbour lists of the VIF model (model order), X: host row-major n x d coordinates.
   VifLaplace(VifSolver* vif, const std::vector<int>& nbr, const std::vector<double>& X, hipStream_t stream);
   ~VifLaplace() override;
 
-  void SetY(const double* y) override;
-  void SetOffset(const double* off) override;
   // The fixed effects as the caller passed them (data order, NULL: none). The reference's covariance
   // gradient (CalcGradPars, re_model_template.h:1859) hands them to CalcGradNegMargLikelihoodLaplaceApproxFSVA
   // without the model-order permutation of FSVA's random ordering (its mode finding, :8487, and CalcGradFLaplace,
@@ -49,7 +47,6 @@ class VifLaplace : public LatentSolverBase {
   // mode_i + F[i]. The covariance / aux gradient of Eval(grad_f = NULL) follows that; the F-gradient uses the
   // model-order offsets. GPBOOST_AMD_VIF_OFFSET_CONSISTENT=1: the model-order offsets everywhere.
   void SetGradOffset(const double* off_data_order);
-  void GetMode(double* mode) override;
   // trafo = (sigma1^2, phi); aux: the shape of likelihood 'gamma' (want_aux_grad: its gradient appended).
   LatentResult Eval(int cov_type, int lik, const double* trafo, double aux, const IterativeConfig& cfg,
                     bool want_grad, bool want_aux_grad, double* grad_f = nullptr,
@@ -85,15 +82,13 @@ class VifLaplace : public LatentSolverBase {
   double MDot(const double* a, const double* b);   // m-vector dot (synchronises)
 
   VifSolver* V_;
-  hipStream_t s_;
-  int n_, m_, ldm_;
+  int m_, ldm_;
   std::unique_ptr<SparseChol> chol_;
-  bool y_set_ = false, has_off_ = false, prev_valid_ = false, evaluated_ = false;
+  bool prev_valid_ = false, evaluated_ = false;
   double cached_obj_ = 0.;
   double aux_ = 1.;
   int lik_ = -1;
-  double sum_log_y_ = 0.;
-  DevBuf<double> y_, off_, mode_, mode_prev_, upd_, trial_, d1_, w_, dw_, rhs_, dinv_, diagS_, dmll_, vS_;
+  DevBuf<double> mode_prev_, upd_, trial_, d1_, w_, dw_, rhs_, dinv_, diagS_, dmll_, vS_;
   DevBuf<double> goff_, gd1_, gw_;       // data-order offsets; d1, W at mode + them (the reference's gradient)
   bool has_goff_ = false;
   DevBuf<double> vec_;                   // n-vector scratch

@@ -4,7 +4,8 @@
 // Device layout: n x m column sets are kept point-major (m x n, leading dimension ldm: point i's m values
 // contiguous), as in VifSolver; the sparse solves take them column-major (n x m, ld n) through a tiled
 // transpose. Per Newton step: one numeric factorization of A, one forward solve with the m columns of
-// C = R K (M2 = M - (L^-1 C)^T (L^-1 C) by the split-K MFMA Gram), two vector solves. Gradient: the selected
+// C = R K (M2 = M - (L^-1 C)^T (L^-1 C) by the split-K MFMA Gram), two vector solves, newton_line_search
+// (laplace_newton.h) on the capped trial kernel. Gradient: the selected
 // inverse of A (traces tr(S' A^-1), diag A^-1), one solve with m columns (A^-1 C), three m x n GEMMs with
 // M2^-1, the sparse products R X / S' X over m-columns, and Frobenius products for the m x m traces.
 #include <hip/hip_runtime.h>
@@ -21,9 +22,11 @@
 #include "dense.h"
 #include "fitc.h"
 #include "kernels.h"
+#include "laplace_kernels.h"
 #include "latent_kernels.h"
 #include "lik_device.h"
 #include "lik_test.h"
+#include "reduce.h"
 #include "vif_laplace.h"
 
 namespace gpb_amd {
@@ -33,26 +36,6 @@ constexpr int kT = 256;
 constexpr int kNvl = 14;                              // n-vector scratch slots
 constexpr int kMvl = 16;                              // m-vector scratch slots
 constexpr double kMaxChangeMode = 4.605170185988091;  // MAX_CHANGE_MODE_NEWTON_ = log(100) (likelihoods.h:12733)
-constexpr double kCArmijo = 1e-4;                     // c_armijo_ (likelihoods.h:12737)
-
-inline int nblk(int n) { return std::max(1, std::min(1024, (n + kT - 1) / kT)); }
-
-__device__ __forceinline__ double wsum64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-order block sum of per-thread values (4 waves)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wsum64(v);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  const double s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
-}
 
 __global__ void __launch_bounds__(kT) vl_recip_kernel(int n, const double* __restrict__ D, double* __restrict__ out) {
   const int i = blockIdx.x * kT + threadIdx.x;
@@ -76,7 +59,7 @@ __global__ void __launch_bounds__(kT) vl_prep_kernel(int n, int lik, double aux,
     if (rhs) rhs[i] = w * mode[i] + a;
     zeros += w == 0. ? 1. : 0.;
   }
-  const double s = block_sum(zeros, red);
+  const double s = block_wave_sum(zeros, red);
   if (part && threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -97,7 +80,7 @@ __global__ void __launch_bounds__(kT) vl_trial_kernel(int n, int lik, double aux
     trial[i] = t;
     ll += lik_loglik(lik, aux, y[i], off ? t + off[i] : t);
   }
-  const double s = block_sum(ll, red);
+  const double s = block_wave_sum(ll, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -112,7 +95,7 @@ __global__ void __launch_bounds__(kT) vl_dot_kernel(int n, const double* __restr
     if (c) v *= c[i];
     acc += v;
   }
-  const double s = block_sum(acc, red);
+  const double s = block_wave_sum(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -122,14 +105,8 @@ __global__ void __launch_bounds__(kT) vl_mdot_kernel(int m, const double* __rest
   __shared__ double red[4];
   double acc = 0.;
   for (int j = threadIdx.x; j < m; j += kT) acc += a[j] * b[j];
-  const double s = block_sum(acc, red);
+  const double s = block_wave_sum(acc, red);
   if (threadIdx.x == 0) *out = s;
-}
-
-__global__ void __launch_bounds__(kT) vl_mul_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
-                                                    double* __restrict__ out) {
-  const int i = blockIdx.x * kT + threadIdx.x;
-  if (i < n) out[i] = a[i] * b[i];
 }
 
 // out = (e - dD o u) o dinv
@@ -232,7 +209,7 @@ __global__ void __launch_bounds__(kT) vl_gamma_kernel(int n, const double* __res
     a1 += W[i] * (full[i] + diagS[i]);
     a2 += d1[i] * v[i];
   }
-  const double s0 = block_sum(a0, red), s1 = block_sum(a1, red), s2 = block_sum(a2, red);
+  const double s0 = block_wave_sum(a0, red), s1 = block_wave_sum(a1, red), s2 = block_wave_sum(a2, red);
   if (threadIdx.x == 0) {
     part[(size_t)blockIdx.x * 3] = s0;
     part[(size_t)blockIdx.x * 3 + 1] = s1;
@@ -268,7 +245,7 @@ __global__ void __launch_bounds__(kT) vl_colsq_kernel(int n, const double* __res
   const double* c = M + (size_t)blockIdx.x * n;
   double acc = 0.;
   for (int k = threadIdx.x; k < n; k += kT) acc += c[k] * c[k];
-  const double s = block_sum(acc, red);
+  const double s = block_wave_sum(acc, red);
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
@@ -287,14 +264,14 @@ __global__ void __launch_bounds__(kT) vl_pvar_kernel(int np, int m, int ldm, con
     const double v = Vp[o + q], sg = Sig[o + q], x1 = X1[o + q], x2 = X2[o + q], x3 = X3[o + q], x4 = X4[o + q];
     s += v * v - sg * x1 + x2 * x1 + 2. * sg * x3 - 2. * x2 * x3 + x4 * x3;
   }
-  s = wsum64(s);
+  s = wave_sum(s);
   if (lane == 0) out[p] = s;
 }
 
 }  // namespace
 
 VifLaplace::VifLaplace(VifSolver* vif, const std::vector<int>& nbr, const std::vector<double>& X, hipStream_t stream)
-    : V_(vif), s_(stream), n_(vif->n_), m_(vif->m_), ldm_(vif->ldm_) {
+    : ObsLaplaceBase(vif->n_, stream), V_(vif), m_(vif->m_), ldm_(vif->ldm_) {
   V_->latent_ = true;
   chol_.reset(new SparseChol(n_, V_->nn_, nbr.data(), V_->d_, X.data(), stream));
   const int n = n_;
@@ -329,22 +306,6 @@ VifLaplace::~VifLaplace() {
   for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
 }
 
-void VifLaplace::SetY(const double* y) {
-  HIP_CHECK(hipMemcpyAsync(y_.get(), y, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-  HIP_CHECK(hipStreamSynchronize(s_));
-  sum_log_y_ = 0.;   // aux_log_normalizing_constant_ of likelihood 'gamma' (likelihoods.h:8181-8191)
-  for (int i = 0; i < n_; ++i) sum_log_y_ += y[i] > 0. ? std::log(y[i]) : 0.;
-  y_set_ = true;
-}
-
-void VifLaplace::SetOffset(const double* off) {
-  has_off_ = off != nullptr;
-  if (has_off_) {
-    HIP_CHECK(hipMemcpyAsync(off_.get(), off, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-    HIP_CHECK(hipStreamSynchronize(s_));
-  }
-}
-
 void VifLaplace::SetGradOffset(const double* off) {
   has_goff_ = off != nullptr;
   if (has_goff_) {
@@ -353,11 +314,6 @@ void VifLaplace::SetGradOffset(const double* off) {
     HIP_CHECK(hipMemcpyAsync(goff_.get(), off, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
     HIP_CHECK(hipStreamSynchronize(s_));
   }
-}
-
-void VifLaplace::GetMode(double* mode) {
-  HIP_CHECK(hipMemcpyAsync(mode, mode_.get(), sizeof(double) * n_, hipMemcpyDeviceToHost, s_));
-  HIP_CHECK(hipStreamSynchronize(s_));
 }
 
 void VifLaplace::ResetModeToPrevious() {
@@ -376,15 +332,14 @@ void VifLaplace::ToMN(const double* nm, double* mn) {
 
 void VifLaplace::RVec(const double* x, double* out, double* t) {
   V_->BVec(x, V_->Bv_.get(), 1., t);
-  hipLaunchKernelGGL(vl_mul_kernel, dim3((n_ + kT - 1) / kT), dim3(kT), 0, s_, n_, t, dinv_.get(), t);
-  HIP_CHECK(hipGetLastError());
+  launch_laplace_mul(n_, t, dinv_.get(), t, s_);
   V_->BtVec(t, V_->BvT_.get(), 1., out);
 }
 
 void VifLaplace::SpVec(const double* x, double* out, double* t, double* t2) {
   // S'_1 x = dB^T u + B^T D^-1 (dB x - dD o u), u = D^-1 B x (SigmaI_deriv, likelihoods.h:4758-4762)
   V_->BVec(x, V_->Bv_.get(), 1., t);
-  hipLaunchKernelGGL(vl_mul_kernel, dim3((n_ + kT - 1) / kT), dim3(kT), 0, s_, n_, t, dinv_.get(), t);
+  launch_laplace_mul(n_, t, dinv_.get(), t, s_);
   V_->BVec(x, V_->dBv1_.get(), 0., t2);
   hipLaunchKernelGGL(vl_zvec_kernel, dim3((n_ + kT - 1) / kT), dim3(kT), 0, s_, n_, t2, V_->dD1_.get(), t,
                      dinv_.get(), t2);
@@ -413,7 +368,7 @@ void VifLaplace::SpMat(const double* X, double* out, double* t, double* t2) {
 double VifLaplace::Objective(int lik, const double* mode, const double* upd, double lam, bool first, bool cap,
                              double* trial) {
   FitcSolver& F = *V_->F_;
-  const int n = n_, m = m_, ldm = ldm_, nb = nblk(n);
+  const int n = n_, m = m_, ldm = ldm_, nb = laplace_blocks(n);
   double* red = red_.get();
   double* t = vec_.get();
   double* mt = mv_.get();
@@ -488,7 +443,7 @@ LatentResult VifLaplace::Eval(int cov_type, int lik, const double* trafo, double
   const bool want_aux = want_aux_grad && want_grad && lik == kLikGamma;
   const bool grad_any = want_grad || grad_f != nullptr;
   FitcSolver& F = *V_->F_;
-  const int n = n_, m = m_, ldm = ldm_, nb = nblk(n);
+  const int n = n_, m = m_, ldm = ldm_, nb = laplace_blocks(n);
   const double var = trafo[0], phi = trafo[1];
   const double* off = has_off_ ? off_.get() : nullptr;
   const bool cap = lik == kLikPoisson || lik == kLikGamma;   // cap_change_mode_newton_ (likelihoods.h:481-490)
@@ -544,11 +499,9 @@ LatentResult VifLaplace::Eval(int cov_type, int lik, const double* trafo, double
   double obj = 0.;
   if (start != ModeStart::kKeep || !evaluated_) {
     obj = Objective(lik, mode_.get(), mode_.get(), 1., true, false, trial_.get());
-    const int maxit = 1000;                           // maxit_mode_newton_ (likelihoods.h:12721)
-    const double delta = cfg.delta_conv_mode_finding;  // :12723
-    bool terminate = false, has_nan = false;
-    int it = 0;
-    for (it = 0; it < maxit; ++it) {
+    const double delta = cfg.delta_conv_mode_finding;  // likelihoods.h:12723
+    bool has_nan = false;
+    for (int it = 0; it < kMaxItModeNewton; ++it) {
       // W, d1 at the mode; rhs = W mode + d1; A = R + W; M2 (:2561-2601)
       hipLaunchKernelGGL(vl_prep_kernel, dim3(nb), dim3(kT), 0, s_, n, lik, aux_, y_.get(), off, mode_.get(), d1_.get(),
                          w_.get(), static_cast<double*>(nullptr), rhs_.get(), static_cast<double*>(nullptr));
@@ -583,29 +536,16 @@ LatentResult VifLaplace::Eval(int cov_type, int lik, const double* trafo, double
         HIP_CHECK(hipStreamSynchronize(s_));
       }
       const double gdd = h_red_[8] - h_red_[10] + h_red_[9];
-      double lam = 1., obj_new = obj;
-      for (int ih = 0; ih < 20; ++ih) {   // max_number_lr_shrinkage_steps_newton_ (:12725)
-        obj_new = Objective(lik, mode_.get(), upd_.get(), lam, ih == 0, cap, trial_.get());
-        if (obj_new < obj + kCArmijo * lam * gdd || std::isnan(obj_new) || std::isinf(obj_new)) lam *= 0.5;
-        else break;
-      }
+      const LineSearchResult ls = newton_line_search(it, obj, gdd, delta, kMaxShrinkNewton, [&](double lam, int ih) {
+        return Objective(lik, mode_.get(), upd_.get(), lam, ih == 0, cap, trial_.get());
+      });
       std::swap(mode_, trial_);
-      // CheckConvergenceModeFinding (:11820-11870)
-      if (std::isnan(obj_new) || std::isinf(obj_new)) {
-        has_nan = true;
-        obj = obj_new;
-        break;
-      }
-      if (it == 0) terminate = std::abs(obj_new - obj) < delta * std::abs(obj);
-      else terminate = (obj_new - obj) < delta * std::abs(obj);
-      obj = obj_new;
-      if (terminate) {
-        ++it;
-        break;
-      }
+      res.newton_its = it + 1;
+      obj = ls.obj_new;
+      has_nan = ls.nan;
+      if (ls.nan || ls.terminate) break;
     }
     if (has_nan) throw LatentNan("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");
-    res.newton_its = it;
     cached_obj_ = obj;
   } else {
     obj = cached_obj_;
@@ -828,9 +768,7 @@ LatentResult VifLaplace::Eval(int cov_type, int lik, const double* trafo, double
       launch_sum_blocks(part_.get(), nb, 3, red + 40, s_);
       HIP_CHECK(hipMemcpyAsync(h_red_ + 40, red + 40, 3 * sizeof(double), hipMemcpyDeviceToHost, s_));
       HIP_CHECK(hipStreamSynchronize(s_));
-      const double a = aux_;
-      const double neg = a * (h_red_[40] - n * (std::log(a) + 1. - digamma_asa103(a)) - sum_log_y_);
-      res.grad.push_back(neg + 0.5 * h_red_[41] + h_red_[42]);
+      res.grad.push_back(gamma_shape_grad(aux_, n, h_red_[40], h_red_[41], h_red_[42], sum_log_y_));
     }
   }
   mark("gradient other");
@@ -1044,12 +982,12 @@ void VifLaplace::Predict(int cov_type, double var, double phi, const double* Xp,
   }
 }
 
-// ---- test launchers (lik_test.h): the launches of NewtonStep / Trial on nblk(n) blocks and their block sums
-int test_vl_blocks(int n) { return nblk(n); }
+// ---- test launchers (lik_test.h): the launches of NewtonStep / Trial on laplace_blocks(n) blocks and their block sums
+int test_vl_blocks(int n) { return laplace_blocks(n); }
 
 void test_vl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, double* d1,
                   double* W, double* dW, double* rhs, double* part, double* sum, hipStream_t s) {
-  const int nb = nblk(n);
+  const int nb = laplace_blocks(n);
   hipLaunchKernelGGL(vl_prep_kernel, dim3(nb), dim3(kT), 0, s, n, lik, aux, y, off, mode, d1, W, dW, rhs, part);
   HIP_CHECK(hipGetLastError());
   if (part) launch_sum_blocks(part, nb, 1, sum, s);
@@ -1057,7 +995,7 @@ void test_vl_prep(int n, int lik, double aux, const double* y, const double* off
 
 void test_vl_trial(int n, int lik, double aux, const double* y, const double* off, const double* mode, const double* upd,
                    double lam, int first, int cap, double* trial, double* part, double* sum, hipStream_t s) {
-  const int nb = nblk(n);
+  const int nb = laplace_blocks(n);
   hipLaunchKernelGGL(vl_trial_kernel, dim3(nb), dim3(kT), 0, s, n, lik, aux, y, off, mode, upd, lam, first, cap, trial,
                      part);
   HIP_CHECK(hipGetLastError());

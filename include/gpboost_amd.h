@@ -398,6 +398,15 @@ GPBOOST_AMD_EXPORT int GPB_PivotedCholeskyHost(const double* coords, int n, int 
                                                double phi, int rank, double tol, double* L, int* pivots,
                                                int* out_rank);
 
+/* The line search and convergence rule of the Laplace mode finding (likelihoods.h:1910-1928, 11820-11870) as every
+ * driver runs it, on a scripted sequence of trial objectives; needs no GPU. it: the Newton iteration, obj: the
+ * objective before the step, gdd: the Armijo slope, delta: delta_conv_mode_finding, max_shrink: the number of trials
+ * allowed; trial k returns trial_objs[k] (an error when more than n_trials are asked for). out (5 + n_trials):
+ * [objective of the last trial, its learning rate, trials used, terminate (0 / 1), NaN or Inf (0 / 1)], then the
+ * learning rate passed to each trial (NaN for the trials not run). No reference counterpart (tests). */
+GPBOOST_AMD_EXPORT int GPB_TestNewtonLineSearch(int it, double obj, double gdd, double delta, int max_shrink,
+                                                const double* trial_objs, int n_trials, double* out);
+
 /* The dense fp64 building blocks (C = alpha op(A) op(B) + beta C on MFMA tiles with triangle masks, its
  * split-K form, the blocked Cholesky with the triangular inverse and the log-determinant, the SPD solve /
  * inverse) on host arrays, one call each: column-major, copied to the device and back, synchronised. Extents

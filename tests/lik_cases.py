@@ -616,7 +616,7 @@ def prep_reference(lik, with_offset, stored_w):
 @functools.lru_cache(maxsize=None)
 def trial_reference(lik, with_offset, kind, lam, first, cap):
     """the trial mode and its log-likelihood term per pool sample. kind "vif": vl_trial_kernel (first, cap at
-    log 100); kind "mix": fl_trial_kernel / dl_trial_kernel (mnew, anew and the term a m of the quadratic form)"""
+    log 100); kind "mix": laplace_trial_kernel (mnew, anew and the term a m of the quadratic form)"""
     pl, aux, R = pool(lik, with_offset), PATH_AUX[lik], PoolRef()
     for k in range(POOL):
         y = float(pl["y"][k])

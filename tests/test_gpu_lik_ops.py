@@ -21,9 +21,10 @@ Largest error / bound measured on an MI355X (-s; 38 tests in 15 s):
   poisson .01 / .01 / .02 / .02, gamma .08 / .08 / .43 / .43.
   glp_obs_kernel<true> d1 .34, W .26, dW .26, sum loglik (with glp_finish_kernel, both forms) .25;
   vl_prep_kernel d1 .33, W .23, dW .22, rhs .32; vl_trial_kernel trial .24, sum loglik .13;
-  fl_prep_kernel d1 .33, W .23, wdw .27, DW .30, rhs .32; fl_trial_kernel mnew .20, anew .19, sum a m .32, sum loglik
-  .14; fl_final_kernel d1 .33, W .23, DW .29, dpwi .27, sum log dpwi .18, sum log W .09;
-  dl_prep_kernel d1 .33, W .23, sqrt W .28, rhs .32; dl_trial_kernel mnew .20, anew .19, sum a m .23, sum loglik .15;
+  fl_prep_kernel d1 .33, W .23, wdw .27, DW .30, rhs .32; laplace_trial_kernel (fitc path) mnew .20, anew .19,
+  sum a m .32, sum loglik .14; fl_final_kernel d1 .33, W .23, DW .29, dpwi .27, sum log dpwi .18, sum log W .09;
+  dl_prep_kernel d1 .33, W .23, sqrt W .28, rhs .32; laplace_trial_kernel (dense path) mnew .20, anew .19,
+  sum a m .23, sum loglik .15;
   dl_dmll_kernel dmll .11, dg .09;
   newton_prep_kernel d1 .33, W .23, rhs .32, dw .50, sdw .46; with an ObsMap d1 .32, W .23, rhs .32, dw .50, sdw .46.
 With the header as it was before (p (1 - p), y - p, y l - softplus(l); erfc until it returns 0) the same device misses
@@ -248,7 +249,7 @@ def test_fitc_prep_trial_and_final(lik):
                 _held("fl_prep_kernel DW", DW, *R.arrays("DW", idx), (what, w_update))
                 if want_rhs:
                     _held("fl_prep_kernel rhs", rhs, *R.arrays("rhs", idx), (what, w_update))
-        _mix_trial(lc.FITC, "fl_trial_kernel", lik, n, with_offset, idx, g, what)
+        _mix_trial(lc.FITC, "laplace_trial_kernel (fitc path)", lik, n, with_offset, idx, g, what)
         R = lc.prep_reference(lik, with_offset, False)
         runs = [lc.path_hook(lc.FITC, lc.FINAL, n, lik, aux, g["y"], g["mode"], g["off"], vecs=(g["dvec"],),
                              want=(1, 1, 1, 1), n_scalars=3) for _ in range(2)]
@@ -279,7 +280,7 @@ def test_dense_prep_trial_and_dmll(lik):
             _held("dl_prep_kernel sqrt W", ws, *R.arrays("ws", idx), what)
             if want_rhs:
                 _held("dl_prep_kernel rhs", rhs, *R.arrays("rhs", idx), what)
-        _mix_trial(lc.DENSE, "dl_trial_kernel", lik, n, with_offset, idx, g, what)
+        _mix_trial(lc.DENSE, "laplace_trial_kernel (dense path)", lik, n, with_offset, idx, g, what)
         if n > 1000:
             continue
         # dmll_j = 0.5 dg_j dinfo_j, dg_j = S_jj - sum_k C_kj^2 (a sum of n squares in any order)
