@@ -259,7 +259,9 @@ class GPModel:
         "gradient_descent" (Nesterov: use_nesterov_acc, acc_rate_cov, momentum_offset,
         nesterov_schedule_version) and "fisher_scoring" (Gaussian likelihood, no covariates);
         convergence_criterion as the reference's. Keys of the coefficient optimizers are accepted and
-        have no effect."""
+        have no effect, except "optimizer_coef" for grouped random effects models: it reaches the library, which
+        fits the covariates of a non-Gaussian model inside the L-BFGS vector and refuses any value but "lbfgs"
+        when covariates are given."""
         if params:
             for key, val in params.items():
                 if key == "init_aux_pars" and val is not None:
@@ -283,7 +285,9 @@ class GPModel:
             self.handle, _dp(init) if init is not None else None, float(p["lr_cov"]), float(p["acc_rate_cov"]),
             int(p["maxit"]), float(p["delta_rel_conv"]), bool(p["use_nesterov_acc"]),
             int(p["nesterov_schedule_version"]), bool(p["trace"]), c_str(p["optimizer_cov"]), int(p["momentum_offset"]),
-            c_str(p["convergence_criterion"]), 0, None, 0.1, 0.5, None,
+            c_str(p["convergence_criterion"]), 0, None, 0.1, 0.5,
+            # grouped models: the coefficient optimizer is checked when covariates are given ("lbfgs" only)
+            c_str(p.get("optimizer_coef")) if getattr(self, "num_group_re", 0) else None,
             int(p["cg_max_num_it"]), int(p["cg_max_num_it_tridiag"]), float(p["cg_delta_conv"]),
             int(p["num_rand_vec_trace"]), bool(p["reuse_rand_vec_trace"]),
             p["cg_preconditioner_type"].encode() if p["cg_preconditioner_type"] else None,
@@ -316,11 +320,12 @@ class GPModel:
                 raise ValueError("Incorrect number of data points in 'X'")
             if not np.all(np.isfinite(Xa)):
                 raise ValueError("'X' contains NaN or Inf")
+            xcol = np.ascontiguousarray(Xa.T).reshape(-1)   # column-major, as the reference passes it
+            self.has_covariates = False   # until the library has accepted them
+            self._call(lib().GPB_OptimLinRegrCoefCovPar(self.handle, _dp(y), _dp(xcol), ctypes.c_int(Xa.shape[1]),
+                                                        _dp(off) if off is not None else None))
             self.num_covariates = Xa.shape[1]
             self.has_covariates = True
-            xcol = np.ascontiguousarray(Xa.T).reshape(-1)   # column-major, as the reference passes it
-            self._call(lib().GPB_OptimLinRegrCoefCovPar(self.handle, _dp(y), _dp(xcol), ctypes.c_int(self.num_covariates),
-                                                        _dp(off) if off is not None else None))
         self.model_fitted = True
         return self
 
@@ -333,6 +338,32 @@ class GPModel:
         out = np.zeros(2 * p if std_err else p)
         _safe_call(lib().GPB_GetCoef(self.handle, _dp(out), ctypes.c_bool(std_err)))
         return out.reshape(2, -1) if std_err else out
+
+    def neg_log_likelihood_and_grad_coef(self, cov_pars, coef, y, X, offset=None, aux_pars=None):
+        """Grouped random effects with a non-Gaussian likelihood (GPB_EvalNegLogLikelihoodGradCoef): the
+        Laplace-approximated negative log-likelihood at cov_pars, coef (on X as given) and aux_pars (None: the
+        current ones), the mode found from zero. Returns (nll, grad wrt log cov_pars, grad wrt log aux_pars or None,
+        grad wrt coef = X^T grad_F)."""
+        cp = self._check_cov_pars(cov_pars)
+        yv = self._check_y(y)
+        Xa = np.asarray(X, dtype=np.float64)
+        if Xa.ndim == 1:
+            Xa = Xa.reshape(-1, 1)
+        if Xa.shape[0] != self.num_data:
+            raise ValueError("Incorrect number of data points in 'X'")
+        b = _as1d(coef, "coef")
+        if b.shape[0] != Xa.shape[1]:
+            raise ValueError("'coef' does not contain one coefficient per column of 'X'")
+        xcol = np.ascontiguousarray(Xa.T).reshape(-1)
+        off = _as1d(offset, "offset") if offset is not None else None
+        aux = _as1d(aux_pars, "aux_pars") if aux_pars is not None else None
+        nll = ctypes.c_double(0.)
+        gcov, gaux, gcoef = np.zeros(self.num_cov_pars), np.full(1, np.nan), np.zeros(Xa.shape[1])
+        _safe_call(lib().GPB_EvalNegLogLikelihoodGradCoef(
+            self.handle, _dp(cp), _dp(aux) if aux is not None else None, _dp(b), _dp(yv) if yv is not None else None,
+            _dp(xcol), ctypes.c_int(Xa.shape[1]), _dp(off) if off is not None else None, ctypes.byref(nll),
+            _dp(gcov), _dp(gaux), _dp(gcoef)))
+        return nll.value, gcov, (gaux if not np.isnan(gaux[0]) else None), gcoef
 
     def predict_training_data_random_effects(self, predict_var=False):
         """Predicted training-data random effects (GPB_PredictREModelTrainingDataRandomEffects,
@@ -414,6 +445,8 @@ class GPModel:
         if getattr(self, "model_fitted", False):
             ll = -self.get_current_neg_log_likelihood()
             npar = self.num_cov_pars
+            if getattr(self, "num_group_re", 0) and getattr(self, "has_covariates", False):
+                npar += self.num_covariates   # reference basic.py:5738-5739 (grouped models; GP models as before)
             aic = 2 * npar - 2 * ll
             bic = npar * np.log(self.num_data) - 2 * ll
             out = pd.DataFrame([[round(ll, 2), round(aic, 2), round(bic, 2)]], columns=["Log-lik", "AIC", "BIC"])
@@ -422,6 +455,16 @@ class GPModel:
         print("Covariance parameters (random effects):")
         print(pd.DataFrame(rows.T, index=self.cov_par_names(),
                            columns=["Param.", "Std. dev."] if std_err else ["Param."]).round(4).to_string())
+        if (getattr(self, "num_group_re", 0) and getattr(self, "has_covariates", False)
+                and getattr(self, "model_fitted", False)):
+            # grouped models with covariates; their standard deviations are not available for "iterative"
+            coef_std = bool(std_err) and self._get_string(lib().GPB_GetCGPreconditionerType) == ""
+            coef = self.get_coef(std_err=coef_std)
+            crow = coef if coef_std else coef.reshape(1, -1)
+            print("-----------------------------------------------------")
+            print("Linear regression coefficients (fixed effects):")
+            print(pd.DataFrame(crow.T, index=[f"Covariate_{j + 1}" for j in range(self.num_covariates)],
+                               columns=["Param.", "Std. dev."] if coef_std else ["Param."]).round(4).to_string())
         if self.num_aux_pars:
             aux, name = self.get_aux_pars()
             print("-----------------------------------------------------")
@@ -718,7 +761,7 @@ class GPModel:
                                        offset_pred, fixed_effects, fixed_effects_pred)
         if getattr(self, "num_group_re", 0):
             return self._predict_grouped(group_data_pred, predict_var, predict_cov_mat, predict_response, y, cov_pars,
-                                         offset, offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred)
+                                         offset, offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred, X_pred)
         if vecchia_pred_type is not None or num_neighbors_pred is not None:
             self.set_prediction_data(vecchia_pred_type=vecchia_pred_type, num_neighbors_pred=num_neighbors_pred)
         if any(v is not None for v in (group_data_pred, group_rand_coef_data_pred, gp_rand_coef_data_pred,
@@ -794,13 +837,14 @@ class GPModel:
         return {"mu": mu, "cov": cov, "var": var}
 
     def _predict_grouped(self, group_data_pred, predict_var, predict_cov_mat, predict_response, y, cov_pars, offset,
-                         offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred=None):
+                         offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred=None, X_pred=None):
         """Predictions of a grouped random effects model at new group labels (GPB_PredictREModel
         with re_group_data_pred): means = sum over the effects of the training posterior mean of the
         label's level (0 for a level not seen in training); with predict_var / predict_cov_mat
         (matrix_inversion_method = "cholesky") the predictive variances / covariance matrix. Non-Gaussian
         likelihoods: the means are sums of the Laplace mode's levels, predict_var gives the latent variances,
-        predict_response maps both through the likelihood (no covariance matrices)."""
+        predict_response maps both through the likelihood (no covariance matrices); a model fitted with
+        covariates needs X_pred, and X_pred beta joins the latent mean before the response transformation."""
         if group_data_pred is None:
             raise ValueError("'group_data_pred' is missing")
         g = np.asarray(group_data_pred)
@@ -830,13 +874,23 @@ class GPModel:
             if xp.shape[1] != self.dim_coords:
                 raise ValueError("'gp_coords_pred' must have %d columns (the dimension of 'gp_coords')" % self.dim_coords)
             xcol = np.ascontiguousarray(xp.T).reshape(-1)
+        xpc = None
+        if X_pred is not None:
+            Xp = np.asarray(X_pred, dtype=np.float64)
+            if Xp.ndim == 1:
+                Xp = Xp.reshape(-1, 1)
+            if Xp.shape[0] != n_pred:
+                raise ValueError("'X_pred' and 'group_data_pred' have different numbers of rows")
+            if self.has_covariates and Xp.shape[1] != self.num_covariates:
+                raise ValueError("Incorrect number of covariates (columns) in 'X_pred'")
+            xpc = np.ascontiguousarray(Xp.T).reshape(-1)
         size = n_pred + (n_pred * n_pred if predict_cov_mat else (n_pred if predict_var else 0))
         out = np.zeros(size)
         _safe_call(lib().GPB_PredictREModel(
             self.handle, _dp(yv) if yv is not None else None, ctypes.c_int32(n_pred), _dp(out),
             ctypes.c_bool(bool(predict_cov_mat)), ctypes.c_bool(bool(predict_var)),
             ctypes.c_bool(bool(predict_response)), None, buf, None, _dp(xcol) if xcol is not None else None, None,
-            _dp(cp) if cp is not None else None, None, ctypes.c_bool(False),
+            _dp(cp) if cp is not None else None, _dp(xpc) if xpc is not None else None, ctypes.c_bool(False),
             _dp(fe) if fe is not None else None, _dp(fep) if fep is not None else None))
         mu = out[:n_pred].copy()
         cov = out[n_pred:].reshape(n_pred, n_pred).T.copy() if predict_cov_mat else None

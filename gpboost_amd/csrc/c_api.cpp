@@ -16,6 +16,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "coef.h"
 #include "grouped_model.h"
 #include "laplace_newton.h"
 #include "latent_test.h"
@@ -250,9 +251,10 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
   // objective (optim_utils.h:656-657)
   (void)trace;
   (void)lr_coef; (void)acc_rate_coef;
-  if (GroupedModel* g = as_grouped(handle)) {   // no coefficients; aux parameters for the gamma likelihood only
+  if (GroupedModel* g = as_grouped(handle)) {   // coefficients: Laplace models, optimizer_coef "lbfgs"; aux: gamma only
     (void)piv_chol_rank;
-    (void)num_covariates; (void)init_coef; (void)optimizer_coef;
+    (void)num_covariates;
+    g->SetOptimizerCoef(optimizer_coef, init_coef != nullptr);   // checked when covariates are given
     if (g->laplace()) {
       g->SetPreconditioner(cg_preconditioner_type);
       if (delta_conv_mode_finding > 0.) g->iter.delta_conv_mode_finding = delta_conv_mode_finding;
@@ -272,6 +274,7 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
     g->iter.num_rand_vec_trace = num_rand_vec_trace;
     g->iter.seed_rand_vec_trace = seed_rand_vec_trace;
     g->iter.reuse_rand_vec_trace = reuse_rand_vec_trace;
+    g->SetCovParIndexGiven(estimate_cov_par_index != nullptr && estimate_cov_par_index[0] >= 0);
     if (estimate_cov_par_index != nullptr && estimate_cov_par_index[0] >= 0) {
       for (int k = 0; k < g->num_cov_pars(); ++k)
         if (estimate_cov_par_index[k] <= 0) gpb_amd::Fatal("estimate_cov_par_index: fixing covariance parameters is not supported by gpboost_amd");
@@ -367,7 +370,9 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
   const bool has_data = re_group_data_pred != nullptr || gp_coords_data_pred != nullptr || covariate_data_pred != nullptr;
   if (has_data) {
     if (num_data_pred <= 0) gpb_amd::Fatal("num_data_pred must be > 0 when prediction data is given");   // CHECK :3075
-    if (g != nullptr && ((gp_coords_data_pred != nullptr && !g->has_gp()) || covariate_data_pred != nullptr))
+    if (g != nullptr && gp_coords_data_pred != nullptr && !g->has_gp())
+      gpb_amd::Fatal("GP coordinates or covariates for a grouped random effects model are not supported by gpboost_amd");
+    if (g != nullptr && covariate_data_pred != nullptr && !g->laplace())
       gpb_amd::Fatal("GP coordinates or covariates for a grouped random effects model are not supported by gpboost_amd");
     if (g == nullptr && re_group_data_pred != nullptr)
       gpb_amd::Fatal("grouped random effects data for a GP model are not supported by gpboost_amd");
@@ -388,7 +393,7 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
       sp.gp_coords.assign(gp_coords_data_pred, gp_coords_data_pred + cnt);
     }
     if (covariate_data_pred != nullptr) {
-      const int p = model(handle)->num_covariates();
+      const int p = g != nullptr ? g->num_covariates() : model(handle)->num_covariates();
       if (p <= 0) gpb_amd::Fatal("Covariate data 'X_pred' is provided but the model has no covariates");
       sp.covariates.assign(covariate_data_pred, covariate_data_pred + (size_t)num_data_pred * p);
     }
@@ -434,9 +439,24 @@ int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_d
   }
   if (GroupedModel* g = as_grouped(handle)) {
     if (cluster_ids_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr ||
-        gp_rand_coef_data_pred != nullptr || covariate_data_pred != nullptr)
+        gp_rand_coef_data_pred != nullptr || (covariate_data_pred != nullptr && !g->laplace()))
       gpb_amd::Fatal("predictions with clusters, random coefficients or covariates are not supported "
                      "for grouped random effects models by gpboost_amd");
+    // Laplace models with covariates: the mode is found with the offset F + X beta (GroupedModel::
+    // SetResponseAndOffset) and X_pred beta joins fixed_effects_pred before the response transformation
+    std::vector<double> mean_add;
+    if (g->has_covariates()) {
+      if (covariate_data_pred == nullptr)
+        gpb_amd::Fatal("Covariate data 'X_pred' is not provided but the model has covariates");
+      if (num_data_pred <= 0) gpb_amd::Fatal("num_data_pred must be > 0");
+      mean_add.assign(num_data_pred, 0.);
+      g->AddLinearPredictor(covariate_data_pred, num_data_pred, mean_add.data());
+      if (fixed_effects_pred != nullptr)
+        for (int i = 0; i < num_data_pred; ++i) mean_add[i] += fixed_effects_pred[i];
+      fixed_effects_pred = mean_add.data();
+    } else if (covariate_data_pred != nullptr) {
+      gpb_amd::Fatal("Covariate data 'X_pred' is provided but the model has no covariates");
+    }
     g->Predict(y_data, num_data_pred, re_group_data_pred, gp_coords_data_pred, cov_pars, predict_cov_mat, predict_var,
                predict_response, fixed_effects, fixed_effects_pred, out_predict);
     return 0;
@@ -568,8 +588,12 @@ int GPB_OptimLinRegrCoefCovPar(REModelHandle handle, const double* y_data, const
   // c_api.cpp:2843-2852 -> REModel::OptimLinRegrCoefCovPar (re_model.cpp:403-469)
   API_BEGIN();
   if (GroupedModel* g = as_grouped(handle)) {
-    if (covariate_data != nullptr && num_covariates > 0)
-      gpb_amd::Fatal("linear regression covariates with grouped random effects are not supported by gpboost_amd");
+    if (covariate_data != nullptr && num_covariates > 0) {
+      if (!g->laplace() || g->has_gp())   // the Gaussian grouped model's GLS is not implemented
+        gpb_amd::Fatal("linear regression covariates with grouped random effects are not supported by gpboost_amd");
+      g->OptimLinRegrCoefCovPar(y_data, covariate_data, num_covariates, fixed_effects);
+      return 0;
+    }
     g->OptimCovPar(y_data, fixed_effects);
     return 0;
   }
@@ -624,7 +648,79 @@ int GPB_CanCalculateStandardErrorsCovPars(REModelHandle handle, int* out) {
 
 int GPB_GetCoef(REModelHandle handle, double* optim_coef, bool calc_std_dev) {
   API_BEGIN();
+  if (GroupedModel* g = as_grouped(handle)) {
+    g->GetCoef(optim_coef, calc_std_dev);
+    return 0;
+  }
   model(handle)->GetCoef(optim_coef, calc_std_dev);
+  API_END();
+}
+
+int GPB_GetNumCoef(REModelHandle handle, int* num_coef) {
+  API_BEGIN();
+  if (num_coef == nullptr) gpb_amd::Fatal("GPB_GetNumCoef: num_coef is NULL");
+  GroupedModel* g = as_grouped(handle);
+  num_coef[0] = g != nullptr ? g->num_covariates() : model(handle)->num_covariates();
+  API_END();
+}
+
+int GPB_EvalNegLogLikelihoodGradCoef(REModelHandle handle, const double* cov_pars, const double* aux_pars,
+                                     const double* coef, const double* y_data, const double* covariate_data,
+                                     int num_covariates, const double* fixed_effects, double* negll, double* grad_cov,
+                                     double* grad_aux, double* grad_coef) {
+  API_BEGIN();
+  GroupedModel* g = as_grouped(handle);
+  if (g == nullptr)
+    gpb_amd::Fatal("GPB_EvalNegLogLikelihoodGradCoef: the model needs grouped random effects with a non-Gaussian "
+                   "likelihood");
+  if (negll == nullptr || grad_coef == nullptr) gpb_amd::Fatal("GPB_EvalNegLogLikelihoodGradCoef: NULL argument");
+  negll[0] = g->EvalGradCoef(cov_pars, aux_pars, coef, y_data, covariate_data, num_covariates, fixed_effects, grad_cov,
+                             grad_aux, grad_coef);
+  API_END();
+}
+
+int GPB_TestCoefOps(int n, int p, const double* X, const double* beta, const double* dir, const double* F,
+                    const double* gF, double* eta0, double* g, double* mom) {
+  API_BEGIN();
+  gpb_amd::test_coef_ops(n, p, X, beta, dir, F, gF, eta0, g, mom);
+  API_END();
+}
+
+int GPB_TestCoefHost(int op, int lik, int n, int p, const double* X, const double* y, const double* F,
+                     const double* in, double* out) {
+  // host only: 0 scaling (out = [intercept_col, scaled, loc (p), scale (p), scaled X row-major (n p)]);
+  // 1 / 2 TransformCoef / TransformBackCoef of in (p) -> out (p); 3 the initial intercept with in[0] = the random
+  // effects' total variance -> out[0]; 4 C_mu, C_sigma2 -> out[0 .. 1]; 5 the step cap from in = [4 sums, C_mu,
+  // C_sigma2] over n observations -> out[0]
+  API_BEGIN();
+  if (out == nullptr) gpb_amd::Fatal("GPB_TestCoefHost: out is NULL");
+  if (op >= 0 && op <= 2) {
+    std::vector<double> Xs;
+    const gpb_amd::CoefScaling sc(n, p, X, op == 0 ? &Xs : nullptr);
+    if (op == 0) {
+      out[0] = sc.intercept_col;
+      out[1] = sc.scaled ? 1. : 0.;
+      std::copy(sc.loc.begin(), sc.loc.end(), out + 2);
+      std::copy(sc.scale.begin(), sc.scale.end(), out + 2 + p);
+      std::copy(Xs.begin(), Xs.end(), out + 2 + 2 * p);
+    } else {
+      if (in == nullptr) gpb_amd::Fatal("GPB_TestCoefHost: in is NULL");
+      const std::vector<double> b(in, in + p);
+      const std::vector<double> r = op == 1 ? sc.ToScaled(b) : sc.ToOriginal(b);
+      std::copy(r.begin(), r.end(), out);
+    }
+  } else if (op == 3) {
+    if (y == nullptr || in == nullptr || n < 1) gpb_amd::Fatal("GPB_TestCoefHost: invalid argument");
+    out[0] = gpb_amd::coef_initial_intercept(lik, n, y, F, in[0]);
+  } else if (op == 4) {
+    if (y == nullptr || n < 1) gpb_amd::Fatal("GPB_TestCoefHost: invalid argument");
+    gpb_amd::coef_cap_constants(lik, n, y, out, out + 1);
+  } else if (op == 5) {
+    if (in == nullptr || n < 1) gpb_amd::Fatal("GPB_TestCoefHost: invalid argument");
+    out[0] = gpb_amd::coef_max_learning_rate(in, n, in[4], in[5]);
+  } else {
+    gpb_amd::Fatal("GPB_TestCoefHost: unknown op %d", op);
+  }
   API_END();
 }
 
@@ -652,8 +748,8 @@ int GPB_GetOptimizerCovPars(REModelHandle handle, char* out_str, int* num_char) 
 
 int GPB_GetOptimizerCoef(REModelHandle handle, char* out_str, int* num_char) {
   API_BEGIN();
-  if (as_grouped(handle) != nullptr) {
-    copy_name("wls", out_str, num_char);
+  if (GroupedModel* g = as_grouped(handle)) {   // a Laplace model fitted with covariates: they sat in the L-BFGS vector
+    copy_name(g->has_covariates() ? g->optimizer_coef() : "wls", out_str, num_char);
     return 0;
   }
   copy_name(model(handle)->optimizer_coef(), out_str, num_char);
@@ -1051,6 +1147,10 @@ int GPB_GetResponseData(REModelHandle handle, double* response_data) {
 
 int GPB_GetCovariateData(REModelHandle handle, double* covariate_data) {
   API_BEGIN();
+  if (GroupedModel* g = as_grouped(handle)) {
+    g->GetCovariateData(covariate_data);
+    return 0;
+  }
   model(handle)->GetCovariateData(covariate_data);
   API_END();
 }

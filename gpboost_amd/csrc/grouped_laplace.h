@@ -60,6 +60,14 @@ class GroupedLaplace {
 
   void SetY(const double* y);              // host, n
   void SetOffset(const double* offset);    // host, n; null: none
+  // Device form of SetOffset: the offset buffer (n doubles on stream()) for the caller to fill before Eval; the
+  // model has an offset from this call on, until SetOffset(nullptr).
+  double* DeviceOffset();
+  // Device access to the gradient wrt the fixed effects: with keep, every Eval with want_grad leaves it in
+  // DeviceGradF() (n doubles, valid after Eval returns) whether or not a host grad_f is given.
+  void KeepDeviceGradF(bool keep) { keep_gradf_ = keep; }
+  const double* DeviceGradF() const { return d_gradf_.get(); }
+  hipStream_t stream() const { return s_; }
   // sigma2: the K variances. grad_f (host n, nullable; needs want_grad): gradient wrt the fixed effects.
   // iterative (K >= 2; likelihoods.h:2019-2048, 2094-2180, 3467-3633): the Newton systems by SSOR-PCG (the first
   // solve of an evaluation from zero, later ones from the previous update), log|A| by SLQ on probes from N(0, P),
@@ -95,7 +103,7 @@ class GroupedLaplace {
   DevBuf<double> d_mode_, d_mode_new_, d_mode_prev_, d_upd_, d_rhs_, d_ztd1_, d_ztwz_, d_D_, d_dmll_, d_vS_;
   DevBuf<double> d_partial_, d_red_, d_dis_, d_blkA_, d_blkB_;
   double* h_red_ = nullptr;   // pinned
-  bool has_off_ = false, y_set_ = false, mode_prev_valid_ = false, evaluated_ = false;
+  bool has_off_ = false, keep_gradf_ = false, y_set_ = false, mode_prev_valid_ = false, evaluated_ = false;
   double lognorm_ = 0., sum_log_y_ = 0.;
   hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
 };

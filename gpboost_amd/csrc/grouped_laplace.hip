@@ -368,6 +368,12 @@ void GroupedLaplace::SetOffset(const double* offset) {
   HIP_CHECK(hipStreamSynchronize(s_));
 }
 
+double* GroupedLaplace::DeviceOffset() {
+  d_off_.alloc(v_.n);
+  has_off_ = true;
+  return d_off_.get();
+}
+
 double GroupedLaplace::LogLikConst(double aux) const {
   if (lik_ == kLikPoisson) return lognorm_;
   if (lik_ == kLikGamma)   // likelihoods.h:8181-8191
@@ -605,12 +611,13 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
   glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_vS_.get(), d_ztd1_.get(), d_red_.get() + kGlpMaxK);
   glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_mode_.get(), d_mode_.get(), d_red_.get() + 2 * kGlpMaxK);
   HIP_CHECK(hipGetLastError());
-  if (grad_f != nullptr) {
+  if (grad_f != nullptr || keep_gradf_) {
     d_gradf_.alloc(n);
     glp_grad_f_kernel<<<blocks_of(n), 256, 0, s_>>>(n, K, d_glev_.get(), d_d1_.get(), d_dwq_.get(), d_W_.get(),
                                                     d_vS_.get(), d_gradf_.get());
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(grad_f, d_gradf_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
+    if (grad_f != nullptr)
+      HIP_CHECK(hipMemcpyAsync(grad_f, d_gradf_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
   }
   HIP_CHECK(hipMemcpyAsync(h_red_, d_red_.get(), sizeof(double) * 3 * kGlpMaxK, hipMemcpyDeviceToHost, s_));
   HIP_CHECK(hipStreamSynchronize(s_));

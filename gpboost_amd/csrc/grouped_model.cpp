@@ -138,7 +138,13 @@ void GroupedModel::SetResponseAndOffset(const double* y, const double* fixed_eff
       if (std::isnan(y_raw_[i]) || std::isinf(y_raw_[i])) Fatal("NaN or Inf in response variable / label ");
     UseDevice();
     if (y != nullptr) lap_->SetY(y_raw_.data());
-    lap_->SetOffset(fixed_effects);
+    if (has_covariates()) {   // the location parameter's offset is F + X beta (has_covariates_, re_model_template.h:3306-3312)
+      std::vector<double> off(n_);
+      coef_->LinearPredictor(beta_.data(), fixed_effects, off.data());
+      lap_->SetOffset(off.data());
+    } else {
+      lap_->SetOffset(fixed_effects);
+    }
     y_set_ = true;
     return;
   }
@@ -778,22 +784,30 @@ namespace {
 // stands (eval_likelihood = false, optim_utils.h:314-330), as LatentObjective (optim.cpp) does.
 class GroupedLaplaceObjective : public LbfgsObjective {
  public:
-  GroupedLaplaceObjective(GroupedModel* m, int K, bool with_aux) : m_(m), K_(K), with_aux_(with_aux) {}
+  // p > 0: x = [log sigma^2 (K), beta (p, on the scaled covariates), log shape]; every evaluation writes the offset
+  // F + X beta on the device first (UpdateFixedEffects) and the coefficient gradient is X^T grad_F (CalcGradPars)
+  GroupedLaplaceObjective(GroupedModel* m, int K, bool with_aux, int p = 0) : m_(m), K_(K), p_(p), with_aux_(with_aux) {}
   double Eval(const std::vector<double>& x, std::vector<double>& grad, bool eval_ll, bool calc_grad,
               bool hint_grad) override {
     if (eval_ll || !(has_grad_ && x == x_)) {
       std::vector<double> s2(K_);
       for (int k = 0; k < K_; ++k) s2[k] = std::exp(x[k]);
       if (with_aux_) {
-        const double aux = std::exp(x[K_]);
+        const double aux = std::exp(x[K_ + p_]);
         m_->SetAuxPars(&aux);
       }
+      if (p_ > 0) m_->CoefWriteOffset(x.data() + K_);
       const bool grad_only = !eval_ll && has_x_ && x == x_;
       EvalResult r = m_->EvalLaplace(s2.data(), calc_grad || hint_grad,
                                      grad_only ? GroupedLaplace::Start::kKeep : GroupedLaplace::Start::kWarm,
                                      /*fatal_on_nan=*/false);
       has_x_ = true;
       bool bad = !std::isfinite(r.nll);
+      if (p_ > 0 && (calc_grad || hint_grad) && (int)r.grad.size() >= K_) {   // [cov, beta, aux]
+        std::vector<double> gb(p_);
+        m_->CoefGradient(gb.data());
+        r.grad.insert(r.grad.begin() + K_, gb.begin(), gb.end());
+      }
       for (double g : r.grad) bad = bad || !std::isfinite(g);
       if (bad) m_->ResetLaplaceModeToPrevious();   // EvalLLforLBFGSpp, optim_utils.h:349-360
       x_ = x;
@@ -807,10 +821,19 @@ class GroupedLaplaceObjective : public LbfgsObjective {
     if (calc_grad) grad = grad_;
     return nll_;
   }
+  double MaxLearningRate(const std::vector<double>& x, const std::vector<double>& drt, double max_log_change) override {
+    if (p_ == 0) return LbfgsObjective::MaxLearningRate(x, drt, max_log_change);
+    double max_abs = 0.;   // MaximalLearningRateCovAuxPars over the covariance and auxiliary entries
+    for (size_t i = 0; i < drt.size(); ++i)
+      if ((int)i < K_ || (int)i >= K_ + p_) max_abs = std::max(max_abs, std::fabs(drt[i]));
+    const double max_lr = max_log_change / max_abs;
+    const double max_lr_beta = m_->CoefMaxLearningRate(x.data() + K_, drt.data() + K_);
+    return max_lr_beta < max_lr ? max_lr_beta : max_lr;
+  }
 
  private:
   GroupedModel* m_;
-  int K_;
+  int K_, p_;
   bool with_aux_;
   std::vector<double> x_, grad_;
   double nll_ = 0.;
@@ -819,17 +842,34 @@ class GroupedLaplaceObjective : public LbfgsObjective {
 
 }  // namespace
 
-void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effects) {
+void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effects, bool with_coef) {
   if (y == nullptr && y_raw_.empty()) Fatal("response variable y has not been set");
   const std::vector<double> yraw(y != nullptr ? y : y_raw_.data(), (y != nullptr ? y : y_raw_.data()) + n_);
+  beta_.clear();   // no coefficients until this fit has estimated them
+  if (!with_coef) coef_.reset();
   SetResponseAndOffset(yraw.data(), fixed_effects);
   const int K = re_->K();
+  const int p = with_coef ? coef_->p() : 0;
   num_iter_ = 0;
   // FindInitCovPar for non-Gaussian data (re_model_template.h:4440-4451): marginal variance 1 / num_comps each
   std::vector<double> s2(K, 1. / K);
   if (cov_pars_initialized_) s2 = cov_pars_orig_;
   else init_used_ = s2;
   const bool with_aux = !aux_pars_.empty() && estimate_aux_pars;
+  const double* orig_fixed_effects = fixed_effects;
+  if (fixed_effects != nullptr) fit_offset_.assign(fixed_effects, fixed_effects + n_);
+  else fit_offset_.clear();
+  // initial coefficients (re_model_template.h:1108-1153): 0, the intercept from FindInitialIntercept with the total
+  // variance of the initial covariance parameters; the shape below is found with the offset F + X beta_init
+  std::vector<double> beta_scaled, off_init;
+  if (with_coef) {
+    double tot_var = 0.;
+    for (double v : s2) tot_var += v;
+    beta_scaled = coef_->Init(lik_, yraw.data(), fixed_effects, tot_var);
+    off_init.resize(n_);
+    coef_->LinearPredictor(beta_scaled.data(), fixed_effects, off_init.data());   // only the intercept is non-zero
+    fixed_effects = off_init.data();
+  }
   if (with_aux && !aux_pars_set_) {
     // FindInitialAuxPars, gamma (likelihoods.h:1116-1145): approximate MLE of the shape ignoring the random
     // effects, s = log(mean y e^-F) - mean(log y - F), k = (3 - s + sqrt((s - 3)^2 + 24 s)) / (12 s)
@@ -850,22 +890,41 @@ void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effec
     cov_pars_orig_ = s2;
     cov_pars_initialized_ = true;
     last_cov_pars_ = cov_pars_orig_;
+    if (with_coef) {
+      beta_ = coef_->ToOriginal(beta_scaled);
+      RefreshCoefOffset();
+    }
     return;
   }
   std::vector<double> x(K);
   for (int k = 0; k < K; ++k) x[k] = std::log(s2[k]);
+  x.insert(x.end(), beta_scaled.begin(), beta_scaled.end());
   if (with_aux) x.push_back(std::log(aux_pars_[0]));
   double fx = 0.;
   lap_->ClearModePrevious();
-  GroupedLaplaceObjective obj(this, K, with_aux);
-  num_it_ = lbfgs_minimize(obj, x, fx, optim_);
+  if (with_coef) {
+    coef_->SetF(orig_fixed_effects);
+    lap_->KeepDeviceGradF(true);
+  }
+  GroupedLaplaceObjective obj(this, K, with_aux, p);
+  try {
+    num_it_ = lbfgs_minimize(obj, x, fx, optim_);
+  } catch (...) {
+    lap_->KeepDeviceGradF(false);
+    throw;
+  }
+  lap_->KeepDeviceGradF(false);
   for (double v : x)
     if (std::isnan(v) || std::isinf(v))
       Fatal("NaN or Inf occurred in covariance parameter optimization using 'lbfgs' (the reference's nelder_mead "
             "restart is not supported by gpboost_amd)");
   cov_pars_orig_.assign(K, 0.);
   for (int k = 0; k < K; ++k) cov_pars_orig_[k] = std::exp(x[k]);
-  if (with_aux) aux_pars_[0] = std::exp(x[K]);
+  if (with_aux) aux_pars_[0] = std::exp(x[K + p]);
+  if (with_coef) {   // TransformBackCoef (:1604-1612); the device offset already holds F + X beta at the optimum
+    beta_ = coef_->ToOriginal(std::vector<double>(x.begin() + K, x.begin() + K + p));
+    RefreshCoefOffset();
+  }
   cov_pars_initialized_ = true;
   last_nll_ = fx;
   last_cov_pars_ = cov_pars_orig_;
@@ -952,6 +1011,180 @@ void GroupedModel::PredictLaplace(const double* y, int n_pred, const char* re_gr
                        mu.data(), var.data(), nullptr);
   std::copy(mu.begin(), mu.end(), out);
   if (predict_var) std::copy(var.begin(), var.end(), out + n_pred);
+}
+
+// ---- linear regression coefficients of Laplace models (CoefLayer, coef.h)
+
+void GroupedModel::SetOptimizerCoef(const char* optimizer_coef, bool init_coef_given) {
+  optimizer_coef_ = optimizer_coef != nullptr && optimizer_coef[0] != '\0' ? optimizer_coef : "lbfgs";
+  init_coef_given_ = init_coef_given;
+}
+
+void GroupedModel::RefreshCoefOffset() {
+  std::vector<double> off(n_);
+  coef_->LinearPredictor(beta_.data(), fit_offset_.empty() ? nullptr : fit_offset_.data(), off.data());
+  UseDevice();
+  lap_->SetOffset(off.data());
+}
+
+void GroupedModel::CoefWriteOffset(const double* beta) { coef_->WriteOffset(beta, lap_->DeviceOffset()); }
+void GroupedModel::CoefGradient(double* grad_beta) { coef_->Gradient(lap_->DeviceGradF(), grad_beta); }
+double GroupedModel::CoefMaxLearningRate(const double* beta, const double* dir) {
+  return coef_->MaxLearningRate(beta, dir);
+}
+
+void GroupedModel::OptimLinRegrCoefCovPar(const double* y, const double* X, int p, const double* fixed_effects) {
+  if (!laplace() || has_gp())
+    Fatal("linear regression covariates with grouped random effects are not supported by gpboost_amd");
+  if (optimizer_coef_ != "lbfgs")
+    Fatal("optimizer_coef = '%s' is not supported for likelihood '%s' with grouped random effects by gpboost_amd "
+          "(supported: lbfgs)", optimizer_coef_.c_str(), likelihood_.c_str());
+  if (init_coef_given_)
+    Fatal("init_coef is not supported for grouped random effects models by gpboost_amd (the coefficients start at 0, "
+          "the intercept at the reference's initial value)");
+  if (cov_par_index_given_)
+    Fatal("estimate_cov_par_index together with linear regression covariates is not supported for grouped random "
+          "effects by gpboost_amd");
+  if (p > kCoefMaxCols)
+    Fatal("num_covariates = %d is not supported for likelihood '%s' with grouped random effects by gpboost_amd (at "
+          "most %d)", p, likelihood_.c_str(), kCoefMaxCols);
+  UseDevice();
+  beta_.clear();
+  coef_.reset(new CoefLayer(n_, p, X, lap_->stream()));
+  try {
+    OptimCovParLaplace(y, fixed_effects, /*with_coef=*/true);
+  } catch (...) {
+    beta_.clear();
+    coef_.reset();
+    throw;
+  }
+}
+
+void GroupedModel::GetCovariateData(double* out) const {
+  if (coef_ == nullptr) Fatal("Model does not have covariates for a linear predictor");
+  std::copy(coef_->X_colmajor().begin(), coef_->X_colmajor().end(), out);
+}
+
+void GroupedModel::AddLinearPredictor(const double* X_pred, int n_pred, double* mean_add) const {
+  if (!has_covariates()) Fatal("Model does not have covariates for a linear predictor");
+  for (int j = 0; j < coef_->p(); ++j)
+    for (int i = 0; i < n_pred; ++i) mean_add[i] += X_pred[(size_t)j * n_pred + i] * beta_[j];
+}
+
+double GroupedModel::EvalGradCoef(const double* cov_pars, const double* aux, const double* coef, const double* y,
+                                  const double* X, int p, const double* fixed_effects, double* grad_cov,
+                                  double* grad_aux, double* grad_coef) {
+  if (!laplace() || has_gp())
+    Fatal("GPB_EvalNegLogLikelihoodGradCoef: the model needs grouped random effects with a non-Gaussian likelihood");
+  if (cov_pars == nullptr || coef == nullptr || X == nullptr) Fatal("GPB_EvalNegLogLikelihoodGradCoef: NULL argument");
+  if (p > kCoefMaxCols)
+    Fatal("num_covariates = %d is not supported for likelihood '%s' with grouped random effects by gpboost_amd (at "
+          "most %d)", p, likelihood_.c_str(), kCoefMaxCols);
+  const int K = re_->K();
+  const std::vector<double> cp = LaplaceCovPars(cov_pars);
+  UseDevice();
+  if (y != nullptr) {   // the response alone: the offset is written on the device below
+    for (int i = 0; i < n_; ++i)
+      if (std::isnan(y[i]) || std::isinf(y[i])) Fatal("NaN or Inf in response variable / label ");
+    y_raw_.assign(y, y + n_);
+    lap_->SetY(y_raw_.data());
+    y_set_ = true;
+  }
+  if (!y_set_) Fatal("response variable y has not been set");
+  if (aux != nullptr && !aux_pars_.empty()) {
+    if (!(aux[0] > 0.)) Fatal("aux_pars must be > 0");
+    SetAuxPars(aux);
+  }
+  CoefLayer layer(n_, p, X, lap_->stream(), /*transform=*/false);
+  layer.SetF(fixed_effects);
+  EvalResult r;
+  try {
+    layer.WriteOffset(coef, lap_->DeviceOffset());
+    lap_->KeepDeviceGradF(true);
+    r = EvalLaplace(cp.data(), true, GroupedLaplace::Start::kZero, true);
+    layer.Gradient(lap_->DeviceGradF(), grad_coef);
+  } catch (...) {
+    lap_->KeepDeviceGradF(false);
+    if (has_covariates()) RefreshCoefOffset();
+    throw;
+  }
+  lap_->KeepDeviceGradF(false);
+  if (grad_cov != nullptr)
+    for (int k = 0; k < K; ++k) grad_cov[k] = r.grad[k];
+  if (grad_aux != nullptr && (int)r.grad.size() > K) grad_aux[0] = r.grad[K];
+  last_cov_pars_ = cp;
+  if (has_covariates()) RefreshCoefOffset();   // the model's own offset again
+  return r.nll;
+}
+
+void GroupedModel::GetCoef(double* out, bool calc_std_dev) {
+  if (!has_covariates()) Fatal("Model does not have covariates for a linear predictor");
+  const int p = coef_->p();
+  std::copy(beta_.begin(), beta_.end(), out);
+  if (!calc_std_dev) return;
+  if (iterative())
+    Fatal("standard deviations of the regression coefficients (std_err) for matrix_inversion_method = 'iterative' are "
+          "not supported by gpboost_amd (use 'cholesky')");
+  // CalcStdDevCoefNonGaussian (re_model_template.h:9825-9854): H = Jacobian of grad_beta by central differences with
+  // step beta_i eps^(1/3) on the unscaled X, symmetrised; sd = sqrt(diag(H^-1))
+  UseDevice();
+  const std::vector<double> cp = LaplaceCovPars(nullptr);
+  CoefLayer layer(n_, p, coef_->X_colmajor().data(), lap_->stream(), /*transform=*/false);
+  layer.SetF(fit_offset_.empty() ? nullptr : fit_offset_.data());
+  const double eps3 = std::cbrt(std::numeric_limits<double>::epsilon());
+  std::vector<double> H((size_t)p * p), gp(p), gm(p);
+  const double nll_fit = last_nll_;   // the evaluations below are not the model's current likelihood
+  lap_->KeepDeviceGradF(true);
+  try {
+    for (int i = 0; i < p; ++i) {
+      const double step = beta_[i] * eps3;
+      std::vector<double> b = beta_;
+      b[i] = beta_[i] + step;
+      layer.WriteOffset(b.data(), lap_->DeviceOffset());
+      EvalLaplace(cp.data(), true, GroupedLaplace::Start::kWarm, true);
+      layer.Gradient(lap_->DeviceGradF(), gp.data());
+      b[i] = beta_[i] - step;
+      layer.WriteOffset(b.data(), lap_->DeviceOffset());
+      EvalLaplace(cp.data(), true, GroupedLaplace::Start::kWarm, true);
+      layer.Gradient(lap_->DeviceGradF(), gm.data());
+      for (int j = 0; j < p; ++j) H[(size_t)i * p + j] = (gp[j] - gm[j]) / (2. * step);
+    }
+  } catch (...) {
+    lap_->KeepDeviceGradF(false);
+    throw;
+  }
+  lap_->KeepDeviceGradF(false);
+  last_nll_ = nll_fit;
+  RefreshCoefOffset();
+  std::vector<double> S((size_t)p * p), inv((size_t)p * p, 0.);
+  for (int i = 0; i < p; ++i)
+    for (int j = 0; j < p; ++j) S[(size_t)i * p + j] = 0.5 * (H[(size_t)i * p + j] + H[(size_t)j * p + i]);
+  // Hsym.inverse(): Gauss-Jordan with partial pivoting on the small p x p matrix
+  for (int i = 0; i < p; ++i) inv[(size_t)i * p + i] = 1.;
+  for (int c = 0; c < p; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < p; ++r)
+      if (std::fabs(S[(size_t)r * p + c]) > std::fabs(S[(size_t)piv * p + c])) piv = r;
+    const double d = S[(size_t)piv * p + c];
+    if (!(d != 0.) || !std::isfinite(d)) Fatal("the numerical Hessian of the regression coefficients is singular");
+    for (int j = 0; j < p; ++j) {
+      std::swap(S[(size_t)c * p + j], S[(size_t)piv * p + j]);
+      std::swap(inv[(size_t)c * p + j], inv[(size_t)piv * p + j]);
+    }
+    for (int j = 0; j < p; ++j) {
+      S[(size_t)c * p + j] /= d;
+      inv[(size_t)c * p + j] /= d;
+    }
+    for (int r = 0; r < p; ++r) {
+      if (r == c) continue;
+      const double f = S[(size_t)r * p + c];
+      for (int j = 0; j < p; ++j) {
+        S[(size_t)r * p + j] -= f * S[(size_t)c * p + j];
+        inv[(size_t)r * p + j] -= f * inv[(size_t)c * p + j];
+      }
+    }
+  }
+  for (int i = 0; i < p; ++i) out[p + i] = std::sqrt(inv[(size_t)i * p + i]);
 }
 
 }  // namespace gpb_amd

@@ -14,6 +14,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "coef.h"
 #include "grouped.h"
 #include "grouped_laplace.h"
 #include "optim.h"
@@ -99,6 +100,36 @@ class GroupedModel {
   // OptimCovPar (re_model.cpp:339-401 -> OptimExternal "lbfgs", optim_utils.h:561-706): L-BFGS on
   // log tau with sigma^2 profiled out (EvalLLforLBFGSpp, optim_utils.h:269-313).
   void OptimCovPar(const double* y, const double* fixed_effects);
+  // OptimLinRegrCoefCovPar for Laplace models (re_model_template.h:926-1647 with optimizer_cov = optimizer_coef =
+  // "lbfgs"): the coefficients of the p covariates X (column-major n x p, p <= 31) join the L-BFGS vector as
+  // [log cov pars, beta, log aux pars] (EvalLLforLBFGSpp, optim_utils.h:243-364), on centred and scaled covariates
+  // (CoefLayer, coef.h); the offset F + X beta and the gradient X^T grad_F stay on the device.
+  void OptimLinRegrCoefCovPar(const double* y, const double* X, int p, const double* fixed_effects);
+  bool has_covariates() const { return coef_ != nullptr && !beta_.empty(); }
+  int num_covariates() const { return has_covariates() ? coef_->p() : 0; }
+  // coefficients on the original scale; calc_std_dev: then their standard deviations by central differences of the
+  // coefficient gradient (CalcStdDevCoefNonGaussian, re_model_template.h:9825-9854; K == 1 and cholesky)
+  void GetCoef(double* out, bool calc_std_dev);
+  void GetCovariateData(double* out) const;
+  // mean_add[i] += sum_j X_pred[i, j] beta_j (X_pred column-major n_pred x p)
+  void AddLinearPredictor(const double* X_pred, int n_pred, double* mean_add) const;
+  // GPB_EvalNegLogLikelihoodGradCoef: one evaluation at the given parameters and coefficients on the unscaled X
+  // (column-major n x p), the mode started from zero; grad = [d/dlog cov pars (K), d/dlog aux (if estimated)],
+  // grad_coef = X^T grad_F (p). Like GPB_EvalNegLogLikelihood it is an evaluation of the model: y (when given)
+  // becomes the stored response, aux (when given) the auxiliary parameters, cov_pars the last evaluated ones. The
+  // covariates and coefficients of a fit stay, and the fit's offset F + X beta is put back before the call returns
+  // or throws; a model without fitted coefficients is left with the offset fixed_effects + X coef, as after a call
+  // that gives fixed_effects.
+  double EvalGradCoef(const double* cov_pars, const double* aux, const double* coef, const double* y, const double* X,
+                      int p, const double* fixed_effects, double* grad_cov, double* grad_aux, double* grad_coef);
+  // NULL or "": the default ("lbfgs" for Laplace models)
+  void SetOptimizerCoef(const char* optimizer_coef, bool init_coef_given);
+  const std::string& optimizer_coef() const { return optimizer_coef_; }
+  void SetCovParIndexGiven(bool given) { cov_par_index_given_ = given; }
+  // hooks of the L-BFGS objective: beta on the optimizer's (scaled) scale
+  void CoefWriteOffset(const double* beta);
+  void CoefGradient(double* grad_beta);
+  double CoefMaxLearningRate(const double* beta, const double* dir);
   void SetNumIter(int it) { num_iter_ = it; }
   int num_it() const { return num_it_; }
   double last_nll() const { return last_nll_; }
@@ -156,11 +187,18 @@ class GroupedModel {
   int lik_ = 0;
   std::vector<double> aux_pars_, init_aux_pars_;
   bool aux_pars_set_ = false;
-  void OptimCovParLaplace(const double* y, const double* fixed_effects);
+  // with_coef: coef_ holds the covariates of this fit and beta joins the optimizer's vector
+  void OptimCovParLaplace(const double* y, const double* fixed_effects, bool with_coef = false);
   void PredictLaplace(const double* y, int n_pred, const char* re_group_data_pred, const double* cov_pars,
                       bool predict_var, bool predict_response, const double* fixed_effects,
                       const double* fixed_effects_pred, double* out);
   std::vector<double> LaplaceCovPars(const double* cov_pars) const;
+  // linear regression coefficients (Laplace models): the layer of the last fit and its coefficients (original scale)
+  std::unique_ptr<CoefLayer> coef_;
+  std::vector<double> beta_, fit_offset_;   // fit_offset_: F of the fit (empty: none)
+  void RefreshCoefOffset();   // the device offset := F of the fit + X beta
+  std::string optimizer_coef_ = "lbfgs";
+  bool cov_par_index_given_ = false, init_coef_given_ = false;
   std::vector<std::vector<int>> levels_;                       // K x n
   std::vector<std::unordered_map<std::string, int>> label_index_;   // label -> level, per effect
   std::vector<double> y_raw_, y_;

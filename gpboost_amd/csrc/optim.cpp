@@ -128,9 +128,7 @@ int lbfgs_minimize(LbfgsObjective& f, std::vector<double>& x, double& fx, const 
     gradp = grad;
     // GetMaximalLearningRate (optim_utils.h:497-534 -> MaximalLearningRateCovAuxPars,
     // re_model_template.h:4937-4945): no parameter changes by more than a factor of 100 per step
-    double max_abs = 0.;
-    for (int i = 0; i < n; ++i) max_abs = std::max(max_abs, std::fabs(drt[i]));
-    const double max_lr = s.max_log_change / max_abs;
+    const double max_lr = f.MaxLearningRate(xp, drt, s.max_log_change);
     if (max_lr < step) step = max_lr;
     backtracking(f, s, xp, drt, step, fx, grad, x);
     f.Eval(x, grad, false, true, false);   // gradient at the accepted point

@@ -10,6 +10,8 @@
 // gradient comes from the device evaluation of REModelAMD.
 #pragma once
 
+#include <algorithm>
+#include <cmath>
 #include <functional>
 #include <string>
 #include <vector>
@@ -36,6 +38,15 @@ class LbfgsObjective {
   // caller expects to ask for the gradient at this x next (lets a device evaluation compute both).
   virtual double Eval(const std::vector<double>& x, std::vector<double>& grad, bool eval_ll, bool calc_grad,
                       bool hint_grad) = 0;
+  // GetMaximalLearningRate (optim_utils.h:497-534): the largest step along drt from x. The default is
+  // MaximalLearningRateCovAuxPars (re_model_template.h:4937-4945) over every entry: no parameter changes by more than
+  // exp(max_log_change) per step. An objective with regression coefficients in x overrides it.
+  virtual double MaxLearningRate(const std::vector<double>& x, const std::vector<double>& drt, double max_log_change) {
+    (void)x;
+    double max_abs = 0.;
+    for (double d : drt) max_abs = std::max(max_abs, std::fabs(d));
+    return max_log_change / max_abs;
+  }
   virtual void SetLag1ProfiledOutVariables() {}     // optim_utils.h (EvalLLforLBFGSpp) / LBFGS.h:232
   virtual void ResetProfiledOutVariablesToLag1() {} // LineSearchBacktracking.h:133
   virtual void SetNumIter(int) {}                   // LBFGS.h:231 (f.SetNumIter(k - 1))

@@ -289,3 +289,51 @@ def bench_grouped_gamma_y(groups: np.ndarray, shape: int = 2, sd=(1.0, 0.5)) -> 
     for j in range(int(shape)):
         g -= np.log(np.maximum(lcg_unif(n, 0.31415 + 0.1 * j), 1e-300))
     return np.exp(_grouped_eta(groups, sd)) * g / int(shape)
+
+
+def bench_grouped_coef_y(groups: np.ndarray, X: np.ndarray, beta, likelihood: str, shape: int = 2,
+                         sd=(1.0, 0.5)) -> np.ndarray:
+    """The bench_grouped_*_y responses with a linear predictor: eta = X beta + the grouped level effects, drawn from
+    the same LCG streams (bernoulli_logit / bernoulli_probit: c = 0.19341 against the inverse link of eta; poisson:
+    log-rate eta by inversion at c = 0.27183; gamma: mean exp(eta), integer shape, streams c = 0.31415 + 0.1 j)."""
+    n = groups.shape[0]
+    eta = X @ np.asarray(beta, dtype=np.float64) + _grouped_eta(groups, sd)
+    if likelihood == "bernoulli_logit":
+        return (lcg_unif(n, 0.19341) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+    if likelihood == "bernoulli_probit":
+        from scipy.stats import norm
+        return (lcg_unif(n, 0.19341) < norm.cdf(eta)).astype(np.float64)
+    if likelihood == "poisson":
+        lam = np.exp(eta)
+        u = lcg_unif(n, 0.27183)
+        k = np.zeros(n)
+        p = np.exp(-lam)
+        cdf = p.copy()
+        active = u > cdf
+        while active.any():
+            k[active] += 1.0
+            p[active] *= lam[active] / k[active]
+            cdf[active] += p[active]
+            active &= (u > cdf) & (k < 1000.0)
+        return k
+    if likelihood == "gamma":
+        g = np.zeros(n)
+        for j in range(int(shape)):
+            g -= np.log(np.maximum(lcg_unif(n, 0.31415 + 0.1 * j), 1e-300))
+        return np.exp(eta) * g / int(shape)
+    raise ValueError(f"unknown likelihood {likelihood!r}")
+
+
+def rtest_grouped_probit_coef(n: int = 100, m: int = 10) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The R test "Binary classification with linear predictor and grouped random effects model"
+    (test_GPModel_non_Gaussian_data.R:20-62, 1830-1833): m groups of n / m consecutive observations, level effects
+    qnorm(sim_rand_unif(m, 0.565)), X = rtest_probit_X, beta = (0.1, 2), y = 1[sim_rand_unif(n, 0.542) < pnorm(eta)].
+    Returns (group labels 1 .. m, X, y)."""
+    from scipy.stats import norm
+
+    group = np.repeat(np.arange(1, m + 1), n // m)
+    b = norm.ppf(sim_rand_unif(m, 0.565))
+    X = rtest_probit_X(n)
+    probs = norm.cdf(b[group - 1] + X @ np.array([0.1, 2.0]))
+    y = (sim_rand_unif(n, 0.542) < probs).astype(np.float64)
+    return group, X, y

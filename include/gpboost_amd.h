@@ -240,6 +240,27 @@ GPBOOST_AMD_EXPORT int GPB_CanCalculateStandardErrorsCovPars(REModelHandle handl
  * (CalcStdDevCoef, re_model_template.h:9797-9814). */
 GPBOOST_AMD_EXPORT int GPB_GetCoef(REModelHandle handle, double* optim_coef, bool calc_std_dev);
 
+/* Grouped random effects with a non-Gaussian likelihood (Laplace): GPB_OptimLinRegrCoefCovPar estimates the
+ * coefficients inside the L-BFGS vector [log cov pars, beta, log aux pars] (optimizer_coef "lbfgs",
+ * optim_utils.h:243-364) on centred and scaled covariates (num_covariates <= 31); GPB_GetCoef returns them on the
+ * original scale, calc_std_dev by central differences of the coefficient gradient (CalcStdDevCoefNonGaussian,
+ * re_model_template.h:9825-9854; not for matrix_inversion_method "iterative"). After such a fit
+ * GPB_EvalNegLogLikelihood, GPB_CalcGradientF, GPB_PredictREModel (with covariate_data_pred) and
+ * GPB_PredictREModelTrainingDataRandomEffects use fixed_effects + X beta as the offset.
+ * GPB_GetNumCoef: the number of coefficients of the last fit (0: none), for every handle. */
+GPBOOST_AMD_EXPORT int GPB_GetNumCoef(REModelHandle handle, int* num_coef);
+
+/* Extension (grouped random effects, non-Gaussian likelihood): one evaluation of the Laplace-approximated negative
+ * log-likelihood at cov_pars (K), aux_pars (NULL: the current ones) and coef (p) on the covariates as given
+ * (column-major num_data x p, not scaled), the mode found from zero. grad_cov (K, nullable): d/dlog cov_pars;
+ * grad_aux (1, nullable; when auxiliary parameters are estimated): d/dlog aux; grad_coef (p) = X^T grad_F. y_data
+ * NULL: the stored response. It is an evaluation of the model like GPB_EvalNegLogLikelihood: y_data, aux_pars and
+ * cov_pars given become the model's; the covariates, coefficients and offset of an earlier fit stay. */
+GPBOOST_AMD_EXPORT int GPB_EvalNegLogLikelihoodGradCoef(REModelHandle handle, const double* cov_pars,
+    const double* aux_pars, const double* coef, const double* y_data, const double* covariate_data,
+    int num_covariates, const double* fixed_effects, double* negll, double* grad_cov, double* grad_aux,
+    double* grad_coef);
+
 /* replaces GPB_PredictREModelTrainingDataRandomEffects (include/LightGBM/c_api.h:1645;
  * re_model.cpp PredictTrainingDataRandomEffects): cov_pars_pred on the original scale (NULL: the
  * estimated / last evaluated ones), y_obs NULL: the stored response. Gaussian likelihood (dense and
@@ -406,6 +427,19 @@ GPBOOST_AMD_EXPORT int GPB_PivotedCholeskyHost(const double* coords, int n, int 
  * learning rate passed to each trial (NaN for the trials not run). No reference counterpart (tests). */
 GPBOOST_AMD_EXPORT int GPB_TestNewtonLineSearch(int it, double obj, double gdd, double delta, int max_shrink,
                                                 const double* trial_objs, int n_trials, double* out);
+
+/* Test hooks of the coefficient layer (coef.h). GPB_TestCoefOps: the three device passes over X (row-major n x p,
+ * p <= 31) with host arrays in and out: eta0 (n) = F + X beta (F nullable), g (p) = X^T gF, mom (4) = [sum X dir,
+ * sum X beta, sum (X dir)^2, sum (X dir)(X beta)]; each output nullable.
+ * GPB_TestCoefHost makes no device call (X column-major n x p): op 0 scaling, out = [intercept column or -1,
+ * scaled 0/1, loc (p), scale (p), scaled X row-major (n p)]; 1 / 2 TransformCoef / TransformBackCoef of in (p) to
+ * out (p); 3 the initial intercept of likelihood lik (1 bernoulli_logit, 2 bernoulli_probit, 3 poisson, 4 gamma)
+ * with in[0] the random effects' total variance; 4 out = [C_mu, C_sigma2]; 5 the step cap from in = [the four sums,
+ * C_mu, C_sigma2] over n observations. */
+GPBOOST_AMD_EXPORT int GPB_TestCoefOps(int n, int p, const double* X, const double* beta, const double* dir,
+    const double* F, const double* gF, double* eta0, double* g, double* mom);
+GPBOOST_AMD_EXPORT int GPB_TestCoefHost(int op, int lik, int n, int p, const double* X, const double* y,
+    const double* F, const double* in, double* out);
 
 /* The dense fp64 building blocks (C = alpha op(A) op(B) + beta C on MFMA tiles with triangle masks, its
  * split-K form, the blocked Cholesky with the triangular inverse and the log-determinant, the SPD solve /
