@@ -152,9 +152,10 @@ class GPModel:
         """Grouped random effects (reference basic.py GPModel.__init__ group_data handling): labels are
         converted to strings and passed column-major as NUL-terminated C strings. With gp_coords: the
         combined model with one GP component (gp_approx "none"). likelihood "bernoulli_logit",
-        "bernoulli_probit", "poisson" or "gamma": the Laplace approximation (several grouping variables: "iterative"
-        by default, or "cholesky"); cov_pars then are the K variances without an error term and
-        gamma's shape is the auxiliary parameter."""
+        "bernoulli_probit", "poisson", "gamma" or "negative_binomial" (aliases "nbinom2", "negative_binomial_2",
+        "negative_binomial2"; without gp_coords only): the Laplace approximation (several grouping variables:
+        "iterative" by default, or "cholesky"); cov_pars then are the K variances without an error term and the
+        shape of gamma / negative_binomial is the auxiliary parameter."""
         g = np.asarray(group_data)
         if g.ndim == 1:
             g = g.reshape(-1, 1)

@@ -174,7 +174,8 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
     // non-Gaussian likelihoods: the Laplace approximation of GroupedLaplace; names outside parse_likelihood's fail there
     const std::string lik_name = str_or(likelihood, "gaussian");
     if (lik_name != "gaussian") {
-      (void)gpb_amd::parse_likelihood(lik_name);
+      const int lik_code = gpb_amd::parse_likelihood(lik_name);
+      if (num_gp == 1) gpb_amd::refuse_grouped_only_likelihood(lik_code, lik_name);
       if (num_gp == 1)
         gpb_amd::Fatal("a Gaussian process beside grouped random effects (gp_coords with group_data) is not supported "
                        "for likelihood '%s' by gpboost_amd", lik_name.c_str());
@@ -251,7 +252,7 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
   // objective (optim_utils.h:656-657)
   (void)trace;
   (void)lr_coef; (void)acc_rate_coef;
-  if (GroupedModel* g = as_grouped(handle)) {   // coefficients: Laplace models, optimizer_coef "lbfgs"; aux: gamma only
+  if (GroupedModel* g = as_grouped(handle)) {   // coefficients: Laplace models, optimizer_coef "lbfgs"; aux: the shape of gamma / negative_binomial
     (void)piv_chol_rank;
     (void)num_covariates;
     g->SetOptimizerCoef(optimizer_coef, init_coef != nullptr);   // checked when covariates are given
@@ -1075,6 +1076,13 @@ int GPB_TestLikPoint(int lik, double aux, int n, const double* y, const double* 
                      double* info, double* dinfo, double* dinfo_lowrank, int* guard_flag) {
   API_BEGIN();
   gpb_amd::test_lik_point(lik, aux, n, y, loc, loglik, d1, info, dinfo, dinfo_lowrank, guard_flag);
+  API_END();
+}
+
+int GPB_TestLikAuxPoint(int lik, double aux, int n, const double* y, const double* loc, double* dd1_aux,
+                        double* dinfo_aux, double* aux_term, int* guard_flag) {
+  API_BEGIN();
+  gpb_amd::test_lik_aux_point(lik, aux, n, y, loc, dd1_aux, dinfo_aux, aux_term, guard_flag);
   API_END();
 }
 

@@ -88,7 +88,7 @@ double coef_initial_intercept(int lik, int n, const double* y, const double* F, 
     const double v = lik == kLikBernoulliLogit ? std::log(pavg / (1. - pavg)) : normal_quantile(pavg);
     return std::min(std::max(v, -3.), 3.);
   }
-  if (lik == kLikPoisson || lik == kLikGamma) {
+  if (lik == kLikPoisson || lik == kLikGamma || lik == kLikNegBinomial) {
     double avg = 0.;
     for (int i = 0; i < n; ++i) avg += F == nullptr ? y[i] : y[i] / std::exp(F[i]);
     avg = std::max(avg / n, 1e-12);
@@ -98,7 +98,7 @@ double coef_initial_intercept(int lik, int n, const double* y, const double* F, 
 }
 
 void coef_cap_constants(int lik, int n, const double* y, double* C_mu, double* C_sigma2) {
-  if (lik == kLikPoisson || lik == kLikGamma) {
+  if (lik == kLikPoisson || lik == kLikGamma || lik == kLikNegBinomial) {
     double mean = 0., sec = 0.;
     for (int i = 0; i < n; ++i) {
       mean += y[i];

@@ -1,5 +1,5 @@
 // GroupedLaplace: Laplace-approximated marginal likelihood of K grouped (crossed or nested) random effects
-// under a non-Gaussian likelihood (bernoulli_logit, bernoulli_probit, poisson, gamma) on one GPU.
+// under a non-Gaussian likelihood (bernoulli_logit, bernoulli_probit, poisson, gamma, negative_binomial) on one GPU.
 //
 // Model: b ~ N(0, Sigma), Sigma = diag(sigma_k^2 I_{m_k}); eta = F + Z b; y_i ~ p(. | eta_i). With
 // A = Sigma^-1 + Z^T W Z (W = the information at the mode, changing with every Newton step) the reference's
@@ -16,6 +16,11 @@
 //          v = A^-1 Z^T (dW/deta . q) / 2 (the derivative of the log-determinant through the mode);
 //          sum_i W_i q_ij = sum (A^-1 . I_j Z^T W Z), the reference's explicit trace, taken per observation;
 //   grad (wrt log shape, gamma) = dnll/dlog a + sum_i W_i q_i / 2 + v^T Z^T d1 (dW/dlog a = W, dd1/dlog a = d1);
+//   grad (wrt log shape, negative_binomial) = dnll/dlog r + sum_i (dW/dlog r)_i q_i / 2 + v^T Z^T (dd1/dlog r), the
+//          general form (:3602-3625, 3723-3739, 3830-3850): glp_nb_aux_kernel writes the two per-observation
+//          derivatives at the mode and sums log(mu_i + r) + (y_i + r) / (mu_i + r); the sum over i of
+//          digamma(y_i + r) (and lgamma(y_i + r) of the normalising constant) comes from a table of the distinct
+//          responses on the host; iterative: the trace by the probes with Z^T diag(dW/dlog r) Z as the operator;
 //   grad (wrt F)_i = -d1_i + dW_i q_i / 2 - W_i (Z v)_i.
 // K == 1: A is diagonal and every solve a division; K >= 2 with matrix_inversion_method = "cholesky": A dense in
 // HBM, refactored at every Newton step on GroupedRE's MFMA POTRF / TRTRI path; K >= 2 with "iterative" (the
@@ -43,7 +48,7 @@ constexpr int kGlpMaxK = 8;
 
 struct GroupedLaplaceResult {
   double nll = 0.;
-  std::vector<double> grad;   // d/dlog sigma_k^2 (K), then (gamma, if requested) d/dlog shape
+  std::vector<double> grad;   // d/dlog sigma_k^2 (K), then (gamma / negative_binomial, if requested) d/dlog shape
   int newton_its = 0, cg_its = 0, lanczos_steps = 0;   // cg_its: the first Newton step's PCG (num_cg_steps_last_)
   bool nan = false;           // NaN / Inf in the mode finding or A not positive definite: nll = NaN
   float ms_assembly = 0.f, ms_newton_step = 0.f;   // GPBOOST_AMD_TIMING: last weighted assembly / Newton step (HIP events)
@@ -105,6 +110,13 @@ class GroupedLaplace {
   double* h_red_ = nullptr;   // pinned
   bool has_off_ = false, keep_gradf_ = false, y_set_ = false, mode_prev_valid_ = false, evaluated_ = false;
   double lognorm_ = 0., sum_log_y_ = 0.;
+  // negative_binomial: the distinct responses ascending with their multiplicities (SetY), so that the sums over
+  // i of lgamma(y_i + r) and digamma(y_i + r) cost O(distinct values) per evaluation and have one order; the
+  // per-observation shape derivatives dd1 / dlog r and dW / dlog r at the mode, Z^T of the former, and (iterative)
+  // Z^T diag(dW / dlog r) Z in the layout of d_ztwz_
+  std::vector<double> y_vals_, y_cnt_;
+  double SumOverY(double (*f)(double), double r) const;   // sum_v c_v f(v + r), ascending v
+  DevBuf<double> d_dd1a_, d_dWa_, d_zta_, d_ztdwz_;
   hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 

@@ -20,7 +20,12 @@ namespace {
 constexpr int kMaxBlocks = 1024;      // blocks of an observation pass (grid-stride; fixed by n -> fixed sum order)
 constexpr int kShortLen = 32;         // destinations of at most this many observations: one thread each
 constexpr int kChunkLen = 512;        // chunk of a longer list: one wave, 8 observations per lane
-constexpr int kRed = 64;              // scalar slots
+constexpr int kRed = 128;             // scalar slots
+// slots of the general shape gradient (negative_binomial); 0 .. 63 are the evaluation's and the gamma gradient's
+constexpr int kRedAuxSum = 64;        // sum_i log(mu_i + r) + (y_i + r) / (mu_i + r)
+constexpr int kRedAuxTrace = 65;      // cholesky: sum_i (dW / dlog r)_i q_i
+constexpr int kRedAuxImp = 72;        // K: v_k^T (Z^T dd1 / dlog r)_k
+constexpr int kRedAuxDinv = 80;       // K, iterative: sum over effect k of diag(Z^T dW/dlog r Z) / D
 
 struct EffArgs {   // per-effect constants, by value
   int K;
@@ -54,19 +59,57 @@ __global__ void __launch_bounds__(256) glp_obs_kernel(int n, int K, const int* _
                                                       double* __restrict__ dW, double* __restrict__ partial) {
   __shared__ double sh[4];
   double ll = 0.;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    double eta = F != nullptr ? F[i] : 0.;
-    for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
-    const double yi = y[i];
-    ll += lik_loglik(lik, aux, yi, eta);
-    if (DERIV) {
-      d1[i] = lik_d1(lik, aux, yi, eta);
-      W[i] = lik_info(lik, aux, yi, eta);
-      if (dW != nullptr) dW[i] = lik_dinfo(lik, aux, yi, eta);
+  if (lik == kLikNegBinomial) {   // kernel-uniform: the nb_* functions with log(shape) taken once per thread
+    const double log_r = log(aux);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+      double eta = F != nullptr ? F[i] : 0.;
+      for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+      const double yi = y[i];
+      ll += nb_loglik(aux, log_r, yi, eta);
+      if (DERIV) {
+        d1[i] = nb_d1(aux, log_r, yi, eta);
+        W[i] = nb_info(aux, log_r, yi, eta);
+        if (dW != nullptr) dW[i] = nb_dinfo(aux, log_r, yi, eta);
+      }
+    }
+  } else {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+      double eta = F != nullptr ? F[i] : 0.;
+      for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+      const double yi = y[i];
+      ll += lik_loglik(lik, aux, yi, eta);
+      if (DERIV) {
+        d1[i] = lik_d1(lik, aux, yi, eta);
+        W[i] = lik_info(lik, aux, yi, eta);
+        if (dW != nullptr) dW[i] = lik_dinfo(lik, aux, yi, eta);
+      }
     }
   }
   ll = block_sum(ll, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = ll;
+}
+
+// negative_binomial, at the converged mode: the shape derivatives dd1 / dlog r and dW / dlog r per observation and
+// per block the sum of log(mu_i + r) + (y_i + r) / (mu_i + r) (the explicit shape gradient, likelihoods.h:10527-10538);
+// grid, stride and block sum as glp_obs_kernel, finished by glp_finish_kernel
+__global__ void __launch_bounds__(256) glp_nb_aux_kernel(int n, int K, const int* __restrict__ glev,
+                                                         const double* __restrict__ y, const double* __restrict__ F,
+                                                         const double* __restrict__ b, double aux,
+                                                         double* __restrict__ dd1a, double* __restrict__ dWa,
+                                                         double* __restrict__ partial) {
+  __shared__ double sh[4];
+  const double log_r = log(aux);
+  double acc = 0.;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    double eta = F != nullptr ? F[i] : 0.;
+    for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+    const double yi = y[i];
+    dd1a[i] = nb_dd1_aux(aux, log_r, yi, eta);
+    dWa[i] = nb_dinfo_aux(aux, log_r, yi, eta);
+    acc += nb_aux_term(aux, log_r, yi, eta);
+  }
+  acc = block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // out[c] = sum_j partial[c nb + j], one block per column
@@ -150,13 +193,16 @@ __global__ void __launch_bounds__(256) glp_effect_dots_kernel(EffArgs a, const d
 }
 
 // q_ij = sum_k A^-1[lev_j(i), lev_k(i)] (K^2 gathers from the dense inverse; K == 1: 1 / D), q_i = sum_j q_ij;
-// written: dwq_i = dW_i q_i / 2 and per block the sums of W_i q_ij (column j)
+// written: dwq_i = dW_i q_i / 2 and per block the sums of W_i q_ij (column j); AUX: also the sums of Wa_i q_i
+// (column K: the determinant term of a shape whose dW / dlog shape is not W)
+template <bool AUX>
 __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __restrict__ glev,
                                                     const double* __restrict__ Ainv, int ld,
                                                     const double* __restrict__ D, const double* __restrict__ W,
-                                                    const double* __restrict__ dW, double* __restrict__ dwq,
-                                                    double* __restrict__ partial) {
+                                                    const double* __restrict__ dW, const double* __restrict__ Wa,
+                                                    double* __restrict__ dwq, double* __restrict__ partial) {
   __shared__ double sh[4];
+  double tra = 0.;
   double tr[kGlpMaxK];
 #pragma unroll
   for (int j = 0; j < kGlpMaxK; ++j) tr[j] = 0.;
@@ -180,6 +226,7 @@ __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __r
       }
     }
     dwq[i] = 0.5 * dW[i] * qi;
+    if (AUX) tra += Wa[i] * qi;
   }
 #pragma unroll
   for (int j = 0; j < kGlpMaxK; ++j) {
@@ -187,6 +234,10 @@ __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __r
       const double s = block_sum(tr[j], sh);
       if (threadIdx.x == 0) partial[(size_t)j * gridDim.x + blockIdx.x] = s;
     }
+  }
+  if (AUX) {
+    const double s = block_sum(tra, sh);
+    if (threadIdx.x == 0) partial[(size_t)K * gridDim.x + blockIdx.x] = s;
   }
 }
 
@@ -315,7 +366,12 @@ GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>
   for (auto* b : {&d_mode_, &d_mode_new_, &d_mode_prev_, &d_upd_, &d_rhs_, &d_ztd1_, &d_D_, &d_dmll_, &d_vS_, &d_dis_})
     b->alloc(M);
   d_ztwz_.alloc(ND);
-  d_partial_.alloc((size_t)kMaxBlocks * kGlpMaxK);
+  d_partial_.alloc((size_t)kMaxBlocks * (kGlpMaxK + 1));   // K columns of glp_q_kernel and its shape column
+  if (lik_ == kLikNegBinomial) {
+    d_dd1a_.alloc(n);
+    d_dWa_.alloc(n);
+    d_zta_.alloc(M);
+  }
   d_red_.alloc(kRed);
   HIP_CHECK(hipMemsetAsync(d_mode_.get(), 0, sizeof(double) * M, s_));
   HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_red_), kRed * sizeof(double), hipHostMallocDefault));
@@ -354,6 +410,27 @@ void GroupedLaplace::SetY(const double* y) {
               "'poisson' ");
       for (int k = 2; k <= (int)y[i]; ++k) lognorm_ -= std::log((double)k);
     }
+  } else if (lik_ == kLikNegBinomial) {   // the checks of poisson (:655-667)
+    for (int i = 0; i < n; ++i) {
+      if (y[i] < 0.)
+        Fatal(" Must have y >= 0 for the response variable ('y') for likelihood = 'negative_binomial', found %g ", y[i]);
+      double ip;
+      if (std::modf(y[i], &ip) != 0.)
+        Fatal("Found non-integer response variable ('y'). Response variable can only be integer valued for likelihood = "
+              "'negative_binomial' ");
+    }
+    std::vector<double> sorted(y, y + n);
+    std::sort(sorted.begin(), sorted.end());
+    y_vals_.clear();
+    y_cnt_.clear();
+    for (int i = 0; i < n; ++i) {
+      if (y_vals_.empty() || sorted[i] != y_vals_.back()) {
+        y_vals_.push_back(sorted[i]);
+        y_cnt_.push_back(0.);
+      }
+      y_cnt_.back() += 1.;
+    }
+    lognorm_ = -SumOverY([](double x) { return std::lgamma(x); }, 1.);   // -sum log y_i! (:8308)
   }
   HIP_CHECK(hipMemcpyAsync(d_y_.get(), y, sizeof(double) * n, hipMemcpyHostToDevice, s_));
   HIP_CHECK(hipStreamSynchronize(s_));
@@ -378,7 +455,16 @@ double GroupedLaplace::LogLikConst(double aux) const {
   if (lik_ == kLikPoisson) return lognorm_;
   if (lik_ == kLikGamma)   // likelihoods.h:8181-8191
     return (aux - 1.) * sum_log_y_ + v_.n * (aux * std::log(aux) - std::lgamma(aux));
+  if (lik_ == kLikNegBinomial)   // LogNormalizingConstantNegBin (:8448-8463)
+    return SumOverY([](double x) { return std::lgamma(x); }, aux) + lognorm_ +
+           v_.n * (aux * std::log(aux) - std::lgamma(aux));
   return 0.;
+}
+
+double GroupedLaplace::SumOverY(double (*f)(double), double r) const {
+  double s = 0.;
+  for (size_t k = 0; k < y_vals_.size(); ++k) s += y_cnt_[k] * f(y_vals_[k] + r);
+  return s;
 }
 
 void GroupedLaplace::Assemble(const double* w, double* out, bool diag_only) {
@@ -439,6 +525,9 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
   for (int k = 0; k < K; ++k)
     if (!(sigma2[k] > 0.)) Fatal("covariance parameters must be > 0");
   if (lik_ == kLikGamma && !(aux > 0.)) Fatal("the shape parameter of the gamma likelihood must be > 0");
+  if (lik_ == kLikNegBinomial && !(aux > 0.))
+    Fatal("the shape parameter of the negative_binomial likelihood must be > 0");
+  const bool nb_aux = lik_ == kLikNegBinomial && want_aux_grad;   // the general shape gradient
   if (iterative && K < 2) Fatal("iterative methods need several grouped random effects");
   if (K > 1 && !iterative) re_->CheckDenseSize();
   const EffArgs ea = make_eff(v_, sigma2);
@@ -557,6 +646,12 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
   if (!want_grad) return res;
 
   // ---- gradient (:3634-3740 / 3791-3853)
+  if (nb_aux) {   // dd1/dlog r, dW/dlog r and the explicit sum at the mode (:10872-10885, 10527-10538)
+    glp_nb_aux_kernel<<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr,
+                                           d_mode_.get(), aux, d_dd1a_.get(), d_dWa_.get(), d_partial_.get());
+    glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get() + kRedAuxSum);
+    HIP_CHECK(hipGetLastError());
+  }
   std::vector<double> tr_iter(K, 0.);
   double aux_det = 0.;   // iterative: d log|A| / dlog shape
   if (iterative) {
@@ -598,10 +693,48 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
       trP /= t;
       aux_det = tr1 + optimal_c(z1.data(), zP.data(), t, tr1, trP) * (tr_dinv_w - trP);
     }
+    if (nb_aux) {
+      // the same estimate with Z^T diag(dW/dlog r) Z in the place of Z^T W Z (:3607-3625): assembled beside d_ztwz_
+      // and made the operator of the two products, on the same probes
+      const size_t mt = (size_t)M * t;
+      d_blkA_.alloc(mt);
+      d_blkB_.alloc(mt);
+      d_ztdwz_.alloc(M + v_.nnz);
+      Assemble(d_dWa_.get(), d_ztdwz_.get(), false);
+      glp_effect_dots_kernel<3><<<K, 256, 0, s_>>>(ea, d_ztdwz_.get(), d_D_.get(), d_red_.get() + kRedAuxDinv);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(h_red_ + kRedAuxDinv, d_red_.get() + kRedAuxDinv, sizeof(double) * K,
+                               hipMemcpyDeviceToHost, s_));
+      std::vector<double> z1(t), zP(t), tmp(t);
+      re_->SetOperator(d_ztdwz_.get() + M, d_ztdwz_.get(), d_D_.get(), d_dis_.get());
+      re_->ApplyOffDiagPlus(PI, d_blkA_.get(), t);
+      re_->ColDots(U, d_blkA_.get(), t, z1.data());   // synchronizes
+      re_->ApplyLower(d_ztdwz_.get(), DI, d_blkB_.get(), t);
+      re_->ColDots(PI, d_blkB_.get(), t, zP.data());
+      re_->ColDots(DI, d_blkB_.get(), t, tmp.data());
+      re_->SetOperator(d_ztwz_.get() + M, d_ztwz_.get(), d_D_.get(), d_dis_.get());   // A again, for the solve below
+      double tr_dinv_dw = 0.;   // tr(D^-1 diag(Z^T dW/dlog r Z))
+      for (int k = 0; k < K; ++k) tr_dinv_dw += h_red_[kRedAuxDinv + k];
+      double tr1 = 0., trP = 0.;
+      for (int c = 0; c < t; ++c) {
+        zP[c] = 2. * zP[c] - tmp[c];
+        tr1 += z1[c];
+        trP += zP[c];
+      }
+      tr1 /= t;
+      trP /= t;
+      aux_det = tr1 + optimal_c(z1.data(), zP.data(), t, tr1, trP) * (tr_dinv_dw - trP);
+    }
   } else {
     const double* Ainv = K > 1 ? re_->DenseInverse() : nullptr;
-    glp_q_kernel<<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(), d_dW_.get(),
-                                      d_dwq_.get(), d_partial_.get());
+    if (nb_aux) {   // one more fused partial: sum_i (dW/dlog r)_i q_i
+      glp_q_kernel<true><<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(),
+                                              d_dW_.get(), d_dWa_.get(), d_dwq_.get(), d_partial_.get());
+      glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get() + (size_t)K * nb_, d_red_.get() + kRedAuxTrace);
+    } else {
+      glp_q_kernel<false><<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(),
+                                               d_dW_.get(), nullptr, d_dwq_.get(), d_partial_.get());
+    }
     glp_finish_kernel<<<K, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get());   // sum_i W_i q_ij
     HIP_CHECK(hipGetLastError());
   }
@@ -611,6 +744,13 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
   glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_vS_.get(), d_ztd1_.get(), d_red_.get() + kGlpMaxK);
   glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_mode_.get(), d_mode_.get(), d_red_.get() + 2 * kGlpMaxK);
   HIP_CHECK(hipGetLastError());
+  if (nb_aux) {   // the implicit term v^T Z^T (dd1/dlog r) (:3628, 3737, 3848)
+    Assemble(d_dd1a_.get(), d_zta_.get(), true);
+    glp_effect_dots_kernel<0><<<K, 256, 0, s_>>>(ea, d_vS_.get(), d_zta_.get(), d_red_.get() + kRedAuxImp);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_ + kRedAuxSum, d_red_.get() + kRedAuxSum, sizeof(double) * (kRedAuxImp + K - kRedAuxSum),
+                             hipMemcpyDeviceToHost, s_));
+  }
   if (grad_f != nullptr || keep_gradf_) {
     d_gradf_.alloc(n);
     glp_grad_f_kernel<<<blocks_of(n), 256, 0, s_>>>(n, K, d_glev_.get(), d_d1_.get(), d_dwq_.get(), d_W_.get(),
@@ -633,6 +773,15 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
     // with ll = -a sum (eta + y e^-eta); dW/dlog a = W and dd1/dlog a = d1
     const double neg = -ll_mode - aux * (n * (std::log(aux) + 1. - digamma_asa103(aux)) + sum_log_y_);
     res.grad.push_back(neg + 0.5 * (iterative ? aux_det : tr_all) + imp_all);
+  }
+  if (nb_aux) {
+    // shape on the log scale (:10527-10538): -dll/dlog r = r sum_i [-digamma(y_i + r) + log(mu_i + r) + (y_i + r) /
+    // (mu_i + r)] + n r (digamma(r) - log r - 1), the digamma sum from the table of distinct responses
+    const double neg = aux * (h_red_[kRedAuxSum] - SumOverY(digamma_asa103, aux)) +
+                       n * aux * (digamma_asa103(aux) - std::log(aux) - 1.);
+    double imp_aux = 0.;
+    for (int j = 0; j < K; ++j) imp_aux += h_red_[kRedAuxImp + j];
+    res.grad.push_back(neg + 0.5 * (iterative ? aux_det : h_red_[kRedAuxTrace]) + imp_aux);
   }
   for (double g : res.grad)
     if (!std::isfinite(g)) res.nan = true;
@@ -672,6 +821,14 @@ void test_glp_obs(int n, int K, const int* glev, const double* y, const double* 
   if (deriv) glp_obs_kernel<true><<<nb, 256, 0, s>>>(n, K, glev, y, F, b, lik, aux, d1, W, dW, partial);
   else glp_obs_kernel<false><<<nb, 256, 0, s>>>(n, K, glev, y, F, b, lik, aux, nullptr, nullptr, nullptr, partial);
   glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial, ll);
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_glp_nb_aux(int n, int K, const int* glev, const double* y, const double* F, const double* b, double aux,
+                     double* dd1a, double* dWa, double* partial, double* sum, hipStream_t s) {
+  const int nb = obs_blocks(n);
+  glp_nb_aux_kernel<<<nb, 256, 0, s>>>(n, K, glev, y, F, b, aux, dd1a, dWa, partial);
+  glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial, sum);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -40,6 +40,7 @@ GroupedModel::GroupedModel(int n, const std::vector<std::vector<int>>& levels, c
   const int K = (int)levels.size();
   if (K < 1) Fatal("num_re_group must be > 0");
   lik_ = parse_likelihood(likelihood_);
+  if (lik_ == kLikNegBinomial) likelihood_ = "negative_binomial";   // the aliases' name (ParseLikelihoodAlias)
   if (mim_ == "default") mim_ = K > 1 ? "iterative" : "cholesky";
   if (mim_ != "iterative" && mim_ != "cholesky")
     Fatal("Matrix inversion method '%s' is not supported.", mim_.c_str());
@@ -61,8 +62,8 @@ GroupedModel::GroupedModel(int n, const std::vector<std::vector<int>>& levels, c
   re_.reset(new GroupedRE(n, levels, stream_));
   if (lik_ != kLikGaussian) {
     lap_.reset(new GroupedLaplace(re_.get(), levels, lik_));
-    if (lik_ == kLikGamma) {
-      aux_pars_ = {1.};   // aux_pars_ = {1.} until set or estimated (likelihoods.h:219-222)
+    if (lik_ == kLikGamma || lik_ == kLikNegBinomial) {
+      aux_pars_ = {1.};   // aux_pars_ = {1.} until set or estimated (likelihoods.h:181-192)
       init_aux_pars_ = {-1.};
     }
   }
@@ -869,6 +870,21 @@ void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effec
     off_init.resize(n_);
     coef_->LinearPredictor(beta_scaled.data(), fixed_effects, off_init.data());   // only the intercept is non-zero
     fixed_effects = off_init.data();
+  }
+  if (with_aux && !aux_pars_set_ && lik_ == kLikNegBinomial) {
+    // FindInitialAuxPars, negative_binomial (likelihoods.h:1091-1116, 1147-1156): method of moments on y e^-F,
+    // r = avg^2 / (var - avg), or 100 avg^2 where the data show no over-dispersion
+    double avg = 0., sum_sq = 0.;
+    for (int i = 0; i < n_; ++i) {
+      const double v = fixed_effects != nullptr ? yraw[i] / std::exp(fixed_effects[i]) : yraw[i];
+      avg += v;
+      sum_sq += v * v;
+    }
+    avg /= n_;
+    const double avg_sq = avg * avg;
+    const double sample_var = std::max((sum_sq - n_ * avg_sq) / (n_ - 1), 1e-6);
+    aux_pars_[0] = sample_var <= avg ? 100 * avg_sq : avg_sq / (sample_var - avg);
+    aux_pars_set_ = true;
   }
   if (with_aux && !aux_pars_set_) {
     // FindInitialAuxPars, gamma (likelihoods.h:1116-1145): approximate MLE of the shape ignoring the random

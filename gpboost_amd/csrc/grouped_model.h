@@ -27,10 +27,10 @@ class GroupedModel {
   // levels: K x n level indices (order of first appearance, as RECompGroup numbers its labels,
   // re_comp.h:245-264). matrix_inversion_method: "default" -> "iterative" for K >= 2, "cholesky"
   // for K == 1 (UseIterativeByDefault, re_model_template.h:6719-6724).
-  // likelihood other than "gaussian" (bernoulli_logit, bernoulli_probit, poisson, gamma): the Laplace
-  // approximation of GroupedLaplace (grouped_laplace.h) for K == 1 and for K >= 2 with "cholesky"; there is no
-  // error term then, the parameters are [sigma_1^2 .. sigma_K^2] on both scales, and gamma's shape is the
-  // auxiliary parameter.
+  // likelihood other than "gaussian" (bernoulli_logit, bernoulli_probit, poisson, gamma, negative_binomial and its
+  // aliases): the Laplace approximation of GroupedLaplace (grouped_laplace.h) for K == 1 and for K >= 2 with
+  // "cholesky"; there is no error term then, the parameters are [sigma_1^2 .. sigma_K^2] on both scales, and the
+  // shape of gamma / negative_binomial is the auxiliary parameter.
   GroupedModel(int n, const std::vector<std::vector<int>>& levels, const std::string& matrix_inversion_method,
                int seed, std::vector<std::unordered_map<std::string, int>> label_index = {},
                const std::string& likelihood = "gaussian");

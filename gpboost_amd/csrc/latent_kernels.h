@@ -329,7 +329,11 @@ void launch_axpby(size_t count, double alpha, const double* X, double beta, cons
 void launch_cap_mode_change(size_t count, const double* mode, double* mnew, hipStream_t s);
 
 // ---- likelihood-specific elementwise and reductions
-enum LatentLik : int { kLikGaussian = 0, kLikBernoulliLogit = 1, kLikBernoulliProbit = 2, kLikPoisson = 3, kLikGamma = 4 };
+// kLikNegBinomial: grouped random effects only (grouped_laplace.hip calls the nb_* functions of lik_device.h; the
+// lik_* dispatchers and every GP Laplace driver do not know it and the model layer refuses it there)
+enum LatentLik : int {
+  kLikGaussian = 0, kLikBernoulliLogit = 1, kLikBernoulliProbit = 2, kLikPoisson = 3, kLikGamma = 4, kLikNegBinomial = 5
+};
 
 // Observations of the latent variables when coordinates repeat (the reference's unique-location
 // form: Z maps n observations to the n_u latent variables, Vecchia_utils.cpp:1121-1139,

@@ -4,6 +4,7 @@
 //   bernoulli_logit likelihoods.h :8724, 9226, 9896, 10187; sigmoid_stable / softplus DF_utils.h:37-60
 //   bernoulli_probit :8708, 9208, 9871, 10171;  poisson :8730, 9230, 9904, 10200
 //   gamma           :8740, 9234, 9908, 10228 (aux = shape; log link, the normalizing constant on the host)
+//   negative_binomial (grouped random effects only): the nb_* functions at the end, not dispatched by lik_*
 // Shared by every Laplace path: sparse Vecchia (sparse_kernels.hip, lowrank_precond.hip), sparse Cholesky
 // (sparse_chol.hip), FITC (fitc_laplace.hip), full-scale Vecchia (vif_laplace.hip), dense (dense_laplace.hip) and
 // grouped (grouped_laplace.hip), and by the logit response mean of latent_pred.hip. Tested point by point through
@@ -103,6 +104,50 @@ __device__ __forceinline__ double lik_dinfo(int lik, double aux, double y, doubl
   if (lik == kLikPoisson) return exp(l);
   const double p = sigmoid_stable(l), q = sigmoid_stable(-l);
   return -p * q * (p - q);
+}
+
+// negative_binomial (aux = shape r, log link, mu = e^l; the normalizing constant on the host): likelihoods.h :8750,
+// :10241, shape derivatives :10872-10885, explicit shape gradient :10527-10538. Grouped random effects only, so
+// these are functions of their own (called by grouped_laplace.hip and the point kernel) and the lik_* dispatchers
+// above stay as they are. Everything goes through t = l - log r, p = sigmoid(t) = mu / (mu + r) and q = sigmoid(-t)
+// = r / (mu + r), each computed on its own: e^l overflows from l = 709.8 and mu / (mu + r) has no digit of q left
+// for l >> log r. log_r = log(r), computed once by the caller.
+// log-likelihood: y l - (y + r) log(mu + r) with l - log(mu + r) = -softplus(-t): two terms that do not cancel
+__device__ __forceinline__ double nb_loglik(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  return -y * softplus(-t) - r * (log_r + softplus(t));
+}
+// y - (y + r) p = y q - r p
+__device__ __forceinline__ double nb_d1(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  return y * sigmoid_stable(-t) - r * sigmoid_stable(t);
+}
+__device__ __forceinline__ double nb_info(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  return (y + r) * (sigmoid_stable(t) * sigmoid_stable(-t));
+}
+__device__ __forceinline__ double nb_dinfo(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  const double p = sigmoid_stable(t), q = sigmoid_stable(-t);
+  return -(y + r) * (p * q) * (p - q);
+}
+// d d1 / dlog r = p q (y - mu), with (y - mu) q = y q - r p (mu q = r p)
+__device__ __forceinline__ double nb_dd1_aux(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  const double p = sigmoid_stable(t), q = sigmoid_stable(-t);
+  return p * (y * q - r * p);
+}
+// d info / dlog r as the reference has it, -p q (y (r - mu) - 2 r mu) / (y + r), with q (r - mu) = r (q - p) and
+// q mu = r p
+__device__ __forceinline__ double nb_dinfo_aux(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  const double p = sigmoid_stable(t), q = sigmoid_stable(-t);
+  return -(p * r) * (y * (q - p) - 2. * (r * p)) / (y + r);
+}
+// log(mu + r) + (y + r) / (mu + r), the per-observation part of the explicit shape gradient
+__device__ __forceinline__ double nb_aux_term(double r, double log_r, double y, double l) {
+  const double t = l - log_r;
+  return log_r + softplus(t) + (y + r) * sigmoid_stable(-t) / r;
 }
 
 }  // namespace gpb_amd

@@ -57,8 +57,11 @@ void upload_int(DevBuf<int>& dst, const int32_t* src, size_t len) {
   if (len) HIP_CHECK(hipMemcpy(dst.get(), src, sizeof(int) * len, hipMemcpyHostToDevice));
 }
 
-void check_lik(const char* fn, int lik, double aux, int n, int n_max) {
-  if (lik < kLikGaussian || lik > kLikGamma) Fatal("%s: unknown likelihood %d", fn, lik);
+// path_name: null where negative_binomial (grouped random effects only) is available
+void check_lik(const char* fn, int lik, double aux, int n, int n_max, const char* path_name = nullptr) {
+  if (lik < kLikGaussian || lik > kLikNegBinomial) Fatal("%s: unknown likelihood %d", fn, lik);
+  if (lik == kLikNegBinomial && path_name != nullptr)
+    Fatal("%s: likelihood %d (negative_binomial) is not available on path %s", fn, lik, path_name);
   if (!(aux > 0.) || !std::isfinite(aux)) Fatal("%s: aux must be finite and > 0", fn);
   if (n < 1 || n >= n_max) Fatal("%s: n = %d is not in 1..%d", fn, n, n_max - 1);
 }
@@ -80,7 +83,7 @@ Shape shape_of(int path, int kernel) {
     case kLikPathGrouped:   // opts = {K, want_dW}
       if (kernel == kLikKernelPrep) return {0, {}, 2, 3, {-1, -1, 1}, 1, true};
       if (kernel == kLikKernelTrial) return {0, {}, 2, 0, {}, 1, true};
-      return none;
+      return {0, {}, 1, 2, {-1, -1}, 1, true};   // negative_binomial's shape pass: opts = {K}, outs = {dd1a, dWa}
     case kLikPathVif:
       if (kernel == kLikKernelPrep) return {0, {}, 3, 4, {-1, -1, 0, 1}, -1, true};   // opts = {want_dW, want_rhs, want_count}
       if (kernel == kLikKernelTrial) return {1, {false}, 2, 1, {-1}, 1, true};         // vecs = {upd}; opts = {first, cap}
@@ -115,11 +118,33 @@ void test_lik_point(int lik, double aux, int n, const double* y, const double* l
   for (Guarded& b : g) b.make(n);
   hipStream_t s = nullptr;
   launch_test_lik_point(n, lik, aux, dy.get(), dl.get(), g[0].p(), g[1].p(), g[2].p(), g[3].p(), s);
-  launch_lik_dinfo(n, lik, aux, dy.get(), dl.get(), nullptr, g[4].p(), s);
+  if (lik != kLikNegBinomial) launch_lik_dinfo(n, lik, aux, dy.get(), dl.get(), nullptr, g[4].p(), s);
   HIP_CHECK(hipDeviceSynchronize());
   double* out[5] = {ll, d1, info, dinfo, dinfo_lowrank};
   bool touched = false;
   for (int k = 0; k < 5; ++k) touched = g[k].fetch(out[k]) || touched;
+  *guard = touched ? 1 : 0;
+}
+
+void test_lik_aux_point(int lik, double aux, int n, const double* y, const double* loc, double* dd1_aux,
+                        double* dinfo_aux, double* aux_term, int* guard) {
+  const char* fn = "GPB_TestLikAuxPoint";
+  check_lik(fn, lik, aux, n, kMaxN);
+  if (lik != kLikNegBinomial) Fatal("%s: likelihood %d has no general shape derivatives (5, negative_binomial, has)", fn, lik);
+  if (y == nullptr || loc == nullptr || dd1_aux == nullptr || dinfo_aux == nullptr || aux_term == nullptr ||
+      guard == nullptr)
+    Fatal("%s: an argument is NULL", fn);
+  DevBuf<double> dy, dl;
+  upload(dy, y, n);
+  upload(dl, loc, n);
+  Guarded g[3];
+  for (Guarded& b : g) b.make(n);
+  hipStream_t s = nullptr;
+  launch_test_nb_aux_point(n, aux, dy.get(), dl.get(), g[0].p(), g[1].p(), g[2].p(), s);
+  HIP_CHECK(hipDeviceSynchronize());
+  double* out[3] = {dd1_aux, dinfo_aux, aux_term};
+  bool touched = false;
+  for (int k = 0; k < 3; ++k) touched = g[k].fetch(out[k]) || touched;
   *guard = touched ? 1 : 0;
 }
 
@@ -131,10 +156,15 @@ void test_lik_path(const LikPathTest& t, int* guard) {
   const Shape sh = shape_of(t.path, t.kernel);
   if (!sh.valid) Fatal("%s: path %d has no kernel %d", fn, t.path, t.kernel);
   const bool dmll = t.path == kLikPathDense && t.kernel == kLikKernelFinal;
-  check_lik(fn, t.lik, t.aux, t.n, dmll ? kMaxDenseN + 1 : kMaxN);
+  static const char* const kPathNames[kNumLikPaths] = {"grouped", "vif", "fitc", "dense", "vecchia"};
+  check_lik(fn, t.lik, t.aux, t.n, dmll ? kMaxDenseN + 1 : kMaxN,
+            t.path == kLikPathGrouped ? nullptr : kPathNames[t.path]);
   const int n = t.n;
   if (t.y == nullptr || guard == nullptr) Fatal("%s: y or guard_flag is NULL", fn);
   const bool grouped = t.path == kLikPathGrouped, vecchia = t.path == kLikPathVecchia;
+  if (grouped && t.kernel == kLikKernelFinal && t.lik != kLikNegBinomial)
+    Fatal("%s: path %d has no kernel %d for likelihood %d (the shape pass is negative_binomial's)", fn, t.path, t.kernel,
+          t.lik);
   if (grouped ? t.mode != nullptr : t.mode == nullptr)
     Fatal("%s: mode is %s", fn, grouped ? "not NULL (the grouped path takes b and glev)" : "NULL");
   if (t.n_vecs != sh.n_vecs || t.n_opts != sh.n_opts || t.n_outs != sh.n_outs)
@@ -223,6 +253,10 @@ void test_lik_path(const LikPathTest& t, int* guard) {
   switch (t.path) {
     case kLikPathGrouped:
       gpart.make(test_glp_blocks(n));
+      if (t.kernel == kLikKernelFinal) {
+        test_glp_nb_aux(n, K, didx.get(), dy.get(), off, darr0.get(), t.aux, o[0], o[1], gpart.p(), gsum.p(), s);
+        break;
+      }
       test_glp_obs(n, K, didx.get(), dy.get(), off, darr0.get(), t.lik, t.aux, t.kernel == kLikKernelPrep, o[0], o[1], o[2],
                    gpart.p(), gsum.p(), s);
       break;

@@ -16,7 +16,7 @@ enum LikPath : int { kLikPathGrouped = 0, kLikPathVif, kLikPathFitc, kLikPathDen
 enum LikKernel : int {
   kLikKernelPrep = 0,   // grouped: glp_obs_kernel<true>; vif / fitc / dense: *_prep_kernel; vecchia: newton_prep_kernel
   kLikKernelTrial,      // grouped: glp_obs_kernel<false>; vif: vl_trial_kernel; fitc / dense: laplace_trial_kernel
-  kLikKernelFinal,      // fitc: fl_final_kernel; dense: dl_dmll_kernel
+  kLikKernelFinal,      // fitc: fl_final_kernel; dense: dl_dmll_kernel; grouped (lik 5 only): glp_nb_aux_kernel
   kNumLikKernels
 };
 constexpr int kLikPathMaxVecs = 4, kLikPathMaxOuts = 5, kLikPathMaxOpts = 4, kLikPathMaxScalars = 3;
@@ -49,8 +49,17 @@ struct LikPathTest {
 void launch_test_lik_point(int n, int lik, double aux, const double* y, const double* loc, double* ll, double* d1,
                            double* info, double* dinfo, hipStream_t s);
 
+// negative_binomial (lik 5): the three shape functions nb_dd1_aux, nb_dinfo_aux and nb_aux_term
+void launch_test_nb_aux_point(int n, double aux, const double* y, const double* loc, double* dd1a, double* dinfoa,
+                              double* term, hipStream_t s);
+
+// lik 5: dinfo_lowrank stays NaN (the low-rank preconditioner belongs to the GP drivers, which do not have it)
 void test_lik_point(int lik, double aux, int n, const double* y, const double* loc, double* ll, double* d1, double* info,
                     double* dinfo, double* dinfo_lowrank, int* guard);
+// GPB_TestLikAuxPoint: the derivatives of d1 and of the information wrt the log of the auxiliary parameter and the
+// per-observation term of the explicit shape gradient; likelihoods with the general shape gradient only (lik 5)
+void test_lik_aux_point(int lik, double aux, int n, const double* y, const double* loc, double* dd1_aux,
+                        double* dinfo_aux, double* aux_term, int* guard);
 void test_lik_path(const LikPathTest& t, int* guard);
 
 // ---- launchers at the end of the production files (device pointers)
@@ -59,6 +68,9 @@ void test_lik_path(const LikPathTest& t, int* guard);
 int test_glp_blocks(int n);
 void test_glp_obs(int n, int K, const int* glev, const double* y, const double* F, const double* b, int lik, double aux,
                   bool deriv, double* d1, double* W, double* dW, double* partial, double* ll, hipStream_t s);
+// glp_nb_aux_kernel on the same blocks, then glp_finish_kernel -> *sum
+void test_glp_nb_aux(int n, int K, const int* glev, const double* y, const double* F, const double* b, double aux,
+                     double* dd1a, double* dWa, double* partial, double* sum, hipStream_t s);
 // vif_laplace.hip: part (nullable for prep) holds test_vl_blocks(n) doubles; the partials are summed into *sum
 int test_vl_blocks(int n);
 void test_vl_prep(int n, int lik, double aux, const double* y, const double* off, const double* mode, double* d1,

@@ -23,9 +23,18 @@ int parse_likelihood(const std::string& name) {
   if (name == "bernoulli_probit") return kLikBernoulliProbit;
   if (name == "poisson") return kLikPoisson;
   if (name == "gamma") return kLikGamma;
+  // ParseLikelihoodAlias (likelihoods.h:7985); grouped random effects only
+  if (name == "negative_binomial" || name == "nbinom2" || name == "negative_binomial_2" || name == "negative_binomial2")
+    return kLikNegBinomial;
   Fatal("likelihood '%s' is not supported by gpboost_amd (supported: gaussian, bernoulli_logit, bernoulli_probit, poisson, "
-        "gamma)", name.c_str());
+        "gamma, negative_binomial)", name.c_str());
   return -1;
+}
+
+void refuse_grouped_only_likelihood(int lik, const std::string& name) {
+  if (lik == kLikNegBinomial)
+    Fatal("likelihood '%s' is available for grouped random effects only in gpboost_amd (group_data without gp_coords); "
+          "Gaussian process models do not have it", name.c_str());
 }
 
 int parse_cov(const std::string& name, double shape) {
@@ -73,6 +82,7 @@ REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor) : 
   cfg_.cov_type = parse_cov(cfg_.cov_fct, cfg_.shape);
   // likelihood and approximation (re_model_template.h:207-211, 563; likelihoods.h:240-257)
   cfg_.lik = parse_likelihood(cfg_.likelihood);
+  refuse_grouped_only_likelihood(cfg_.lik, cfg_.likelihood);
   if (cfg_.gp_approx == "vecchia_latent") {
     vecchia_ = true;
     cfg_.latent = true;
@@ -901,6 +911,13 @@ void response_transform(int lik, double aux_shape, double aux_gauss, double delt
     for (int p = 0; p < n_pred; ++p) {
       const double pm = std::exp(mean[p] + 0.5 * var[p]);
       var[p] = (std::exp(var[p]) - 1.) * pm * pm + std::exp(2 * mean[p] + 2 * var[p]) / a;
+      mean[p] = pm;
+    }
+  } else if (lik == kLikNegBinomial) {   // :7585-7594, the variance as the reference has it (its last term included)
+    const double r = aux_shape;
+    for (int p = 0; p < n_pred; ++p) {
+      const double pm = std::exp(mean[p] + 0.5 * var[p]);
+      var[p] = std::exp(2 * (mean[p] + var[p])) * (1 + 1 / r) + pm * (1 - pm);
       mean[p] = pm;
     }
   } else if (lik == kLikPoisson) {   // :7557-7569

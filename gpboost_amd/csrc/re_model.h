@@ -52,8 +52,10 @@ struct ModelConfig {
 };
 
 int parse_likelihood(const std::string& name);   // LatentLik code
+// fails for a likelihood that only grouped random effects have (negative_binomial): called by every GP model
+void refuse_grouped_only_likelihood(int lik, const std::string& name);
 // PredictResponse (likelihoods.h:7526-7580) on latent predictive means / variances (host, n_pred each, in place);
-// aux_shape: gamma's shape, aux_gauss: the error variance of the latent Gaussian likelihood (cov nullable)
+// aux_shape: the shape of gamma / negative_binomial, aux_gauss: the error variance of the latent Gaussian likelihood (cov nullable)
 void response_transform(int lik, double aux_shape, double aux_gauss, double delta_conv, hipStream_t stream, int n_pred,
                         double* mean, double* var, double* cov);
 // cov_fcts.h:438-460: range rho -> phi on the transformed scale

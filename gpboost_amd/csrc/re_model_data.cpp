@@ -345,6 +345,7 @@ void REModelAMD::SetLikelihood(const std::string& likelihood) {
   ModelConfig c = cfg_;
   c.likelihood = likelihood;
   const int lik = parse_likelihood(likelihood);
+  refuse_grouped_only_likelihood(lik, likelihood);
   const bool dense = c.gp_approx == "none";
   const bool latent = c.gp_approx == "vecchia_latent" || ((vecchia_ || fitc_ || vif_ || dense) && lik != kLikGaussian);
   if (vif_) {   // full-scale Vecchia: the Laplace solver on the same inducing points and neighbours (Cholesky)

@@ -281,6 +281,29 @@ def bench_grouped_poisson_y(groups: np.ndarray, sd=(1.0, 0.5)) -> np.ndarray:
     return k
 
 
+def _negbin_by_inversion(mu: np.ndarray, shape: float, u: np.ndarray) -> np.ndarray:
+    """Negative binomial counts (mean mu, variance mu + mu^2 / shape) by inversion of the CDF at u:
+    p_0 = (shape / (shape + mu))^shape, p_{k+1} = p_k (k + shape) / (k + 1) mu / (mu + shape)."""
+    k = np.zeros(mu.shape[0])
+    p = np.exp(shape * (np.log(shape) - np.log(shape + mu)))
+    ratio = mu / (mu + shape)
+    cdf = p.copy()
+    active = u > cdf
+    while active.any():
+        p[active] *= (k[active] + shape) / (k[active] + 1.0) * ratio[active]
+        k[active] += 1.0
+        cdf[active] += p[active]
+        active &= (u > cdf) & (k < 100000.0)
+    return k
+
+
+def bench_grouped_negbin_y(groups: np.ndarray, shape: float = 1.5, sd=(1.0, 0.5)) -> np.ndarray:
+    """Over-dispersed counts: negative binomial with log-mean 0.5 + eta and the given shape, drawn by inversion of
+    its CDF at u from LCG c=0.16180."""
+    n = groups.shape[0]
+    return _negbin_by_inversion(np.exp(0.5 + _grouped_eta(groups, sd)), float(shape), lcg_unif(n, 0.16180))
+
+
 def bench_grouped_gamma_y(groups: np.ndarray, shape: int = 2, sd=(1.0, 0.5)) -> np.ndarray:
     """Gamma responses with integer shape and mean exp(eta): exp(eta) / shape times a sum of `shape`
     exponentials -log u_j, u_j from LCG streams c = 0.31415 + 0.1 j."""
@@ -321,6 +344,8 @@ def bench_grouped_coef_y(groups: np.ndarray, X: np.ndarray, beta, likelihood: st
         for j in range(int(shape)):
             g -= np.log(np.maximum(lcg_unif(n, 0.31415 + 0.1 * j), 1e-300))
         return np.exp(eta) * g / int(shape)
+    if likelihood == "negative_binomial":   # mean exp(eta), the (real) shape, by inversion at c = 0.16180
+        return _negbin_by_inversion(np.exp(eta), float(shape), lcg_unif(n, 0.16180))
     raise ValueError(f"unknown likelihood {likelihood!r}")
 
 

@@ -632,20 +632,28 @@ GPBOOST_AMD_EXPORT int GPB_TestVifVector(int op, int n, int m, int d, int cov_ty
  * Everything is checked on the host before any device call, a violation being an error return; outputs and
  * scratch start as NaN between 64 guard doubles on either side; guard_flag = 1 when a guard word changed or a
  * scalar that was not asked for was written. lik: LatentLik of csrc/latent_kernels.h (0 gaussian, 1
- * bernoulli_logit, 2 bernoulli_probit, 3 poisson, 4 gamma); aux finite and > 0; n < 2^22.
+ * bernoulli_logit, 2 bernoulli_probit, 3 poisson, 4 gamma, 5 negative_binomial: GPB_TestLikPoint,
+ * GPB_TestLikAuxPoint and path 0 of GPB_TestLikPath only, as grouped random effects alone have it; every other
+ * path refuses it before any device call); aux finite and > 0; n < 2^22.
  *
  * GPB_TestLikPoint: log-likelihood, first derivative, information and the information's derivative at (y_i,
  * loc_i), i < n, from a kernel that calls the four device functions and nothing else; dinfo_lowrank: the same
- * derivative from the low-rank preconditioner's launch_lik_dinfo. */
+ * derivative from the low-rank preconditioner's launch_lik_dinfo (lik 5: left NaN, that path does not have it). */
 GPBOOST_AMD_EXPORT int GPB_TestLikPoint(int lik, double aux, int n, const double* y, const double* loc, double* loglik,
                                         double* d1, double* info, double* dinfo, double* dinfo_lowrank,
                                         int* guard_flag);
+/* lik 5 only (the likelihood whose shape gradient takes the general form): the derivatives of d1 and of the
+ * information with respect to log(aux), and log(mu + aux) + (y + aux) / (mu + aux), the per-observation term of
+ * the explicit shape gradient, at (y_i, loc_i), i < n. */
+GPBOOST_AMD_EXPORT int GPB_TestLikAuxPoint(int lik, double aux, int n, const double* y, const double* loc,
+                                           double* dd1_aux, double* dinfo_aux, double* aux_term, int* guard_flag);
 /* One production kernel (set) of a Laplace path on its production grid (LikPath / LikKernel of csrc/lik_test.h).
  * y, mode, offset (nullable), every vecs[k] and every outs[k]: n entries; an output is given exactly when its
  * option asks for it (NULL otherwise). lam in (0, 1]. idx / arr0 / arr1 / mats are NULL (lengths 0) unless named.
  *   path 0 grouped (mode NULL, offset = F; idx = glev, K x n with entries in [0, arr_len), arr0 = b; opts = {K,
  *     want_dW}): kernel 0 glp_obs_kernel<true>, outs = {d1, W, dW}; kernel 1 glp_obs_kernel<false>, no outs; both
- *     followed by glp_finish_kernel, scalars = {sum loglik}.
+ *     followed by glp_finish_kernel, scalars = {sum loglik}; kernel 2 (lik 5 only; opts = {K}) glp_nb_aux_kernel,
+ *     outs = {dd1 / dlog aux, dW / dlog aux}, then glp_finish_kernel, scalars = {sum of the explicit term}.
  *   path 1 full-scale Vecchia: kernel 0 vl_prep_kernel (opts = {want_dW, want_rhs, want_count}, outs = {d1, W,
  *     dW, rhs}, scalars = {#(W == 0)} with want_count); kernel 1 vl_trial_kernel (vecs = {upd}, opts = {first,
  *     cap}, outs = {trial}, scalars = {sum loglik}).
