@@ -22,6 +22,7 @@
 #include "latent_test.h"
 #include "re_model.h"
 #include "sparse_chol.h"
+#include "grouped_test.h"
 #include "lik_test.h"
 #include "vif_test.h"
 
@@ -1095,6 +1096,76 @@ int GPB_TestLikPath(int path, int kernel, int n, int lik, double aux, const doub
   const gpb_amd::LikPathTest t{path, kernel, n,       lik,  aux,      y,   mode, offset, vecs,   n_vecs, idx,     idx_len,
                                arr0, arr1,   arr_len, mats, mats_len, lam, opts, n_opts, outs,   n_outs, scalars, n_scalars};
   gpb_amd::test_lik_path(t, guard_flag);
+  API_END();
+}
+
+int GPB_TestGroupedCreate(int n, int K, const int32_t* levels, int64_t levels_len, void** out) {
+  API_BEGIN();
+  const char* fn = "GPB_TestGroupedCreate";
+  if (out == nullptr || levels == nullptr) gpb_amd::Fatal("%s: levels or out is NULL", fn);
+  if (n < 1 || n > (1 << 22) || K < 1 || K > 16) gpb_amd::Fatal("%s: n = %d, K = %d", fn, n, K);
+  if (levels_len != (int64_t)n * K)
+    gpb_amd::Fatal("%s: levels holds %lld entries, not K n = %lld", fn, (long long)levels_len, (long long)n * K);
+  for (int64_t e = 0; e < levels_len; ++e)
+    if (levels[e] < 0 || levels[e] >= n) gpb_amd::Fatal("%s: levels[%lld] = %d is not in 0..n-1", fn, (long long)e, levels[e]);
+  *out = new gpb_amd::GroupedTest(n, K, levels);
+  API_END();
+}
+
+static gpb_amd::GroupedTest* grouped_test(void* handle, const char* fn) {
+  if (handle == nullptr) gpb_amd::Fatal("%s: handle is NULL", fn);
+  return static_cast<gpb_amd::GroupedTest*>(handle);
+}
+
+int GPB_TestGroupedFree(void* handle) {
+  API_BEGIN();
+  delete static_cast<gpb_amd::GroupedTest*>(handle);
+  API_END();
+}
+
+int GPB_TestGroupedInfo(void* handle, int t, int64_t* stats, int64_t stats_len, int32_t* ints, int64_t ints_len,
+                        double* dbls, int64_t dbls_len) {
+  API_BEGIN();
+  grouped_test(handle, "GPB_TestGroupedInfo")->Info(t, stats, stats_len, ints, ints_len, dbls, dbls_len);
+  API_END();
+}
+
+int GPB_TestGroupedApply(void* handle, int op, int t, const double* val, const double* dg_or_D, const double* dis,
+                         const double* In, double* Out0, double* Out1, int64_t block_len, int* guard_flag) {
+  API_BEGIN();
+  grouped_test(handle, "GPB_TestGroupedApply")->Apply(op, t, val, dg_or_D, dis, In, Out0, Out1, block_len, guard_flag);
+  API_END();
+}
+
+int GPB_TestGroupedSmall(void* handle, int op, const double* const* in, const int64_t* in_len, int n_in,
+                         double* const* out, const int64_t* out_len, int n_out, int* guard_flag) {
+  API_BEGIN();
+  grouped_test(handle, "GPB_TestGroupedSmall")->Small(op, in, in_len, n_in, out, out_len, n_out, guard_flag);
+  API_END();
+}
+
+int GPB_TestGroupedDense(void* handle, int op, int ld, int np, const int32_t* idx, const double* const* in,
+                         const int64_t* in_len, int n_in, double* const* out, const int64_t* out_len, int n_out,
+                         int* guard_flag) {
+  API_BEGIN();
+  grouped_test(handle, "GPB_TestGroupedDense")->Dense(op, ld, np, idx, in, in_len, n_in, out, out_len, n_out, guard_flag);
+  API_END();
+}
+
+int GPB_TestGroupedSolve(void* handle, const double* val, const double* cnt, const double* D, const double* dis,
+                         const double* rhs, int warm, const double* u0, int pmax, double delta, double* u, int* its,
+                         int* guard_flag) {
+  API_BEGIN();
+  grouped_test(handle, "GPB_TestGroupedSolve")->Solve(val, cnt, D, dis, rhs, warm, u0, pmax, delta, u, its, guard_flag);
+  API_END();
+}
+
+int GPB_TestGroupedLaplaceOps(void* handle, int op, int sub, int t, int ld, double alpha, const double* const* in,
+                              const int64_t* in_len, int n_in, double* const* out, const int64_t* out_len, int n_out,
+                              int* guard_flag) {
+  API_BEGIN();
+  grouped_test(handle, "GPB_TestGroupedLaplaceOps")
+      ->LaplaceOps(op, sub, t, ld, alpha, in, in_len, n_in, out, out_len, n_out, guard_flag);
   API_END();
 }
 

@@ -121,6 +121,9 @@ class GroupedRE {
   const double* slq_solution() { return bt_->U.get(); }   // A^-1 z (M x t) after SlqLogdet
   const double* probes_pinv() const { return d_PI_.get(); }   // P^-1 z after StochTraces
   const double* probes_dinv_upper() const { return d_DI_.get(); }
+  // test hook (grouped_test.cpp): reads the structure and the chunk plans as the device holds them and calls Op /
+  // Precond; adds nothing to a production path
+  friend struct GroupedTestAccess;
 
  private:
   struct Block {   // work space of a t-column PCG

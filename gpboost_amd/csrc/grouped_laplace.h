@@ -87,6 +87,8 @@ class GroupedLaplace {
   void PredVar(int np, const std::vector<int>& idx, double* out);
   // test hook: the diagonal (M) and the off-diagonal CSR values (nnz) of Z^T W Z of the last evaluation
   void GetZtWZ(double* diag, double* vals);
+  // test hook (grouped_test.cpp): Assemble on a caller's w, the level table and the segment counts
+  friend struct GroupedTestAccess;
 
  private:
   void Assemble(const double* w, double* out, bool diag_only);

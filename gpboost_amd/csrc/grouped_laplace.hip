@@ -8,6 +8,7 @@
 #include <limits>
 #include <utility>
 
+#include "grouped_test.h"
 #include "lik_device.h"
 #include "lik_test.h"
 #include "slq_host.h"
@@ -830,6 +831,73 @@ void test_glp_nb_aux(int n, int K, const int* glev, const double* y, const doubl
   glp_nb_aux_kernel<<<nb, 256, 0, s>>>(n, K, glev, y, F, b, aux, dd1a, dWa, partial);
   glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial, sum);
   HIP_CHECK(hipGetLastError());
+}
+
+// ---- test launchers (grouped_test.h): the gradient's launches of Eval with its grids
+void test_glp_q(int n, int K, const int* glev, const double* Ainv, int ld, const double* D, const double* W,
+                const double* dW, const double* Wa, bool aux, double* dwq, double* partial, double* out, hipStream_t s) {
+  const int nb = obs_blocks(n);
+  if (aux) {
+    glp_q_kernel<true><<<nb, 256, 0, s>>>(n, K, glev, Ainv, ld, D, W, dW, Wa, dwq, partial);
+    glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial + (size_t)K * nb, out + K);
+  } else {
+    glp_q_kernel<false><<<nb, 256, 0, s>>>(n, K, glev, Ainv, ld, D, W, dW, nullptr, dwq, partial);
+  }
+  glp_finish_kernel<<<K, 256, 0, s>>>(nb, partial, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_glp_row_trace(int n, int K, int t, const int* glev, const double* U, const double* V, const double* dW,
+                        double* dwq, hipStream_t s) {
+  glp_row_trace_kernel<<<blocks_of(n), 256, 0, s>>>(n, K, t, glev, U, V, dW, dwq);
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_glp_grad_f(int n, int K, const int* glev, const double* d1, const double* dwq, const double* W,
+                     const double* v, double* out, hipStream_t s) {
+  glp_grad_f_kernel<<<blocks_of(n), 256, 0, s>>>(n, K, glev, d1, dwq, W, v, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_glp_vec(int form, const GroupedRE::View& v, const double* sigma2, double alpha, const double* x,
+                  const double* y, double* out, hipStream_t s) {
+  const EffArgs ea = make_eff(v, sigma2);
+  const int M = v.M;
+  switch (form) {
+    case kVecDiag: glp_vec_kernel<kVecDiag><<<blocks_of(M), 256, 0, s>>>(M, ea, alpha, x, y, out); break;
+    case kVecRhs: glp_vec_kernel<kVecRhs><<<blocks_of(M), 256, 0, s>>>(M, ea, alpha, x, y, out); break;
+    case kVecDiv: glp_vec_kernel<kVecDiv><<<blocks_of(M), 256, 0, s>>>(M, ea, alpha, x, y, out); break;
+    case kVecAxpy: glp_vec_kernel<kVecAxpy><<<blocks_of(M), 256, 0, s>>>(M, ea, alpha, x, y, out); break;
+    case kVecInvSqrt: glp_vec_kernel<kVecInvSqrt><<<blocks_of(M), 256, 0, s>>>(M, ea, alpha, x, y, out); break;
+    default: Fatal("test_glp_vec: unknown form %d", form);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void test_glp_effect_dots(int mode, const GroupedRE::View& v, const double* sigma2, const double* x, const double* y,
+                          double* out, hipStream_t s) {
+  const EffArgs ea = make_eff(v, sigma2);
+  const int K = v.K;
+  switch (mode) {
+    case 0: glp_effect_dots_kernel<0><<<K, 256, 0, s>>>(ea, x, y, out); break;
+    case 1: glp_effect_dots_kernel<1><<<K, 256, 0, s>>>(ea, x, y, out); break;
+    case 2: glp_effect_dots_kernel<2><<<K, 256, 0, s>>>(ea, x, y, out); break;
+    case 3: glp_effect_dots_kernel<3><<<K, 256, 0, s>>>(ea, x, y, out); break;
+    default: Fatal("test_glp_effect_dots: unknown mode %d", mode);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// the friend of GroupedLaplace and GroupedRE: its GroupedLaplace half lives here, beside the private members it reads
+void GroupedTestAccess::Assemble(GroupedLaplace& g, const double* w, double* out, bool diag_only) {
+  g.Assemble(w, out, diag_only);
+}
+const int* GroupedTestAccess::Glev(const GroupedLaplace& g) { return g.d_glev_.get(); }
+void GroupedTestAccess::SegCounts(const GroupedLaplace& g, int out[4]) {
+  out[0] = g.n_long_diag_;
+  out[1] = g.n_chunks_diag_;
+  out[2] = g.n_long_;
+  out[3] = g.n_chunks_;
 }
 
 }  // namespace gpb_amd

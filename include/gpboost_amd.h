@@ -674,6 +674,62 @@ GPBOOST_AMD_EXPORT int GPB_TestLikPath(int path, int kernel, int n, int lik, dou
                                        int64_t arr_len, const double* mats, int64_t mats_len, double lam,
                                        const int32_t* opts, int n_opts, double* const* outs, int n_outs,
                                        double* scalars, int n_scalars, int* guard_flag);
+/* The grouped random-effects engine (csrc/grouped_kernels.hip, csrc/grouped_laplace.hip) on host arrays, through
+ * the production launch functions. No reference counterpart (tests). Everything is checked on the host before any
+ * device call, a violation being an error return. Outputs and scratch (the chunk partials included) start as NaN
+ * between 64 guard doubles on either side; guard_flag = 1 when a guard word changed. Dense matrices are host M x M
+ * column-major; the hook places them at leading dimension ld >= M and fills the ld - M padding with NaN.
+ *
+ * GPB_TestGroupedCreate: a GroupedRE on a stream of its own for levels (K x n, levels_len = K n, each in 0..n-1,
+ * taken as given: an index that no observation uses is a row with count 0 and no entries).
+ * GPB_TestGroupedInfo: stats (14): M, nnz, n, K, then for the lane split of t columns tc, the chunk length, the
+ * chunk counts of the full / lower / upper plan, the entries of ints, and the segmented sums' long level
+ * destinations, their chunks, all long destinations, all chunks. ints (nullable together with dbls): cum (K + 1),
+ * rowptr (M + 1), split (M), col (nnz), the observation lists' ptr (M + 1) and entries (n K), then e0, e1 (chunk
+ * count each) and ptr (M + 1) of the full, the lower and the upper plan, lower_q and upper_q (K + 1 each), all as
+ * the device holds them; dbls: val (nnz), cnt (M). */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedCreate(int n, int K, const int32_t* levels, int64_t levels_len, void** out);
+GPBOOST_AMD_EXPORT int GPB_TestGroupedFree(void* handle);
+GPBOOST_AMD_EXPORT int GPB_TestGroupedInfo(void* handle, int t, int64_t* stats, int64_t stats_len, int32_t* ints,
+                                           int64_t ints_len, double* dbls, int64_t dbls_len);
+/* One product on M x t row-major blocks (block_len = M t, t in 1..1024), K >= 2. val: the nnz off-diagonal values
+ * in CSR order, NULL: the model's counts. op 0 apply: Out0 = (diag(dg) + offdiag) In; 1 the same with the lower
+ * off-diagonal part; 2 Out0 = (L D^-1/2) In; 3 the SSOR sweeps: Out0 = X = (L D^-1/2)^-1 In, Out1 = Z =
+ * (L D^-1/2)^-T X; 4 Out0 = D^-1 (upper triangle of A) In; 5 GroupedRE::Precond after SetOperator(val, NULL, D,
+ * dis) (Out0 = its scratch X, Out1 = Z). dis: M entries for ops 2, 3 and 5 (independent of D), NULL otherwise;
+ * Out1: for ops 3 and 5 only. */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedApply(void* handle, int op, int t, const double* val, const double* dg_or_D,
+                                            const double* dis, const double* In, double* Out0, double* Out1,
+                                            int64_t block_len, int* guard_flag);
+/* op 0 launch_gre_zty: in = y (n); out = Z^T y (M). 1 launch_gre_diag: in = cnt (M), tau (K, > 0); out = D (M),
+ * dis (M), sums (2 K). 2 launch_gre_single on m = in_len[0] rows: in = zty, cnt, D (m each); out = u (m), sums (2).
+ * 3 launch_gre_residual: in = rhs, V (any equal length); out = rhs - V. */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedSmall(void* handle, int op, const double* const* in, const int64_t* in_len,
+                                            int n_in, double* const* out, const int64_t* out_len, int n_out,
+                                            int* guard_flag);
+/* M <= 4096, M <= ld <= 8192. op 0 launch_gre_dense_build: in = val (nnz, or length 0: the model's counts), D (M);
+ * out = the M columns of ld entries, zero before the launch. 1 launch_gre_inv_diag: in = Li (M x M); out (M).
+ * 2 / 3 launch_gre_pred_cols with E / with var: idx (np x K, -1..M-1), in = Li; out = E (np columns of ld entries,
+ * the padding as left) / var (np). 4 launch_gre_fisher_cols: in = sc (M), Ainv (M x M); out = part (M x K), diag (M). */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedDense(void* handle, int op, int ld, int np, const int32_t* idx,
+                                            const double* const* in, const int64_t* in_len, int n_in,
+                                            double* const* out, const int64_t* out_len, int n_out, int* guard_flag);
+/* SetOperator(val, cnt, D, dis) (val / cnt NULL: the model's) and SolveVec(rhs, u, pmax, delta, warm); warm = 1:
+ * u starts from u0. its: the iterations run. */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedSolve(void* handle, const double* val, const double* cnt, const double* D,
+                                            const double* dis, const double* rhs, int warm, const double* u0,
+                                            int pmax, double delta, double* u, int* its, int* guard_flag);
+/* A GroupedLaplace on the handle's engine (K <= 8). op 0 Assemble: sub = diag_only, in = w (n); out (M, or M + nnz:
+ * the levels, then the CSR slots). 1 glp_q_kernel<sub = AUX> and glp_finish_kernel on the production block count:
+ * in = Ainv (M x M at ld; length 0 for K = 1), D (M), W, dW (n), Wa (n, length 0 without AUX); out = dwq (n), sums
+ * (K, + 1 with AUX). 2 glp_row_trace_kernel: in = U, V (M x t), dW (n); out (n). 3 glp_grad_f_kernel: in = d1, dwq,
+ * W (n), v (M); out (n). 4 glp_vec_kernel, sub = form (0 1/sigma2 + x, 1 x - y / sigma2, 2 x / y, 3 x + alpha y,
+ * 4 sqrt(1 / x)): in = sigma2 (K), x (M), y (M, length 0 for forms 0 and 4); out (M). 5 glp_effect_dots_kernel,
+ * sub = mode (0 x y, 1 log x, 2 1 / x, 3 x / y): in = sigma2 (K), x (M), y (M, length 0 for modes 1 and 2); out (K). */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedLaplaceOps(void* handle, int op, int sub, int t, int ld, double alpha,
+                                                 const double* const* in, const int64_t* in_len, int n_in,
+                                                 double* const* out, const int64_t* out_len, int n_out,
+                                                 int* guard_flag);
 /* The residual factor of a gp_approx = "full_scale_vecchia" model at cov_pars (original scale) in the model
  * order: perm (n, nullable: perm[i] = original index of the i-th point), neighbors (n x num_neighbors, nullable),
  * D (n), B_vals (n x num_neighbors, B(i, nbr) = -A_i, 0-padded) and their derivatives with respect to log var and
