@@ -96,15 +96,16 @@ class GPModel:
                  free_raw_data=False, model_file=None, model_dict=None, vecchia_approx=None,
                  vecchia_pred_type=None, num_neighbors_pred=None):
         self.handle = None
-        if group_rand_coef_data is not None:
-            raise GPBoostError("grouped random coefficients are out of scope for gpboost_amd")
         if gp_rand_coef_data is not None:
-            raise GPBoostError("GP random coefficients are out of scope for gpboost_amd")
+            raise GPBoostError("GP random coefficients (gp_rand_coef_data) are out of scope for gpboost_amd")
+        if group_rand_coef_data is not None and group_data is None:
+            raise ValueError("'group_rand_coef_data' needs 'group_data'")
         if model_file is not None or model_dict is not None:
             raise GPBoostError("model loading is out of scope for gpboost_amd")
         if group_data is not None:   # grouped random effects, optionally beside one dense GP (gp_approx "none")
             self._init_grouped(group_data, likelihood, matrix_inversion_method, seed, cluster_ids, weights,
-                               gp_coords, cov_function, cov_fct_shape, gp_approx)
+                               gp_coords, cov_function, cov_fct_shape, gp_approx, group_rand_coef_data,
+                               ind_effect_group_rand_coef, drop_intercept_group_rand_effect)
             return
         if gp_coords is None:
             raise ValueError("Either 'group_data' or 'gp_coords' must be provided")
@@ -148,14 +149,20 @@ class GPModel:
         self._post_init()
 
     def _init_grouped(self, group_data, likelihood, matrix_inversion_method, seed, cluster_ids, weights,
-                      gp_coords=None, cov_function="matern", cov_fct_shape=1.5, gp_approx="none"):
+                      gp_coords=None, cov_function="matern", cov_fct_shape=1.5, gp_approx="none",
+                      group_rand_coef_data=None, ind_effect_group_rand_coef=None,
+                      drop_intercept_group_rand_effect=None):
         """Grouped random effects (reference basic.py GPModel.__init__ group_data handling): labels are
         converted to strings and passed column-major as NUL-terminated C strings. With gp_coords: the
         combined model with one GP component (gp_approx "none"). likelihood "bernoulli_logit",
         "bernoulli_probit", "poisson", "gamma" or "negative_binomial" (aliases "nbinom2", "negative_binomial_2",
         "negative_binomial2"; without gp_coords only): the Laplace approximation (several grouping variables:
         "iterative" by default, or "cholesky"); cov_pars then are the K variances without an error term and the
-        shape of gamma / negative_binomial is the auxiliary parameter."""
+        shape of gamma / negative_binomial is the auxiliary parameter.
+        group_rand_coef_data (n x R) with ind_effect_group_rand_coef (R, the grouping variable of each slope, counted
+        from 1) adds random slopes: one more component (variance) each, after the intercepts;
+        drop_intercept_group_rand_effect (K booleans) removes the intercept of one grouping variable that has a slope
+        (reference basic.py GPModel.__init__)."""
         g = np.asarray(group_data)
         if g.ndim == 1:
             g = g.reshape(-1, 1)
@@ -186,10 +193,45 @@ class GPModel:
         cluster = None
         if cluster_ids is not None:
             cluster = np.ascontiguousarray(np.asarray(cluster_ids), dtype=np.int32)
+        self.num_group_rand_coef = 0
+        self.re_comp_names = [f"Group_{k + 1}" for k in range(self.num_group_re)]
+        slope_cm = ind = drop = None
+        if group_rand_coef_data is not None:
+            sl = np.asarray(group_rand_coef_data, dtype=np.float64)
+            if sl.ndim == 1:
+                sl = sl.reshape(-1, 1)
+            if sl.ndim != 2 or sl.shape[0] != self.num_data:
+                raise ValueError("Incorrect number of data points in 'group_rand_coef_data'")
+            if ind_effect_group_rand_coef is None:
+                raise ValueError("Indices of grouped random effects ('ind_effect_group_rand_coef') for random slopes "
+                                 "in 'group_rand_coef_data' not provided")
+            ind = np.ascontiguousarray(np.asarray(ind_effect_group_rand_coef).reshape(-1), dtype=np.int32)
+            if ind.shape[0] != sl.shape[1]:
+                raise ValueError("Number of random coefficients in 'group_rand_coef_data' does not match number in "
+                                 "'ind_effect_group_rand_coef'")
+            self.num_group_rand_coef = sl.shape[1]
+            slope_cm = np.ascontiguousarray(sl.T).reshape(-1)
+            counter = np.zeros(self.num_group_re, dtype=int)   # names of unnamed input (reference basic.py:4715-4727)
+            for k in ind:
+                if 1 <= k <= self.num_group_re:
+                    counter[k - 1] += 1
+                    self.re_comp_names.append(f"Group_{k}_rand_coef_nb_{counter[k - 1]}")
+                else:   # refused by the library below
+                    self.re_comp_names.append(f"Group_{k}_rand_coef")
+            if drop_intercept_group_rand_effect is not None:
+                d = np.asarray(drop_intercept_group_rand_effect).reshape(-1)
+                if d.shape[0] != self.num_group_re:
+                    raise ValueError("Length of 'drop_intercept_group_rand_effect' does not match number of random "
+                                     "effects")
+                drop = np.ascontiguousarray(d.astype(bool), dtype=np.int32)
+                self.re_comp_names = [nm for i, nm in enumerate(self.re_comp_names)
+                                      if not (i < self.num_group_re and drop[i])]
         handle = ctypes.c_void_p()
         _safe_call(lib().GPB_CreateREModel(
             ctypes.c_int32(self.num_data), _ip(cluster) if cluster is not None else None,
-            buf, ctypes.c_int32(self.num_group_re), None, None, ctypes.c_int32(0), None,
+            buf, ctypes.c_int32(self.num_group_re), _dp(slope_cm) if slope_cm is not None else None,
+            _ip(ind) if ind is not None else None, ctypes.c_int32(self.num_group_rand_coef),
+            _ip(drop) if drop is not None else None,
             ctypes.c_int32(1 if self.has_gp else 0), _dp(coords_cm) if self.has_gp else None,
             ctypes.c_int(self.dim_coords), None, ctypes.c_int32(0),
             c_str(cov_function if self.has_gp else "exponential"),
@@ -370,7 +412,7 @@ class GPModel:
         """Predicted training-data random effects (GPB_PredictREModelTrainingDataRandomEffects,
         reference basic.py:6316-6367): (n,) means, or (n, 2) [mean, variance] with predict_var; grouped
         models: (n, K) means per effect, or (n, 2K) [means..., variances...]."""
-        k = max(1, getattr(self, "num_group_re", 0))
+        k = max(1, len(getattr(self, "re_comp_names", [])))   # grouped: one block per component (slopes included)
         out = np.zeros((2 if predict_var else 1) * k * self.num_data)
         _safe_call(lib().GPB_PredictREModelTrainingDataRandomEffects(self.handle, None, None, _dp(out), None,
                                                                      ctypes.c_bool(bool(predict_var))))
@@ -428,8 +470,8 @@ class GPModel:
         """Parameter names as the reference labels them (error term only for the Gaussian likelihood)."""
         if getattr(self, "num_group_re", 0):
             if self.likelihood != "gaussian":   # no error term
-                return [f"Group_{k + 1}" for k in range(self.num_group_re)]
-            return (["Error_term"] + [f"Group_{k + 1}" for k in range(self.num_group_re)] +
+                return list(self.re_comp_names)
+            return (["Error_term"] + list(self.re_comp_names) +
                     (["GP_var", "GP_range"] if getattr(self, "has_gp", False) else []))
         return (["Error_term"] if self.num_cov_pars == 3 else []) + ["GP_var", "GP_range"]
 
@@ -703,10 +745,12 @@ class GPModel:
         """Prediction settings and data (reference basic.py:6095-6190, GPB_SetPredictionData): the data is
         saved in the model for predict(use_saved_data=True) (gp_coords_pred / X_pred for GP models,
         group_data_pred for grouped random effects)."""
-        if any(v is not None for v in (group_rand_coef_data_pred, gp_rand_coef_data_pred, cluster_ids_pred)):
-            raise GPBoostError("set_prediction_data: random coefficients and clusters are not supported by gpboost_amd")
+        if gp_rand_coef_data_pred is not None or cluster_ids_pred is not None or (
+                group_rand_coef_data_pred is not None and not getattr(self, "num_group_rand_coef", 0)):
+            raise GPBoostError("set_prediction_data: GP random coefficients, grouped random coefficients of a model "
+                               "without them and clusters are not supported by gpboost_amd")
         num_data_pred = 0
-        gbuf = xcol = xpc = None
+        gbuf = xcol = xpc = slc = None
         if group_data_pred is not None:
             g = np.asarray(group_data_pred)
             if g.ndim == 1:
@@ -716,6 +760,9 @@ class GPModel:
             num_data_pred = g.shape[0]
             labels = g.astype(np.dtype(str)).flatten(order="F")
             gbuf = ctypes.create_string_buffer(b"\0".join(s.encode() for s in labels) + b"\0")
+        if group_rand_coef_data_pred is not None:
+            slc = self._slope_pred(group_rand_coef_data_pred, num_data_pred)
+            num_data_pred = slc.shape[0] // self.num_group_rand_coef
         if gp_coords_pred is not None:
             xp = np.asarray(gp_coords_pred, dtype=np.float64)
             if xp.ndim == 1:
@@ -735,7 +782,8 @@ class GPModel:
             num_data_pred = Xp.shape[0]
             xpc = np.ascontiguousarray(Xp.T).reshape(-1)
         _safe_call(lib().GPB_SetPredictionData(
-            self.handle, ctypes.c_int32(num_data_pred), None, gbuf, None, _dp(xcol) if xcol is not None else None,
+            self.handle, ctypes.c_int32(num_data_pred), None, gbuf, _dp(slc) if slc is not None else None,
+            _dp(xcol) if xcol is not None else None,
             None, _dp(xpc) if xpc is not None else None, c_str(vecchia_pred_type),
             ctypes.c_int(int(num_neighbors_pred) if num_neighbors_pred is not None else -1),
             ctypes.c_double(float(cg_delta_conv_pred) if cg_delta_conv_pred is not None else -1.),
@@ -744,6 +792,17 @@ class GPModel:
         if num_data_pred > 0:
             self.prediction_data_is_set = True
             self.num_data_pred = num_data_pred
+
+    def _slope_pred(self, group_rand_coef_data_pred, n_pred):
+        """group_rand_coef_data_pred (n_pred x R) column-major; n_pred = 0: taken from the data"""
+        sl = np.asarray(group_rand_coef_data_pred, dtype=np.float64)
+        if sl.ndim == 1:
+            sl = sl.reshape(-1, 1)
+        if sl.shape[1] != self.num_group_rand_coef:
+            raise ValueError("Incorrect number of covariates (columns) in 'group_rand_coef_data_pred'")
+        if n_pred and sl.shape[0] != n_pred:
+            raise ValueError("Incorrect number of data points in 'group_rand_coef_data_pred'")
+        return np.ascontiguousarray(sl.T).reshape(-1)
 
     def predict(self, predict_response=True, predict_var=False, predict_cov_mat=False, y=None, cov_pars=None,
                 group_data_pred=None, group_rand_coef_data_pred=None, gp_coords_pred=None,
@@ -761,8 +820,12 @@ class GPModel:
             return self._predict_saved(predict_var, predict_cov_mat, predict_response, y, cov_pars, offset,
                                        offset_pred, fixed_effects, fixed_effects_pred)
         if getattr(self, "num_group_re", 0):
+            if gp_rand_coef_data_pred is not None or cluster_ids_pred is not None:
+                raise GPBoostError("predictions with GP random coefficients (gp_rand_coef_data_pred) or clusters "
+                                   "(cluster_ids_pred) are not supported by gpboost_amd")
             return self._predict_grouped(group_data_pred, predict_var, predict_cov_mat, predict_response, y, cov_pars,
-                                         offset, offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred, X_pred)
+                                         offset, offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred, X_pred,
+                                         group_rand_coef_data_pred)
         if vecchia_pred_type is not None or num_neighbors_pred is not None:
             self.set_prediction_data(vecchia_pred_type=vecchia_pred_type, num_neighbors_pred=num_neighbors_pred)
         if any(v is not None for v in (group_data_pred, group_rand_coef_data_pred, gp_rand_coef_data_pred,
@@ -838,7 +901,8 @@ class GPModel:
         return {"mu": mu, "cov": cov, "var": var}
 
     def _predict_grouped(self, group_data_pred, predict_var, predict_cov_mat, predict_response, y, cov_pars, offset,
-                         offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred=None, X_pred=None):
+                         offset_pred, fixed_effects, fixed_effects_pred, gp_coords_pred=None, X_pred=None,
+                         group_rand_coef_data_pred=None):
         """Predictions of a grouped random effects model at new group labels (GPB_PredictREModel
         with re_group_data_pred): means = sum over the effects of the training posterior mean of the
         label's level (0 for a level not seen in training); with predict_var / predict_cov_mat
@@ -856,6 +920,12 @@ class GPModel:
         n_pred = g.shape[0]
         labels = g.astype(np.dtype(str)).flatten(order="F")
         buf = ctypes.create_string_buffer(b"\0".join(s.encode() for s in labels) + b"\0")
+        slc = None   # a model with slopes and no slope data: the library's message
+        if group_rand_coef_data_pred is not None:
+            if not getattr(self, "num_group_rand_coef", 0):
+                raise GPBoostError("group_rand_coef_data_pred is given but the model has no grouped random "
+                                   "coefficients")
+            slc = self._slope_pred(group_rand_coef_data_pred, n_pred)
         yv = self._check_y(y)
         if offset is not None:
             fixed_effects = offset if fixed_effects is None else np.asarray(fixed_effects) + np.asarray(offset)
@@ -890,7 +960,8 @@ class GPModel:
         _safe_call(lib().GPB_PredictREModel(
             self.handle, _dp(yv) if yv is not None else None, ctypes.c_int32(n_pred), _dp(out),
             ctypes.c_bool(bool(predict_cov_mat)), ctypes.c_bool(bool(predict_var)),
-            ctypes.c_bool(bool(predict_response)), None, buf, None, _dp(xcol) if xcol is not None else None, None,
+            ctypes.c_bool(bool(predict_response)), None, buf, _dp(slc) if slc is not None else None,
+            _dp(xcol) if xcol is not None else None, None,
             _dp(cp) if cp is not None else None, _dp(xpc) if xpc is not None else None, ctypes.c_bool(False),
             _dp(fe) if fe is not None else None, _dp(fep) if fep is not None else None))
         mu = out[:n_pred].copy()

@@ -48,6 +48,7 @@ struct SavedPred {
   std::vector<double> gp_coords;     // column-major num_data_pred x dim
   std::vector<double> covariates;    // column-major num_data_pred x p
   std::vector<char> re_group;        // num_data_pred x K NUL-terminated level strings, effect-major
+  std::vector<double> re_group_rand_coef;   // column-major num_data_pred x R (grouped models with random slopes)
 };
 std::mutex g_saved_mu;
 std::unordered_map<const void*, SavedPred> g_saved;
@@ -152,13 +153,18 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
                       bool has_weights, const double* weights, double likelihood_learning_rate,
                       REModelHandle* out) {
   API_BEGIN();
-  (void)re_group_rand_coef_data; (void)ind_effect_group_rand_coef; (void)drop_intercept_group_rand_effect;
   (void)cov_fct_taper_range; (void)cov_fct_taper_shape;
   (void)likelihood_additional_param; (void)num_parallel_threads; (void)GPU_use;
   (void)weights; (void)likelihood_learning_rate;
   if (out == nullptr) gpb_amd::Fatal("'out' is NULL");
-  if (num_re_group_rand_coef > 0 || num_gp_rand_coef > 0 || gp_rand_coef_data != nullptr)
-    gpb_amd::Fatal("random coefficients are out of scope for gpboost_amd (SURVEY.md §8)");
+  if (num_gp_rand_coef > 0 || gp_rand_coef_data != nullptr)
+    gpb_amd::Fatal("GP random coefficients (gp_rand_coef_data) are out of scope for gpboost_amd (SURVEY.md §8)");
+  if (num_re_group_rand_coef < 0) gpb_amd::Fatal("num_re_group_rand_coef must be >= 0");
+  if (num_re_group_rand_coef > 0 && (num_re_group <= 0 || re_group_data == nullptr))
+    gpb_amd::Fatal("grouped random coefficients (group_rand_coef_data) need group_data");
+  if (num_re_group_rand_coef > 0 && cluster_ids_data != nullptr)
+    gpb_amd::Fatal("cluster_ids together with grouped random coefficients (group_rand_coef_data) are not supported "
+                   "by gpboost_amd");
   if (has_weights) gpb_amd::Fatal("'weights' are not supported by gpboost_amd");
   if (cluster_ids_data != nullptr) {
     for (int32_t i = 1; i < num_data; ++i)
@@ -169,6 +175,9 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
     if (num_re_group <= 0 || re_group_data == nullptr) gpb_amd::Fatal("re_group_data and num_re_group must be given together");
     if ((num_gp > 0) != (gp_coords_data != nullptr)) gpb_amd::Fatal("num_gp and gp_coords_data must be given together");
     if (num_gp > 1) gpb_amd::Fatal("gpboost_amd supports at most one GP component (num_gp = 1)");
+    if (num_gp == 1 && num_re_group_rand_coef > 0)
+      gpb_amd::Fatal("group_rand_coef_data together with gp_coords (a Gaussian process beside grouped random effects) "
+                     "is not supported by gpboost_amd");
     if (num_gp == 1 && str_or(gp_approx, "none") != "none")
       gpb_amd::Fatal("GP + grouped random effects models with gp_approx = '%s' are not supported (the reference "
                      "allows only 'none' there, re_model_template.h:236-239)", gp_approx);
@@ -186,7 +195,13 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
     auto levels = gpb_amd::parse_group_levels(num_data, num_re_group, re_group_data, &index);
     std::string mim = str_or(matrix_inversion_method, "default");
     if (num_gp == 1 && mim == "default") mim = "cholesky";   // a GP beside: the dense path
-    std::unique_ptr<GroupedModel> gm(new GroupedModel(num_data, levels, mim, seed, std::move(index), lik_name));
+    gpb_amd::GroupedSlopes slopes;
+    slopes.R = num_re_group_rand_coef;
+    slopes.data = re_group_rand_coef_data;
+    slopes.ind = ind_effect_group_rand_coef;
+    slopes.drop = drop_intercept_group_rand_effect;
+    std::unique_ptr<GroupedModel> gm(
+        new GroupedModel(num_data, levels, mim, seed, std::move(index), lik_name, slopes));
     if (num_gp == 1)
       gm->AttachGP(dim_gp_coords, gp_coords_data, gpb_amd::parse_cov(str_or(cov_fct, "exponential"), cov_fct_shape),
                    seed);
@@ -366,10 +381,14 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
   (void)cg_delta_conv_pred;   // the Vecchia-Laplace draws use the model's cg_delta_conv (likelihoods.h:12052)
   (void)rank_pred_approx_matrix_lanczos;
   if (handle == nullptr) gpb_amd::Fatal("REModelHandle is NULL");
-  if (cluster_ids_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr || gp_rand_coef_data_pred != nullptr)
-    gpb_amd::Fatal("GPB_SetPredictionData: clusters and random coefficients are not supported by gpboost_amd");
   GroupedModel* g = as_grouped(handle);
-  const bool has_data = re_group_data_pred != nullptr || gp_coords_data_pred != nullptr || covariate_data_pred != nullptr;
+  if (cluster_ids_data_pred != nullptr || gp_rand_coef_data_pred != nullptr ||
+      (re_group_rand_coef_data_pred != nullptr && g == nullptr))
+    gpb_amd::Fatal("GPB_SetPredictionData: clusters and random coefficients are not supported by gpboost_amd");
+  if (re_group_rand_coef_data_pred != nullptr && !g->has_slopes())
+    gpb_amd::Fatal("group_rand_coef_data_pred is given but the model has no grouped random coefficients");
+  const bool has_data = re_group_data_pred != nullptr || gp_coords_data_pred != nullptr ||
+                        covariate_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr;
   if (has_data) {
     if (num_data_pred <= 0) gpb_amd::Fatal("num_data_pred must be > 0 when prediction data is given");   // CHECK :3075
     if (g != nullptr && gp_coords_data_pred != nullptr && !g->has_gp())
@@ -388,6 +407,7 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
       if (gp_coords_data_pred == nullptr) sp.gp_coords.clear();
       if (covariate_data_pred == nullptr) sp.covariates.clear();
       if (re_group_data_pred == nullptr) sp.re_group.clear();
+      if (re_group_rand_coef_data_pred == nullptr) sp.re_group_rand_coef.clear();
     }
     sp.num_data_pred = num_data_pred;
     if (gp_coords_data_pred != nullptr) {
@@ -401,9 +421,12 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
     }
     if (re_group_data_pred != nullptr) {   // num_data_pred x K NUL-terminated strings
       const char* e = re_group_data_pred;
-      for (long k = 0; k < (long)num_data_pred * g->K(); ++k) e += std::strlen(e) + 1;
+      for (long k = 0; k < (long)num_data_pred * g->num_groups(); ++k) e += std::strlen(e) + 1;
       sp.re_group.assign(re_group_data_pred, e);
     }
+    if (re_group_rand_coef_data_pred != nullptr)
+      sp.re_group_rand_coef.assign(re_group_rand_coef_data_pred,
+                                   re_group_rand_coef_data_pred + (size_t)num_data_pred * g->num_slopes());
     std::lock_guard<std::mutex> lk(g_saved_mu);
     g_saved[handle] = std::move(sp);
   }
@@ -433,16 +456,16 @@ int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_d
       gpb_amd::Fatal("num_data_pred (%d) differs from the saved prediction data (%d)", num_data_pred, saved.num_data_pred);
     num_data_pred = saved.num_data_pred;
     cluster_ids_data_pred = nullptr;
-    re_group_rand_coef_data_pred = nullptr;
+    re_group_rand_coef_data_pred = saved.re_group_rand_coef.empty() ? nullptr : saved.re_group_rand_coef.data();
     gp_rand_coef_data_pred = nullptr;
     re_group_data_pred = saved.re_group.empty() ? nullptr : saved.re_group.data();
     gp_coords_data_pred = saved.gp_coords.empty() ? nullptr : saved.gp_coords.data();
     covariate_data_pred = saved.covariates.empty() ? nullptr : saved.covariates.data();
   }
   if (GroupedModel* g = as_grouped(handle)) {
-    if (cluster_ids_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr ||
-        gp_rand_coef_data_pred != nullptr || (covariate_data_pred != nullptr && !g->laplace()))
-      gpb_amd::Fatal("predictions with clusters, random coefficients or covariates are not supported "
+    if (cluster_ids_data_pred != nullptr || gp_rand_coef_data_pred != nullptr ||
+        (covariate_data_pred != nullptr && !g->laplace()))
+      gpb_amd::Fatal("predictions with clusters, GP random coefficients or covariates are not supported "
                      "for grouped random effects models by gpboost_amd");
     // Laplace models with covariates: the mode is found with the offset F + X beta (GroupedModel::
     // SetResponseAndOffset) and X_pred beta joins fixed_effects_pred before the response transformation
@@ -460,7 +483,7 @@ int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_d
       gpb_amd::Fatal("Covariate data 'X_pred' is provided but the model has no covariates");
     }
     g->Predict(y_data, num_data_pred, re_group_data_pred, gp_coords_data_pred, cov_pars, predict_cov_mat, predict_var,
-               predict_response, fixed_effects, fixed_effects_pred, out_predict);
+               predict_response, fixed_effects, fixed_effects_pred, out_predict, re_group_rand_coef_data_pred);
     return 0;
   }
   if (cluster_ids_data_pred != nullptr || re_group_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr ||
@@ -1109,6 +1132,29 @@ int GPB_TestGroupedCreate(int n, int K, const int32_t* levels, int64_t levels_le
   for (int64_t e = 0; e < levels_len; ++e)
     if (levels[e] < 0 || levels[e] >= n) gpb_amd::Fatal("%s: levels[%lld] = %d is not in 0..n-1", fn, (long long)e, levels[e]);
   *out = new gpb_amd::GroupedTest(n, K, levels);
+  API_END();
+}
+
+int GPB_TestGroupedCreateWeighted(int n, int K, const int32_t* levels, int64_t levels_len, const double* weights,
+                                  int64_t weights_len, const int32_t* has_weight, void** out) {
+  API_BEGIN();
+  const char* fn = "GPB_TestGroupedCreateWeighted";
+  if (out == nullptr || levels == nullptr || weights == nullptr || has_weight == nullptr)
+    gpb_amd::Fatal("%s: levels, weights, has_weight or out is NULL", fn);
+  if (n < 1 || n > (1 << 22) || K < 1 || K > 16) gpb_amd::Fatal("%s: n = %d, K = %d", fn, n, K);
+  if (levels_len != (int64_t)n * K || weights_len != (int64_t)n * K)
+    gpb_amd::Fatal("%s: levels / weights hold %lld / %lld entries, not K n = %lld", fn, (long long)levels_len,
+                   (long long)weights_len, (long long)n * K);
+  for (int64_t e = 0; e < levels_len; ++e)
+    if (levels[e] < 0 || levels[e] >= n) gpb_amd::Fatal("%s: levels[%lld] = %d is not in 0..n-1", fn, (long long)e, levels[e]);
+  bool any = false;
+  for (int k = 0; k < K; ++k) {
+    if (has_weight[k] == 0) continue;
+    any = true;
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(weights[(size_t)k * n + i])) gpb_amd::Fatal("%s: weights[%d, %d] is not finite", fn, k, i);
+  }
+  *out = new gpb_amd::GroupedTest(n, K, levels, any ? weights : nullptr, has_weight);
   API_END();
 }
 

@@ -22,9 +22,13 @@ constexpr int kOut = 4096;   // pinned host / device scalar slots (>= 1024 resid
 constexpr int kDenseMaxM = 60000;   // K >= 2 cholesky: dense M x M factor (3.5 M^2 doubles, ~100 GB at the limit)
 }  // namespace
 
-GroupedRE::GroupedRE(int n, const std::vector<std::vector<int>>& levels, hipStream_t s)
+GroupedRE::GroupedRE(int n, const std::vector<std::vector<int>>& levels, hipStream_t s,
+                     const std::vector<const double*>& weights)
     : n_(n), K_((int)levels.size()), s_(s) {
   if (K_ < 1) Fatal("grouped random effects need at least one grouping variable");
+  if (!weights.empty() && (int)weights.size() != K_) Fatal("grouped random effects: one weight array per effect");
+  for (const double* w : weights) weighted_ = weighted_ || w != nullptr;
+  auto zw = [&](int k, int i) { return weights[k] != nullptr ? weights[k][i] : 1.; };
   m_.resize(K_);
   cum_.assign(K_ + 1, 0);
   for (int k = 0; k < K_; ++k) {
@@ -40,37 +44,71 @@ GroupedRE::GroupedRE(int n, const std::vector<std::vector<int>>& levels, hipStre
     for (int i = 0; i < n; ++i) ++cnt_i[cum_[k] + levels[k][i]];
   for (int r = 0; r < M_; ++r) optr[r + 1] = optr[r] + cnt_i[r];
   std::vector<int> obs((size_t)n * K_), fill(optr.begin(), optr.end() - 1);
+  std::vector<double> obs_w(weighted_ ? obs.size() : 0);
   for (int k = 0; k < K_; ++k)
-    for (int i = 0; i < n; ++i) obs[fill[cum_[k] + levels[k][i]]++] = i;
-  // off-diagonal entries (r, c), r and c in different effects: sort the n K (K-1) pairs
-  std::vector<int64_t> pairs;
-  pairs.reserve((size_t)n * K_ * (K_ - 1));
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < K_; ++k)
-      for (int l = 0; l < K_; ++l)
-        if (k != l) pairs.push_back((int64_t)(cum_[k] + levels[k][i]) * M_ + (cum_[l] + levels[l][i]));
-  std::sort(pairs.begin(), pairs.end());
-  std::vector<int> rowptr(M_ + 1, 0), split(M_, 0), col;
-  std::vector<double> val;
-  for (size_t a = 0; a < pairs.size();) {
-    size_t b = a;
-    while (b < pairs.size() && pairs[b] == pairs[a]) ++b;
-    const int r = (int)(pairs[a] / M_), c = (int)(pairs[a] % M_);
-    col.push_back(c);
-    val.push_back((double)(b - a));
-    ++rowptr[r + 1];
-    a = b;
-  }
-  for (int r = 0; r < M_; ++r) rowptr[r + 1] += rowptr[r];
+    for (int i = 0; i < n; ++i) {
+      const int e = fill[cum_[k] + levels[k][i]]++;
+      obs[e] = i;
+      if (weighted_) obs_w[e] = zw(k, i);
+    }
   std::vector<int> blk(M_);
   for (int k = 0; k < K_; ++k)
+    for (int r = cum_[k]; r < cum_[k + 1]; ++r) blk[r] = k;
+  // off-diagonal entries (r, c), r and c in different effects: sort the n K (K-1) pairs
+  std::vector<int> rowptr(M_ + 1, 0), split(M_, 0), col;
+  std::vector<double> val;
+  if (!weighted_) {
+    std::vector<int64_t> pairs;
+    pairs.reserve((size_t)n * K_ * (K_ - 1));
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < K_; ++k)
+        for (int l = 0; l < K_; ++l)
+          if (k != l) pairs.push_back((int64_t)(cum_[k] + levels[k][i]) * M_ + (cum_[l] + levels[l][i]));
+    std::sort(pairs.begin(), pairs.end());
+    for (size_t a = 0; a < pairs.size();) {
+      size_t b = a;
+      while (b < pairs.size() && pairs[b] == pairs[a]) ++b;
+      const int r = (int)(pairs[a] / M_), c = (int)(pairs[a] % M_);
+      col.push_back(c);
+      val.push_back((double)(b - a));
+      ++rowptr[r + 1];
+      a = b;
+    }
+  } else {   // the same keys with their observation: the value is sum z_a[i] z_b[i], observations ascending
+    std::vector<std::pair<int64_t, int>> pairs;
+    pairs.reserve((size_t)n * K_ * (K_ - 1));
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < K_; ++k)
+        for (int l = 0; l < K_; ++l)
+          if (k != l) pairs.emplace_back((int64_t)(cum_[k] + levels[k][i]) * M_ + (cum_[l] + levels[l][i]), i);
+    std::sort(pairs.begin(), pairs.end());
+    for (size_t a = 0; a < pairs.size();) {
+      const int r = (int)(pairs[a].first / M_), c = (int)(pairs[a].first % M_);
+      size_t b = a;
+      double v = 0.;
+      for (; b < pairs.size() && pairs[b].first == pairs[a].first; ++b)
+        v += zw(blk[r], pairs[b].second) * zw(blk[c], pairs[b].second);
+      col.push_back(c);
+      val.push_back(v);
+      ++rowptr[r + 1];
+      a = b;
+    }
+  }
+  for (int r = 0; r < M_; ++r) rowptr[r + 1] += rowptr[r];
+  for (int k = 0; k < K_; ++k)
     for (int r = cum_[k]; r < cum_[k + 1]; ++r) {
-      blk[r] = k;
       int e = rowptr[r];
       while (e < rowptr[r + 1] && col[e] < cum_[k]) ++e;
       split[r] = e;
     }
   std::vector<double> cnt(cnt_i.begin(), cnt_i.end());
+  if (weighted_) {   // sum z_k[i]^2 in the order of the observation lists (ascending)
+    for (int r = 0; r < M_; ++r) {
+      double v = 0.;
+      for (int e = optr[r]; e < optr[r + 1]; ++e) v += obs_w[e] * obs_w[e];
+      cnt[r] = v;
+    }
+  }
   rowptr_h_ = rowptr;
   split_h_ = split;
   const size_t nnz = std::max<size_t>(col.size(), 1);
@@ -92,6 +130,10 @@ GroupedRE::GroupedRE(int n, const std::vector<std::vector<int>>& levels, hipStre
   HIP_CHECK(hipMemcpyAsync(d_cnt_.get(), cnt.data(), sizeof(double) * M_, hipMemcpyHostToDevice, s_));
   HIP_CHECK(hipMemcpyAsync(d_obs_ptr_.get(), optr.data(), sizeof(int) * (M_ + 1), hipMemcpyHostToDevice, s_));
   HIP_CHECK(hipMemcpyAsync(d_obs_.get(), obs.data(), sizeof(int) * obs.size(), hipMemcpyHostToDevice, s_));
+  if (weighted_) {
+    d_obs_w_.alloc(obs_w.size());
+    HIP_CHECK(hipMemcpyAsync(d_obs_w_.get(), obs_w.data(), sizeof(double) * obs_w.size(), hipMemcpyHostToDevice, s_));
+  }
   for (auto* b : {&d_D_, &d_sqrtD_, &d_zty_, &d_u_, &d_ztzu_}) b->alloc(M_);
   d_tau_.alloc(K_);
   d_dsum_.alloc(2 * K_);
@@ -111,7 +153,8 @@ GroupedRE::~GroupedRE() {
 void GroupedRE::SetY(const double* y) {
   d_y_.alloc(n_);
   HIP_CHECK(hipMemcpyAsync(d_y_.get(), y, sizeof(double) * n_, hipMemcpyHostToDevice, s_));
-  launch_gre_zty(M_, d_obs_ptr_.get(), d_obs_.get(), d_y_.get(), d_zty_.get(), s_);
+  launch_gre_zty(M_, d_obs_ptr_.get(), d_obs_.get(), weighted_ ? d_obs_w_.get() : nullptr, d_y_.get(), d_zty_.get(),
+                 s_);
   const double* A[1] = {d_y_.get()};
   const double* B[1] = {d_y_.get()};
   launch_coldots(n_, 1, 1, A, B, d_partials_.get(), d_yty_.get(), s_);
@@ -418,18 +461,20 @@ void GroupedRE::Blup(const double* tau, bool iterative, bool warm, const Iterati
     }
 }
 
-void GroupedRE::PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out, const double* D_k1) {
+void GroupedRE::PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out, const double* D_k1,
+                        const double* wt) {
   if (np <= 0) return;
   if (K_ == 1) {   // A^-1 = diag(1/D)
     std::vector<double> D(M_);
     HIP_CHECK(hipMemcpyAsync(D.data(), D_k1 != nullptr ? D_k1 : d_D_.get(), sizeof(double) * M_, hipMemcpyDeviceToHost, s_));
     HIP_CHECK(hipStreamSynchronize(s_));
+    auto w = [&](int p) { return wt != nullptr ? wt[p] : 1.; };
     if (want_cov) {
       for (int q = 0; q < np; ++q)
         for (int p = 0; p < np; ++p)
-          out[(size_t)q * np + p] = (idx[p] >= 0 && idx[p] == idx[q]) ? 1. / D[idx[p]] : 0.;
+          out[(size_t)q * np + p] = (idx[p] >= 0 && idx[p] == idx[q]) ? w(p) * w(q) / D[idx[p]] : 0.;
     } else {
-      for (int p = 0; p < np; ++p) out[p] = idx[p] >= 0 ? 1. / D[idx[p]] : 0.;
+      for (int p = 0; p < np; ++p) out[p] = idx[p] >= 0 ? w(p) * w(p) / D[idx[p]] : 0.;
     }
     return;
   }
@@ -437,15 +482,20 @@ void GroupedRE::PredCov(int np, const std::vector<int>& idx, bool want_cov, doub
   const int ld = ldM_;
   DevBuf<int> d_idx(idx.size());
   HIP_CHECK(hipMemcpyAsync(d_idx.get(), idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, s_));
+  DevBuf<double> d_wt;
+  if (wt != nullptr) {
+    d_wt.alloc(idx.size());
+    HIP_CHECK(hipMemcpyAsync(d_wt.get(), wt, sizeof(double) * idx.size(), hipMemcpyHostToDevice, s_));
+  }
   if (want_cov) {
     DevBuf<double> E((size_t)ld * np), C((size_t)np * np);
     HIP_CHECK(hipMemsetAsync(E.get(), 0, sizeof(double) * (size_t)ld * np, s_));
-    launch_gre_pred_cols(M_, ld, K_, np, d_idx.get(), dW_.get(), E.get(), nullptr, s_);
+    launch_gre_pred_cols(M_, ld, K_, np, d_idx.get(), d_wt.get(), dW_.get(), E.get(), nullptr, s_);
     gemm_f64(s_, np, np, M_, 1., E.get(), ld, 1, E.get(), ld, 0, 0., C.get(), np);
     HIP_CHECK(hipMemcpyAsync(out, C.get(), sizeof(double) * (size_t)np * np, hipMemcpyDeviceToHost, s_));
   } else {
     DevBuf<double> v(np);
-    launch_gre_pred_cols(M_, ld, K_, np, d_idx.get(), dW_.get(), nullptr, v.get(), s_);
+    launch_gre_pred_cols(M_, ld, K_, np, d_idx.get(), d_wt.get(), dW_.get(), nullptr, v.get(), s_);
     HIP_CHECK(hipMemcpyAsync(out, v.get(), sizeof(double) * np, hipMemcpyDeviceToHost, s_));
   }
   HIP_CHECK(hipStreamSynchronize(s_));

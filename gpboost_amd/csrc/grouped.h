@@ -51,7 +51,14 @@ class GroupedRE {
  public:
   // levels: K x n, levels[k][i] = level index (0 .. m_k - 1, order of first appearance) of
   // observation i for effect k.
-  GroupedRE(int n, const std::vector<std::vector<int>>& levels, hipStream_t s);
+  // weights (empty, or K host pointers to n doubles, null = all ones): Z[i, level of i in effect k] = weights[k][i],
+  // the covariate of a random slope; an intercept has the weight 1. Two effects may share their levels (the
+  // intercept and the slopes of one grouping variable): level l of the one then couples with level l of the other
+  // through the ordinary pair entries of Z^T Z, and the diagonal block of every single effect stays diagonal. The
+  // diagonal of Z^T Z is sum z_k[i]^2, an off-diagonal value sum z_a[i] z_b[i], both over the observations ascending
+  // (an entry whose products sum to 0 stays in the structure); without weights both are the integer counts.
+  GroupedRE(int n, const std::vector<std::vector<int>>& levels, hipStream_t s,
+            const std::vector<const double*>& weights = {});
   ~GroupedRE();
   GroupedRE(const GroupedRE&) = delete;
   GroupedRE& operator=(const GroupedRE&) = delete;
@@ -77,13 +84,20 @@ class GroupedRE {
   // U - sum_k tau_k [same seen level] + e_p^T A^-1 e_q. K >= 2: E = Li [e_p] on the device (one wave per
   // point), variances ||E_p||^2, covariances E^T E on the MFMA GEMM; K == 1: A^-1 = diag(1/D).
   // D_k1 (nullable, device, M): the diagonal of A for K == 1 when it is not the Gaussian model's own
-  void PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out, const double* D_k1 = nullptr);
+  // wt (nullable, np x K): Z's values z_k(p) of the prediction points (random slopes); e_p then holds them in the
+  // place of the ones. The derivation uses only Z^T Z = A - Sigma^-1, so it holds for any Z; the term U =
+  // sum_k tau_k z_k(p) z_k(q) [same unseen label] is the caller's.
+  void PredCov(int np, const std::vector<int>& idx, bool want_cov, double* out, const double* D_k1 = nullptr,
+               const double* wt = nullptr);
+  bool weighted() const { return weighted_; }
   // Fisher information of the original-scale parameters [sigma^2, sigma_1^2 .. sigma_K^2] (cholesky;
   // CalcFisherInformation_Only_Grouped_REs_Woodbury re_model_template.h:9559-9651 with transf_scale =
   // false): with B = S^1/2 A^-1 S^1/2 (S = Sigma^-1 on the transformed scale), F_jk = ||B_jk||_F^2 and
   // t_j = tr(B_jj), Z_j^T Psi^-1 Z_k = S^1/2 (delta_jk I - B_jk) S^1/2 and Psi^-1 Z = Z A^-1 S give
   //   2 sigma^4 FI_00 = n - M + sum_jk F_jk,  2 sigma^4 FI_0j = (t_j - sum_k F_jk) / tau_j,
   //   2 sigma^4 FI_jk = (F_jk + delta_jk (m_j - 2 t_j)) / (tau_j tau_k).
+  // All of it (the n - M of FI_00 included: tr(Psi^-2) = n - 2 tr(A^-1 Z^T Z) + tr((A^-1 Z^T Z)^2) with
+  // A^-1 Z^T Z = I - A^-1 Sigma^-1) uses Z only through Z^T Z = A - Sigma^-1 and so holds for weighted Z.
   // Factors A at tau first. FI: (1 + K)^2 row-major.
   void Fisher(const double* tau, double sigma2, double* FI);
   // the pieces of both forms: F (K x K, F_jk = ||B_jk||_F^2) and t_j = tr(B_jj)
@@ -173,6 +187,8 @@ class GroupedRE {
   DevBuf<double> d_chunk_partials_;
   DevBuf<int> d_rowptr_, d_split_, d_col_, d_blk_, d_obs_ptr_, d_obs_, d_cum_;
   DevBuf<double> d_val_, d_cnt_, d_D_, d_sqrtD_, d_tau_, d_dsum_;
+  DevBuf<double> d_obs_w_;   // weighted: Z's value of every entry of d_obs_
+  bool weighted_ = false;
   DevBuf<double> d_zty_, d_y_, d_yty_, d_u_, d_ztzu_, d_partials_, d_out_;
   DevBuf<double> d_probes_, d_probesP_, d_PI_, d_DI_;
   double* h_out_ = nullptr;   // pinned

@@ -18,7 +18,8 @@ struct GreChunks {
 };
 
 // Off-diagonal part of Z^T Z in CSR over the M RE rows (columns ascending; entries [rowptr[r],
-// split[r]) belong to lower effects, [split[r], rowptr[r+1]) to higher ones), values = counts, and
+// split[r]) belong to lower effects, [split[r], rowptr[r+1]) to higher ones), values = counts (sums of
+// z_a[i] z_b[i] with random slopes), and
 // its chunk plans for a t-column pass: tc = min(64, next_pow2(t)) lanes span columns, 256 / tc
 // lanes of a workgroup span the entries of one chunk (chunk length = 8 entries per lane).
 struct GroupedOp {
@@ -34,7 +35,10 @@ struct GroupedOp {
 int gre_tc(int t);
 int gre_chunk_len(int tc);
 
-void launch_gre_zty(int M, const int* obs_ptr, const int* obs, const double* y, double* zty, hipStream_t s);
+// zty[r] = sum over the entries e of level r's observation list of w[e] y[obs[e]] (w null: all ones, the
+// unweighted kernel; else Z's value of the entry: the slope covariate of a random-slope component)
+void launch_gre_zty(int M, const int* obs_ptr, const int* obs, const double* w, const double* y, double* zty,
+                    hipStream_t s);
 // D = 1/tau_k + cnt, dis = sqrt(1/D); out[k] = sum_{effect k} log D, out[K + k] = sum 1/D
 void launch_gre_diag(int K, const int* cum, const double* cnt, const double* tau, double* D, double* dis, double* out,
                      hipStream_t s);
@@ -63,10 +67,10 @@ void launch_gre_residual(size_t count, const double* rhs, const double* V, doubl
 void launch_gre_dense_build(int M, int ld, const int* rowptr, const int* col, const double* val, const double* D,
                             double* A, hipStream_t s);
 void launch_gre_inv_diag(int M, int ld, const double* Li, double* out, hipStream_t s);
-// E[:, p] = sum_k Li[:, idx[p K + k]] (lower part only; idx < 0 skipped) into E (M x np, ld), or (E null)
-// var[p] = ||that column||^2
-void launch_gre_pred_cols(int M, int ld, int K, int np, const int* idx, const double* Li, double* E, double* var,
-                          hipStream_t s);
+// E[:, p] = sum_k wt[p K + k] Li[:, idx[p K + k]] (lower part only; idx < 0 skipped; wt null: all ones, the
+// unweighted kernel) into E (M x np, ld), or (E null) var[p] = ||that column||^2
+void launch_gre_pred_cols(int M, int ld, int K, int np, const int* idx, const double* wt, const double* Li, double* E,
+                          double* var, hipStream_t s);
 // Fisher information pieces (cholesky): B = S^1/2 A^-1 S^1/2 (sc[r] = 1 / sqrt(tau_k(r))) from the dense
 // A^-1 (Ainv, ld); part[c K + k] = sum_{r in effect k} B[r, c]^2, diag[c] = B[c, c]. One wave per column.
 void launch_gre_fisher_cols(int M, int ld, int K, const int* cum, const double* sc, const double* Ainv, double* part,

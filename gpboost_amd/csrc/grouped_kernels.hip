@@ -90,15 +90,17 @@ __global__ void __launch_bounds__(256) gre_combine_kernel(int row0, int row1, in
   }
 }
 
-// Z^T y: one wave per RE level, lanes stride its observations, fixed-order butterfly.
+// Z^T y: one wave per RE level, lanes stride its observations, fixed-order butterfly. WEIGHTED (random slopes):
+// entry e of the observation lists carries Z's value w[e] (streamed beside obs; 1 for an intercept).
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256) gre_zty_kernel(int M, const int* __restrict__ obs_ptr,
-                                                      const int* __restrict__ obs, const double* __restrict__ y,
-                                                      double* __restrict__ zty) {
+                                                      const int* __restrict__ obs, const double* __restrict__ w,
+                                                      const double* __restrict__ y, double* __restrict__ zty) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= M) return;
   double s = 0.;
-  for (int e = obs_ptr[r] + lane; e < obs_ptr[r + 1]; e += 64) s += y[obs[e]];
+  for (int e = obs_ptr[r] + lane; e < obs_ptr[r + 1]; e += 64) s += WEIGHTED ? w[e] * y[obs[e]] : y[obs[e]];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
   if (lane == 0) zty[r] = s;
@@ -217,8 +219,12 @@ int gre_tc(int t) {
 
 int gre_chunk_len(int tc) { return (256 / tc) * kEntriesPerLane; }
 
-void launch_gre_zty(int M, const int* obs_ptr, const int* obs, const double* y, double* zty, hipStream_t s) {
-  hipLaunchKernelGGL(gre_zty_kernel, dim3((M + 3) / 4), dim3(256), 0, s, M, obs_ptr, obs, y, zty);
+void launch_gre_zty(int M, const int* obs_ptr, const int* obs, const double* w, const double* y, double* zty,
+                    hipStream_t s) {
+  if (w != nullptr)
+    hipLaunchKernelGGL(gre_zty_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, s, M, obs_ptr, obs, w, y, zty);
+  else
+    hipLaunchKernelGGL(gre_zty_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, s, M, obs_ptr, obs, w, y, zty);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -292,7 +298,10 @@ __global__ void __launch_bounds__(256) gre_inv_diag_kernel(int M, int ld, const 
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if (lane == 0) out[i] = s;
 }
+// WEIGHTED: column k enters with the coefficient wt[p K + k] = z_k(p) (random slopes) instead of 1
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256) gre_pred_cols_kernel(int M, int ld, int K, int np, const int* __restrict__ idx,
+                                                            const double* __restrict__ wt,
                                                             const double* __restrict__ Li, double* __restrict__ E,
                                                             double* __restrict__ var) {
   const int lane = threadIdx.x & 63;
@@ -304,7 +313,7 @@ __global__ void __launch_bounds__(256) gre_pred_cols_kernel(int M, int ld, int K
     double v = 0.;
     for (int k = 0; k < K; ++k) {
       const int a = ip[k];
-      if (a >= 0 && r >= a) v += Li[(size_t)a * ld + r];
+      if (a >= 0 && r >= a) v += WEIGHTED ? wt[(size_t)p * K + k] * Li[(size_t)a * ld + r] : Li[(size_t)a * ld + r];
     }
     if (E) E[(size_t)p * ld + r] = v;
     s = fma(v, v, s);
@@ -342,9 +351,14 @@ void launch_gre_fisher_cols(int M, int ld, int K, const int* cum, const double* 
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_gre_pred_cols(int M, int ld, int K, int np, const int* idx, const double* Li, double* E, double* var,
-                          hipStream_t s) {
-  hipLaunchKernelGGL(gre_pred_cols_kernel, dim3((np + 3) / 4), dim3(256), 0, s, M, ld, K, np, idx, Li, E, var);
+void launch_gre_pred_cols(int M, int ld, int K, int np, const int* idx, const double* wt, const double* Li, double* E,
+                          double* var, hipStream_t s) {
+  if (wt != nullptr)
+    hipLaunchKernelGGL(gre_pred_cols_kernel<true>, dim3((np + 3) / 4), dim3(256), 0, s, M, ld, K, np, idx, wt, Li, E,
+                       var);
+  else
+    hipLaunchKernelGGL(gre_pred_cols_kernel<false>, dim3((np + 3) / 4), dim3(256), 0, s, M, ld, K, np, idx, wt, Li, E,
+                       var);
   HIP_CHECK(hipGetLastError());
 }
 

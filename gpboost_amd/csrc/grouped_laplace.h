@@ -33,6 +33,12 @@
 // at most 32 observations are summed by one thread each; longer lists (the levels of an effect with few
 // levels) are cut into chunks of 512 summed by one wave each, and the chunk partials are added in chunk order.
 // No floating-point atomics: equal inputs give equal bits.
+//
+// Random slopes (Z[i, lev_k(i)] = z_k[i] instead of 1): every formula above holds for any Z. The kernels have a
+// second, WEIGHTED instantiation: the per-observation gathers multiply by z_k[i] read from a K x n table, and the
+// segmented sums multiply each list entry by its precomputed value of Z (z_a[i], or z_a[i] z_b[i] for a destination
+// of Z^T W Z), stored beside the observation index: one streamed double per entry, where two gathers from the
+// table would move two 64-byte sectors. Models without slopes run the unweighted instantiation, unchanged.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -58,7 +64,9 @@ class GroupedLaplace {
  public:
   // where the Newton iterations begin (as LatentSolverBase::ModeStart, latent.h)
   enum class Start { kZero, kWarm, kKeep };
-  GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>>& levels, int lik);
+  // weights: as GroupedRE's (the same arrays; empty or all null: no random slopes, the unweighted kernels run)
+  GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>>& levels, int lik,
+                 const std::vector<const double*>& weights = {});
   ~GroupedLaplace();
   GroupedLaplace(const GroupedLaplace&) = delete;
   GroupedLaplace& operator=(const GroupedLaplace&) = delete;
@@ -83,8 +91,9 @@ class GroupedLaplace {
   void ResetModeToPrevious();
   void ClearModePrevious() { mode_prev_valid_ = false; }
   void GetMode(double* b);                 // host, M (effect-major)
-  // e_p^T A^-1 e_p on the factor of the last evaluation (idx: np x K global level indices, -1: unseen)
-  void PredVar(int np, const std::vector<int>& idx, double* out);
+  // e_p^T A^-1 e_p on the factor of the last evaluation (idx: np x K global level indices, -1: unseen; wt nullable,
+  // np x K: Z's values of the prediction points, the entries of e_p)
+  void PredVar(int np, const std::vector<int>& idx, double* out, const double* wt = nullptr);
   // test hook: the diagonal (M) and the off-diagonal CSR values (nnz) of Z^T W Z of the last evaluation
   void GetZtWZ(double* diag, double* vals);
   // test hook (grouped_test.cpp): Assemble on a caller's w, the level table and the segment counts
@@ -102,6 +111,11 @@ class GroupedLaplace {
   hipStream_t s_;
   int nb_ = 1;   // blocks of the observation passes
   DevBuf<int> d_glev_;   // K x n global level indices
+  // random slopes (wt_): Z's values as the K x n table of the per-observation gathers (eta, q, the probe rows,
+  // grad_F) and per entry of the inverted index (d_seg_w1_: z_k[i] over the M level lists, for Z^T v; d_seg_w2_:
+  // z_k[i]^2 over them and z_a[i] z_b[i] over the pair lists, for Z^T W Z). Null without slopes.
+  bool wt_ = false;
+  DevBuf<double> d_zw_, d_seg_w1_, d_seg_w2_;
   // inverted index: destination -> observations
   DevBuf<int> d_seg_ptr_, d_seg_obs_, d_c0_, d_c1_, d_long_dst_, d_long_cptr_;
   int n_chunks_ = 0, n_chunks_diag_ = 0, n_long_ = 0, n_long_diag_ = 0;

@@ -51,10 +51,11 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
 }
 
 // Observation pass: eta_i = F_i + sum_k b[lev_k(i)] (K gathers), the log-likelihood summed per block, and
-// (DERIV) d1, W and, when asked, dW / deta from the same read of y.
-template <bool DERIV>
+// (DERIV) d1, W and, when asked, dW / deta from the same read of y. WT (random slopes): eta_i = F_i + sum_k
+// zw[k n + i] b[lev_k(i)], one more coalesced read per gather.
+template <bool DERIV, bool WT>
 __global__ void __launch_bounds__(256) glp_obs_kernel(int n, int K, const int* __restrict__ glev,
-                                                      const double* __restrict__ y, const double* __restrict__ F,
+                                                      const double* __restrict__ zw, const double* __restrict__ y, const double* __restrict__ F,
                                                       const double* __restrict__ b, int lik, double aux,
                                                       double* __restrict__ d1, double* __restrict__ W,
                                                       double* __restrict__ dW, double* __restrict__ partial) {
@@ -64,7 +65,8 @@ __global__ void __launch_bounds__(256) glp_obs_kernel(int n, int K, const int* _
     const double log_r = log(aux);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
       double eta = F != nullptr ? F[i] : 0.;
-      for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+      for (int k = 0; k < K; ++k)
+        eta += WT ? zw[(size_t)k * n + i] * b[glev[(size_t)k * n + i]] : b[glev[(size_t)k * n + i]];
       const double yi = y[i];
       ll += nb_loglik(aux, log_r, yi, eta);
       if (DERIV) {
@@ -76,7 +78,8 @@ __global__ void __launch_bounds__(256) glp_obs_kernel(int n, int K, const int* _
   } else {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
       double eta = F != nullptr ? F[i] : 0.;
-      for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+      for (int k = 0; k < K; ++k)
+        eta += WT ? zw[(size_t)k * n + i] * b[glev[(size_t)k * n + i]] : b[glev[(size_t)k * n + i]];
       const double yi = y[i];
       ll += lik_loglik(lik, aux, yi, eta);
       if (DERIV) {
@@ -93,8 +96,9 @@ __global__ void __launch_bounds__(256) glp_obs_kernel(int n, int K, const int* _
 // negative_binomial, at the converged mode: the shape derivatives dd1 / dlog r and dW / dlog r per observation and
 // per block the sum of log(mu_i + r) + (y_i + r) / (mu_i + r) (the explicit shape gradient, likelihoods.h:10527-10538);
 // grid, stride and block sum as glp_obs_kernel, finished by glp_finish_kernel
+template <bool WT>
 __global__ void __launch_bounds__(256) glp_nb_aux_kernel(int n, int K, const int* __restrict__ glev,
-                                                         const double* __restrict__ y, const double* __restrict__ F,
+                                                         const double* __restrict__ zw, const double* __restrict__ y, const double* __restrict__ F,
                                                          const double* __restrict__ b, double aux,
                                                          double* __restrict__ dd1a, double* __restrict__ dWa,
                                                          double* __restrict__ partial) {
@@ -103,7 +107,8 @@ __global__ void __launch_bounds__(256) glp_nb_aux_kernel(int n, int K, const int
   double acc = 0.;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     double eta = F != nullptr ? F[i] : 0.;
-    for (int k = 0; k < K; ++k) eta += b[glev[(size_t)k * n + i]];
+    for (int k = 0; k < K; ++k)
+      eta += WT ? zw[(size_t)k * n + i] * b[glev[(size_t)k * n + i]] : b[glev[(size_t)k * n + i]];
     const double yi = y[i];
     dd1a[i] = nb_dd1_aux(aux, log_r, yi, eta);
     dWa[i] = nb_dinfo_aux(aux, log_r, yi, eta);
@@ -123,29 +128,34 @@ __global__ void __launch_bounds__(256) glp_finish_kernel(int nb, const double* _
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
-// Segmented sums, short destinations: out[d] = sum of w over d's observations, in list order
+// Segmented sums, short destinations: out[d] = sum of w over d's observations, in list order. WT (random slopes):
+// entry e of the lists carries the precomputed value sw[e] of Z (z_a[i] for Z^T v, z_a[i] z_b[i] for a destination
+// of Z^T W Z), streamed beside obs[e].
+template <bool WT>
 __global__ void __launch_bounds__(256) glp_seg_short_kernel(int ndst, const int* __restrict__ ptr,
-                                                            const int* __restrict__ obs, const double* __restrict__ w,
-                                                            double* __restrict__ out) {
+                                                            const int* __restrict__ obs, const double* __restrict__ sw,
+                                                            const double* __restrict__ w, double* __restrict__ out) {
   const int d = blockIdx.x * 256 + threadIdx.x;
   if (d >= ndst) return;
   const int e0 = ptr[d], e1 = ptr[d + 1];
   if (e1 - e0 > kShortLen) return;   // chunked
   double s = 0.;
-  for (int e = e0; e < e1; ++e) s += w[obs[e]];
+  for (int e = e0; e < e1; ++e) s += WT ? sw[e] * w[obs[e]] : w[obs[e]];
   out[d] = s;
 }
 
 // long destinations, stage 1: one wave per chunk
+template <bool WT>
 __global__ void __launch_bounds__(256) glp_seg_chunk_kernel(int nchunks, const int* __restrict__ c0,
                                                             const int* __restrict__ c1, const int* __restrict__ obs,
-                                                            const double* __restrict__ w, double* __restrict__ P) {
+                                                            const double* __restrict__ sw, const double* __restrict__ w,
+                                                            double* __restrict__ P) {
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= nchunks) return;   // wave-uniform
   const int lane = threadIdx.x & 63;
   double s = 0.;
   const int e1 = c1[q];
-  for (int e = c0[q] + lane; e < e1; e += 64) s += w[obs[e]];
+  for (int e = c0[q] + lane; e < e1; e += 64) s += WT ? sw[e] * w[obs[e]] : w[obs[e]];
   s = lane_group_sum<64>(s);
   if (lane == 0) P[q] = s;
 }
@@ -195,9 +205,11 @@ __global__ void __launch_bounds__(256) glp_effect_dots_kernel(EffArgs a, const d
 
 // q_ij = sum_k A^-1[lev_j(i), lev_k(i)] (K^2 gathers from the dense inverse; K == 1: 1 / D), q_i = sum_j q_ij;
 // written: dwq_i = dW_i q_i / 2 and per block the sums of W_i q_ij (column j); AUX: also the sums of Wa_i q_i
-// (column K: the determinant term of a shape whose dW / dlog shape is not W)
-template <bool AUX>
+// (column K: the determinant term of a shape whose dW / dlog shape is not W). WT (random slopes): q_ij =
+// z_j(i) sum_k z_k(i) A^-1[lev_j(i), lev_k(i)] (K == 1: z^2 / D), z from the K x n table zw.
+template <bool AUX, bool WT>
 __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __restrict__ glev,
+                                                    const double* __restrict__ zw,
                                                     const double* __restrict__ Ainv, int ld,
                                                     const double* __restrict__ D, const double* __restrict__ W,
                                                     const double* __restrict__ dW, const double* __restrict__ Wa,
@@ -211,6 +223,11 @@ __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __r
     int g[kGlpMaxK];
 #pragma unroll
     for (int k = 0; k < kGlpMaxK; ++k) g[k] = k < K ? glev[(size_t)k * n + i] : 0;
+    double z[kGlpMaxK];
+    if (WT) {
+#pragma unroll
+      for (int k = 0; k < kGlpMaxK; ++k) z[k] = k < K ? zw[(size_t)k * n + i] : 0.;
+    }
     const double wi = W[i];
     double qi = 0.;
 #pragma unroll
@@ -218,7 +235,12 @@ __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __r
       if (j < K) {
         double qj = 0.;
         if (Ainv == nullptr) {
-          qj = 1. / D[g[0]];
+          qj = WT ? z[0] * z[0] / D[g[0]] : 1. / D[g[0]];
+        } else if (WT) {
+#pragma unroll
+          for (int k = 0; k < kGlpMaxK; ++k)
+            if (k < K) qj += z[k] * Ainv[(size_t)g[k] * ld + g[j]];
+          qj *= z[j];
         } else {
           for (int k = 0; k < K; ++k) qj += Ainv[(size_t)g[k] * ld + g[j]];
         }
@@ -243,23 +265,29 @@ __global__ void __launch_bounds__(256) glp_q_kernel(int n, int K, const int* __r
 }
 
 // iterative: dwq_i = dW_i mean_c[(Z U)_ic (Z V)_ic] / 2 from the M x t blocks U = A^-1 z and V = P^-1 z (row-major:
-// K gathered rows of t doubles per observation; no n x t matrix is formed)
+// K gathered rows of t doubles per observation; no n x t matrix is formed). WT: row k enters with z_k(i).
+template <bool WT>
 __global__ void __launch_bounds__(256) glp_row_trace_kernel(int n, int K, int t, const int* __restrict__ glev,
-                                                            const double* __restrict__ U, const double* __restrict__ V,
+                                                            const double* __restrict__ zw, const double* __restrict__ U, const double* __restrict__ V,
                                                             const double* __restrict__ dW, double* __restrict__ dwq) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   size_t g[kGlpMaxK];
 #pragma unroll
   for (int k = 0; k < kGlpMaxK; ++k) g[k] = k < K ? (size_t)glev[(size_t)k * n + i] * t : 0;
+  double z[kGlpMaxK];
+  if (WT) {
+#pragma unroll
+    for (int k = 0; k < kGlpMaxK; ++k) z[k] = k < K ? zw[(size_t)k * n + i] : 0.;
+  }
   double acc = 0.;
   for (int c = 0; c < t; ++c) {
     double a = 0., p = 0.;
 #pragma unroll
     for (int k = 0; k < kGlpMaxK; ++k) {
       if (k < K) {
-        a += U[g[k] + c];
-        p += V[g[k] + c];
+        a += WT ? z[k] * U[g[k] + c] : U[g[k] + c];
+        p += WT ? z[k] * V[g[k] + c] : V[g[k] + c];
       }
     }
     acc += a * p;
@@ -268,14 +296,16 @@ __global__ void __launch_bounds__(256) glp_row_trace_kernel(int n, int K, int t,
 }
 
 // gradient wrt the fixed effects: -d1_i + dW_i q_i / 2 - W_i (Z v)_i
+template <bool WT>
 __global__ void __launch_bounds__(256) glp_grad_f_kernel(int n, int K, const int* __restrict__ glev,
-                                                         const double* __restrict__ d1, const double* __restrict__ dwq,
+                                                         const double* __restrict__ zw, const double* __restrict__ d1, const double* __restrict__ dwq,
                                                          const double* __restrict__ W, const double* __restrict__ v,
                                                          double* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   double zv = 0.;
-  for (int k = 0; k < K; ++k) zv += v[glev[(size_t)k * n + i]];
+  for (int k = 0; k < K; ++k)
+    zv += WT ? zw[(size_t)k * n + i] * v[glev[(size_t)k * n + i]] : v[glev[(size_t)k * n + i]];
   out[i] = -d1[i] + dwq[i] - W[i] * zv;
 }
 
@@ -283,11 +313,56 @@ inline int blocks_of(int count) { return (count + 255) / 256; }
 // blocks of an observation pass (nb_)
 inline int obs_blocks(int n) { return std::max(1, std::min(blocks_of(n), kMaxBlocks)); }
 
+// Launches of the observation kernels: zw null runs the unweighted instantiation (models without random slopes),
+// else the weighted one on the K x n table of Z's values.
+void launch_glp_obs(int nb, bool deriv, const double* zw, int n, int K, const int* glev, const double* y,
+                    const double* F, const double* b, int lik, double aux, double* d1, double* W, double* dW,
+                    double* partial, hipStream_t s) {
+  if (zw != nullptr) {
+    if (deriv) glp_obs_kernel<true, true><<<nb, 256, 0, s>>>(n, K, glev, zw, y, F, b, lik, aux, d1, W, dW, partial);
+    else glp_obs_kernel<false, true><<<nb, 256, 0, s>>>(n, K, glev, zw, y, F, b, lik, aux, nullptr, nullptr, nullptr, partial);
+  } else {
+    if (deriv) glp_obs_kernel<true, false><<<nb, 256, 0, s>>>(n, K, glev, zw, y, F, b, lik, aux, d1, W, dW, partial);
+    else glp_obs_kernel<false, false><<<nb, 256, 0, s>>>(n, K, glev, zw, y, F, b, lik, aux, nullptr, nullptr, nullptr, partial);
+  }
+}
+void launch_glp_nb_aux(int nb, const double* zw, int n, int K, const int* glev, const double* y, const double* F,
+                       const double* b, double aux, double* dd1a, double* dWa, double* partial, hipStream_t s) {
+  if (zw != nullptr) glp_nb_aux_kernel<true><<<nb, 256, 0, s>>>(n, K, glev, zw, y, F, b, aux, dd1a, dWa, partial);
+  else glp_nb_aux_kernel<false><<<nb, 256, 0, s>>>(n, K, glev, zw, y, F, b, aux, dd1a, dWa, partial);
+}
+void launch_glp_q(int nb, bool aux, const double* zw, int n, int K, const int* glev, const double* Ainv, int ld,
+                  const double* D, const double* W, const double* dW, const double* Wa, double* dwq, double* partial,
+                  hipStream_t s) {
+  if (zw != nullptr) {
+    if (aux) glp_q_kernel<true, true><<<nb, 256, 0, s>>>(n, K, glev, zw, Ainv, ld, D, W, dW, Wa, dwq, partial);
+    else glp_q_kernel<false, true><<<nb, 256, 0, s>>>(n, K, glev, zw, Ainv, ld, D, W, dW, nullptr, dwq, partial);
+  } else {
+    if (aux) glp_q_kernel<true, false><<<nb, 256, 0, s>>>(n, K, glev, zw, Ainv, ld, D, W, dW, Wa, dwq, partial);
+    else glp_q_kernel<false, false><<<nb, 256, 0, s>>>(n, K, glev, zw, Ainv, ld, D, W, dW, nullptr, dwq, partial);
+  }
+}
+void launch_glp_row_trace(const double* zw, int n, int K, int t, const int* glev, const double* U, const double* V,
+                          const double* dW, double* dwq, hipStream_t s) {
+  if (zw != nullptr) glp_row_trace_kernel<true><<<blocks_of(n), 256, 0, s>>>(n, K, t, glev, zw, U, V, dW, dwq);
+  else glp_row_trace_kernel<false><<<blocks_of(n), 256, 0, s>>>(n, K, t, glev, zw, U, V, dW, dwq);
+}
+void launch_glp_grad_f(const double* zw, int n, int K, const int* glev, const double* d1, const double* dwq,
+                       const double* W, const double* v, double* out, hipStream_t s) {
+  if (zw != nullptr) glp_grad_f_kernel<true><<<blocks_of(n), 256, 0, s>>>(n, K, glev, zw, d1, dwq, W, v, out);
+  else glp_grad_f_kernel<false><<<blocks_of(n), 256, 0, s>>>(n, K, glev, zw, d1, dwq, W, v, out);
+}
+
 }  // namespace
 
-GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>>& levels, int lik)
+GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>>& levels, int lik,
+                               const std::vector<const double*>& weights)
     : re_(re), v_(re->view()), lik_(lik), s_(v_.s) {
   const int n = v_.n, K = v_.K, M = v_.M;
+  if (!weights.empty() && (int)weights.size() != K) Fatal("grouped random effects: one weight array per effect");
+  for (const double* w : weights) wt_ = wt_ || w != nullptr;
+  if (wt_ != re->weighted()) Fatal("internal error: the weights of GroupedLaplace and GroupedRE differ");
+  auto zw = [&](int k, int i) { return weights[k] != nullptr ? weights[k][i] : 1.; };
   if (K > kGlpMaxK)
     Fatal("non-Gaussian likelihoods with grouped random effects: at most %d grouping variables are supported by "
           "gpboost_amd", kGlpMaxK);
@@ -301,14 +376,32 @@ GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>
   const int ND = M + v_.nnz;
   std::vector<int> ptr(ND + 1, 0), obs;
   obs.reserve((size_t)n * K * K);
+  // weighted: Z's value of every list entry, z_k[i] for the M levels as destinations of Z^T v (w1) and z_k[i]^2 /
+  // z_a[i] z_b[i] for the destinations of Z^T W Z (w2)
+  std::vector<double> w1, w2;
+  std::vector<int> blk(wt_ ? M : 0);
+  for (int k = 0; wt_ && k < K; ++k)
+    for (int r = cum[k]; r < cum[k + 1]; ++r) blk[r] = k;
   {
     std::vector<int> cnt(M, 0);
     for (size_t e = 0; e < glev.size(); ++e) ++cnt[glev[e]];
     for (int r = 0; r < M; ++r) ptr[r + 1] = ptr[r] + cnt[r];
     obs.resize((size_t)n * K);
     std::vector<int> fill(ptr.begin(), ptr.begin() + M);
+    if (wt_) {
+      w1.resize((size_t)n * K);
+      w2.reserve((size_t)n * K * K);
+      w2.resize((size_t)n * K);
+    }
     for (int k = 0; k < K; ++k)
-      for (int i = 0; i < n; ++i) obs[fill[glev[(size_t)k * n + i]]++] = i;
+      for (int i = 0; i < n; ++i) {
+        const int e = fill[glev[(size_t)k * n + i]]++;
+        obs[e] = i;
+        if (wt_) {
+          w1[e] = zw(k, i);
+          w2[e] = w1[e] * w1[e];
+        }
+      }
   }
   if (K > 1) {
     std::vector<std::pair<int64_t, int>> pairs;
@@ -322,7 +415,11 @@ GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>
     int slot = 0;
     for (size_t a = 0; a < pairs.size();) {
       size_t b = a;
-      while (b < pairs.size() && pairs[b].first == pairs[a].first) obs.push_back(pairs[b++].second);
+      const int pr = (int)(pairs[a].first / M), pc = (int)(pairs[a].first % M);
+      while (b < pairs.size() && pairs[b].first == pairs[a].first) {
+        if (wt_) w2.push_back(zw(blk[pr], pairs[b].second) * zw(blk[pc], pairs[b].second));
+        obs.push_back(pairs[b++].second);
+      }
       if (slot >= v_.nnz) Fatal("internal error: the inverted index does not match the CSR of Z^T Z");
       ptr[M + slot + 1] = (int)obs.size();
       ++slot;
@@ -362,6 +459,19 @@ GroupedLaplace::GroupedLaplace(GroupedRE* re, const std::vector<std::vector<int>
   upload(d_c1_, c1);
   upload(d_long_dst_, long_dst);
   upload(d_long_cptr_, long_cptr);
+  if (wt_) {
+    std::vector<double> tab((size_t)K * n);
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < n; ++i) tab[(size_t)k * n + i] = zw(k, i);
+    auto upload_d = [&](DevBuf<double>& dst, const std::vector<double>& src) {
+      dst.alloc(std::max<size_t>(src.size(), 1));
+      HIP_CHECK(hipMemcpyAsync(dst.get(), src.data(), sizeof(double) * src.size(), hipMemcpyHostToDevice, s_));
+    };
+    upload_d(d_zw_, tab);
+    upload_d(d_seg_w1_, w1);
+    upload_d(d_seg_w2_, w2);
+    HIP_CHECK(hipStreamSynchronize(s_));   // tab goes out of scope
+  }
   d_chunk_P_.alloc(std::max(n_chunks_, 1));
   for (auto* b : {&d_y_, &d_d1_, &d_W_, &d_dW_, &d_dwq_}) b->alloc(n);
   for (auto* b : {&d_mode_, &d_mode_new_, &d_mode_prev_, &d_upd_, &d_rhs_, &d_ztd1_, &d_D_, &d_dmll_, &d_vS_, &d_dis_})
@@ -472,10 +582,20 @@ void GroupedLaplace::Assemble(const double* w, double* out, bool diag_only) {
   const int ndst = diag_only ? v_.M : v_.M + v_.nnz;
   const int nchunks = diag_only ? n_chunks_diag_ : n_chunks_;
   const int nlong = diag_only ? n_long_diag_ : n_long_;
-  glp_seg_short_kernel<<<blocks_of(ndst), 256, 0, s_>>>(ndst, d_seg_ptr_.get(), d_seg_obs_.get(), w, out);
+  if (wt_) {   // diag_only: Z^T w (Z's values), else the destinations of Z^T diag(w) Z (their products)
+    const double* sw = diag_only ? d_seg_w1_.get() : d_seg_w2_.get();
+    glp_seg_short_kernel<true><<<blocks_of(ndst), 256, 0, s_>>>(ndst, d_seg_ptr_.get(), d_seg_obs_.get(), sw, w, out);
+    if (nchunks > 0)
+      glp_seg_chunk_kernel<true><<<(nchunks + 3) / 4, 256, 0, s_>>>(nchunks, d_c0_.get(), d_c1_.get(),
+                                                                    d_seg_obs_.get(), sw, w, d_chunk_P_.get());
+  } else {
+    glp_seg_short_kernel<false><<<blocks_of(ndst), 256, 0, s_>>>(ndst, d_seg_ptr_.get(), d_seg_obs_.get(), nullptr, w,
+                                                                 out);
+    if (nchunks > 0)
+      glp_seg_chunk_kernel<false><<<(nchunks + 3) / 4, 256, 0, s_>>>(nchunks, d_c0_.get(), d_c1_.get(),
+                                                                     d_seg_obs_.get(), nullptr, w, d_chunk_P_.get());
+  }
   if (nchunks > 0) {
-    glp_seg_chunk_kernel<<<(nchunks + 3) / 4, 256, 0, s_>>>(nchunks, d_c0_.get(), d_c1_.get(), d_seg_obs_.get(), w,
-                                                            d_chunk_P_.get());
     glp_seg_long_kernel<<<blocks_of(nlong), 256, 0, s_>>>(nlong, d_long_dst_.get(), d_long_cptr_.get(),
                                                           d_chunk_P_.get(), out);
   }
@@ -494,8 +614,8 @@ EffArgs make_eff(const GroupedRE::View& v, const double* sigma2) {
 
 double GroupedLaplace::Objective(const double* mode, double aux, const double* sigi) {
   const int n = v_.n, K = v_.K;
-  glp_obs_kernel<false><<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr, mode,
-                                             lik_, aux, nullptr, nullptr, nullptr, d_partial_.get());
+  launch_glp_obs(nb_, false, d_zw_.get(), n, K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr, mode,
+                 lik_, aux, nullptr, nullptr, nullptr, d_partial_.get(), s_);
   glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get());
   EffArgs a{};
   a.K = K;
@@ -510,9 +630,8 @@ double GroupedLaplace::Objective(const double* mode, double aux, const double* s
 }
 
 void GroupedLaplace::Deriv(const double* mode, double aux, bool want_dw) {
-  glp_obs_kernel<true><<<nb_, 256, 0, s_>>>(v_.n, v_.K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr,
-                                            mode, lik_, aux, d_d1_.get(), d_W_.get(), want_dw ? d_dW_.get() : nullptr,
-                                            d_partial_.get());
+  launch_glp_obs(nb_, true, d_zw_.get(), v_.n, v_.K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr,
+                 mode, lik_, aux, d_d1_.get(), d_W_.get(), want_dw ? d_dW_.get() : nullptr, d_partial_.get(), s_);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -648,8 +767,8 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
 
   // ---- gradient (:3634-3740 / 3791-3853)
   if (nb_aux) {   // dd1/dlog r, dW/dlog r and the explicit sum at the mode (:10872-10885, 10527-10538)
-    glp_nb_aux_kernel<<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr,
-                                           d_mode_.get(), aux, d_dd1a_.get(), d_dWa_.get(), d_partial_.get());
+    launch_glp_nb_aux(nb_, d_zw_.get(), n, K, d_glev_.get(), d_y_.get(), has_off_ ? d_off_.get() : nullptr,
+                      d_mode_.get(), aux, d_dd1a_.get(), d_dWa_.get(), d_partial_.get(), s_);
     glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get() + kRedAuxSum);
     HIP_CHECK(hipGetLastError());
   }
@@ -670,7 +789,7 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
     const double* U = re_->slq_solution();
     const double* PI = re_->probes_pinv();
     const double* DI = re_->probes_dinv_upper();
-    glp_row_trace_kernel<<<blocks_of(n), 256, 0, s_>>>(n, K, t, d_glev_.get(), U, PI, d_dW_.get(), d_dwq_.get());
+    launch_glp_row_trace(d_zw_.get(), n, K, t, d_glev_.get(), U, PI, d_dW_.get(), d_dwq_.get(), s_);
     HIP_CHECK(hipGetLastError());
     if (lik_ == kLikGamma && want_aux_grad) {
       // dW/dlog shape = W: tr(A^-1 Z^T W Z) by the probes, its SSOR control variate with the lower triangle of
@@ -729,12 +848,12 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
   } else {
     const double* Ainv = K > 1 ? re_->DenseInverse() : nullptr;
     if (nb_aux) {   // one more fused partial: sum_i (dW/dlog r)_i q_i
-      glp_q_kernel<true><<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(),
-                                              d_dW_.get(), d_dWa_.get(), d_dwq_.get(), d_partial_.get());
+      launch_glp_q(nb_, true, d_zw_.get(), n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(),
+                   d_dW_.get(), d_dWa_.get(), d_dwq_.get(), d_partial_.get(), s_);
       glp_finish_kernel<<<1, 256, 0, s_>>>(nb_, d_partial_.get() + (size_t)K * nb_, d_red_.get() + kRedAuxTrace);
     } else {
-      glp_q_kernel<false><<<nb_, 256, 0, s_>>>(n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(),
-                                               d_dW_.get(), nullptr, d_dwq_.get(), d_partial_.get());
+      launch_glp_q(nb_, false, d_zw_.get(), n, K, d_glev_.get(), Ainv, re_->dense_ld(), d_D_.get(), d_W_.get(),
+                   d_dW_.get(), nullptr, d_dwq_.get(), d_partial_.get(), s_);
     }
     glp_finish_kernel<<<K, 256, 0, s_>>>(nb_, d_partial_.get(), d_red_.get());   // sum_i W_i q_ij
     HIP_CHECK(hipGetLastError());
@@ -754,8 +873,8 @@ GroupedLaplaceResult GroupedLaplace::Eval(const double* sigma2, double aux, cons
   }
   if (grad_f != nullptr || keep_gradf_) {
     d_gradf_.alloc(n);
-    glp_grad_f_kernel<<<blocks_of(n), 256, 0, s_>>>(n, K, d_glev_.get(), d_d1_.get(), d_dwq_.get(), d_W_.get(),
-                                                    d_vS_.get(), d_gradf_.get());
+    launch_glp_grad_f(d_zw_.get(), n, K, d_glev_.get(), d_d1_.get(), d_dwq_.get(), d_W_.get(), d_vS_.get(),
+                      d_gradf_.get(), s_);
     HIP_CHECK(hipGetLastError());
     if (grad_f != nullptr)
       HIP_CHECK(hipMemcpyAsync(grad_f, d_gradf_.get(), sizeof(double) * n, hipMemcpyDeviceToHost, s_));
@@ -800,9 +919,9 @@ void GroupedLaplace::GetMode(double* b) {
   HIP_CHECK(hipStreamSynchronize(s_));
 }
 
-void GroupedLaplace::PredVar(int np, const std::vector<int>& idx, double* out) {
+void GroupedLaplace::PredVar(int np, const std::vector<int>& idx, double* out, const double* wt) {
   if (!evaluated_) Fatal("predictive variances need an evaluation of the Laplace approximation first");
-  re_->PredCov(np, idx, false, out, v_.K == 1 ? d_D_.get() : nullptr);
+  re_->PredCov(np, idx, false, out, v_.K == 1 ? d_D_.get() : nullptr, wt);
 }
 
 void GroupedLaplace::GetZtWZ(double* diag, double* vals) {
@@ -819,8 +938,7 @@ int test_glp_blocks(int n) { return obs_blocks(n); }
 void test_glp_obs(int n, int K, const int* glev, const double* y, const double* F, const double* b, int lik, double aux,
                   bool deriv, double* d1, double* W, double* dW, double* partial, double* ll, hipStream_t s) {
   const int nb = obs_blocks(n);
-  if (deriv) glp_obs_kernel<true><<<nb, 256, 0, s>>>(n, K, glev, y, F, b, lik, aux, d1, W, dW, partial);
-  else glp_obs_kernel<false><<<nb, 256, 0, s>>>(n, K, glev, y, F, b, lik, aux, nullptr, nullptr, nullptr, partial);
+  launch_glp_obs(nb, deriv, nullptr, n, K, glev, y, F, b, lik, aux, d1, W, dW, partial, s);
   glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial, ll);
   HIP_CHECK(hipGetLastError());
 }
@@ -828,34 +946,31 @@ void test_glp_obs(int n, int K, const int* glev, const double* y, const double* 
 void test_glp_nb_aux(int n, int K, const int* glev, const double* y, const double* F, const double* b, double aux,
                      double* dd1a, double* dWa, double* partial, double* sum, hipStream_t s) {
   const int nb = obs_blocks(n);
-  glp_nb_aux_kernel<<<nb, 256, 0, s>>>(n, K, glev, y, F, b, aux, dd1a, dWa, partial);
+  launch_glp_nb_aux(nb, nullptr, n, K, glev, y, F, b, aux, dd1a, dWa, partial, s);
   glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial, sum);
   HIP_CHECK(hipGetLastError());
 }
 
 // ---- test launchers (grouped_test.h): the gradient's launches of Eval with its grids
-void test_glp_q(int n, int K, const int* glev, const double* Ainv, int ld, const double* D, const double* W,
-                const double* dW, const double* Wa, bool aux, double* dwq, double* partial, double* out, hipStream_t s) {
+void test_glp_q(int n, int K, const int* glev, const double* zw, const double* Ainv, int ld, const double* D,
+                const double* W, const double* dW, const double* Wa, bool aux, double* dwq, double* partial, double* out,
+                hipStream_t s) {
   const int nb = obs_blocks(n);
-  if (aux) {
-    glp_q_kernel<true><<<nb, 256, 0, s>>>(n, K, glev, Ainv, ld, D, W, dW, Wa, dwq, partial);
-    glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial + (size_t)K * nb, out + K);
-  } else {
-    glp_q_kernel<false><<<nb, 256, 0, s>>>(n, K, glev, Ainv, ld, D, W, dW, nullptr, dwq, partial);
-  }
+  launch_glp_q(nb, aux, zw, n, K, glev, Ainv, ld, D, W, dW, Wa, dwq, partial, s);
+  if (aux) glp_finish_kernel<<<1, 256, 0, s>>>(nb, partial + (size_t)K * nb, out + K);
   glp_finish_kernel<<<K, 256, 0, s>>>(nb, partial, out);
   HIP_CHECK(hipGetLastError());
 }
 
-void test_glp_row_trace(int n, int K, int t, const int* glev, const double* U, const double* V, const double* dW,
-                        double* dwq, hipStream_t s) {
-  glp_row_trace_kernel<<<blocks_of(n), 256, 0, s>>>(n, K, t, glev, U, V, dW, dwq);
+void test_glp_row_trace(int n, int K, int t, const int* glev, const double* zw, const double* U, const double* V,
+                        const double* dW, double* dwq, hipStream_t s) {
+  launch_glp_row_trace(zw, n, K, t, glev, U, V, dW, dwq, s);
   HIP_CHECK(hipGetLastError());
 }
 
-void test_glp_grad_f(int n, int K, const int* glev, const double* d1, const double* dwq, const double* W,
-                     const double* v, double* out, hipStream_t s) {
-  glp_grad_f_kernel<<<blocks_of(n), 256, 0, s>>>(n, K, glev, d1, dwq, W, v, out);
+void test_glp_grad_f(int n, int K, const int* glev, const double* zw, const double* d1, const double* dwq,
+                     const double* W, const double* v, double* out, hipStream_t s) {
+  launch_glp_grad_f(zw, n, K, glev, d1, dwq, W, v, out, s);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -893,6 +1008,7 @@ void GroupedTestAccess::Assemble(GroupedLaplace& g, const double* w, double* out
   g.Assemble(w, out, diag_only);
 }
 const int* GroupedTestAccess::Glev(const GroupedLaplace& g) { return g.d_glev_.get(); }
+const double* GroupedTestAccess::Zw(const GroupedLaplace& g) { return g.d_zw_.get(); }
 void GroupedTestAccess::SegCounts(const GroupedLaplace& g, int out[4]) {
   out[0] = g.n_long_diag_;
   out[1] = g.n_chunks_diag_;

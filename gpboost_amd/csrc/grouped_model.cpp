@@ -33,12 +33,59 @@ std::vector<std::vector<int>> parse_group_levels(int n, int K, const char* re_gr
 }
 
 GroupedModel::GroupedModel(int n, const std::vector<std::vector<int>>& levels, const std::string& mim, int seed,
-                           std::vector<std::unordered_map<std::string, int>> label_index, const std::string& likelihood)
-    : n_(n), mim_(mim), likelihood_(likelihood), levels_(levels), label_index_(std::move(label_index)) {
+                           std::vector<std::unordered_map<std::string, int>> label_index, const std::string& likelihood,
+                           const GroupedSlopes& slopes)
+    : n_(n), mim_(mim), likelihood_(likelihood), label_index_(std::move(label_index)) {
   (void)seed;   // grouped models draw no random numbers at construction (probes use seed_rand_vec_trace)
   if (n <= 0) Fatal("num_data must be > 0");
-  const int K = (int)levels.size();
-  if (K < 1) Fatal("num_re_group must be > 0");
+  G_ = (int)levels.size();
+  if (G_ < 1) Fatal("num_re_group must be > 0");
+  // components (re_model_template.h:6833-6872): the intercepts, the slopes, then the dropped intercept removed
+  for (int k = 0; k < G_; ++k) {
+    comp_group_.push_back(k);
+    comp_slope_.push_back(-1);
+  }
+  if (slopes.R > 0) {
+    if (slopes.data == nullptr || slopes.ind == nullptr)
+      Fatal("group_rand_coef_data and ind_effect_group_rand_coef must be given together");
+    std::vector<bool> has_slope(G_, false);
+    for (int r = 0; r < slopes.R; ++r) {
+      if (slopes.ind[r] < 1 || slopes.ind[r] > G_)   // :252-254
+        Fatal("ind_effect_group_rand_coef[%d] = %d is not in 1..%d (the grouping variables, counted from 1)", r,
+              slopes.ind[r], G_);
+      has_slope[slopes.ind[r] - 1] = true;
+      const double* col = slopes.data + (size_t)r * n;
+      for (int i = 0; i < n; ++i)
+        if (std::isnan(col[i]) || std::isinf(col[i])) Fatal("NaN or Inf in group_rand_coef_data");
+      slope_data_.emplace_back(col, col + n);
+      comp_group_.push_back(slopes.ind[r] - 1);
+      comp_slope_.push_back(r);
+    }
+    int dropped = -1;
+    for (int k = 0; slopes.drop != nullptr && k < G_; ++k) {
+      if (!(slopes.drop[k] > 0)) continue;
+      if (!has_slope[k])   // the intent of :258-265
+        Fatal("Cannot drop intercept random effect number %d (drop_intercept_group_rand_effect) as this random effect "
+              "has no corresponding random coefficients", k + 1);
+      if (dropped >= 0)
+        Fatal("drop_intercept_group_rand_effect: dropping more than one intercept is not supported by gpboost_amd (the "
+              "reference removes other components than the documented ones then)");
+      dropped = k;
+    }
+    if (dropped >= 0) {
+      comp_group_.erase(comp_group_.begin() + dropped);
+      comp_slope_.erase(comp_slope_.begin() + dropped);
+    }
+    if (comp_group_.size() == 1)
+      Fatal("group_rand_coef_data: a model whose only random effect is a random slope (one grouping variable, one "
+            "slope, its intercept dropped) is not supported by gpboost_amd");
+  }
+  const int K = (int)comp_group_.size();
+  std::vector<const double*> weights;
+  for (int c = 0; c < K; ++c) {
+    levels_.push_back(levels[comp_group_[c]]);
+    if (has_slopes()) weights.push_back(comp_slope_[c] >= 0 ? slope_data_[comp_slope_[c]].data() : nullptr);
+  }
   lik_ = parse_likelihood(likelihood_);
   if (lik_ == kLikNegBinomial) likelihood_ = "negative_binomial";   // the aliases' name (ParseLikelihoodAlias)
   if (mim_ == "default") mim_ = K > 1 ? "iterative" : "cholesky";
@@ -59,9 +106,9 @@ GroupedModel::GroupedModel(int n, const std::vector<std::vector<int>>& levels, c
   }
   UseDevice();
   HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-  re_.reset(new GroupedRE(n, levels, stream_));
+  re_.reset(new GroupedRE(n, levels_, stream_, weights));
   if (lik_ != kLikGaussian) {
-    lap_.reset(new GroupedLaplace(re_.get(), levels, lik_));
+    lap_.reset(new GroupedLaplace(re_.get(), levels_, lik_, weights));
     if (lik_ == kLikGamma || lik_ == kLikNegBinomial) {
       aux_pars_ = {1.};   // aux_pars_ = {1.} until set or estimated (likelihoods.h:181-192)
       init_aux_pars_ = {-1.};
@@ -78,6 +125,9 @@ GroupedModel::~GroupedModel() {
 void GroupedModel::UseDevice() const { HIP_CHECK(hipSetDevice(device_)); }
 
 void GroupedModel::AttachGP(int d, const double* coords_colmajor, int cov_type, int seed) {
+  if (has_slopes())
+    Fatal("group_rand_coef_data together with gp_coords (a Gaussian process beside grouped random effects) is not "
+          "supported by gpboost_amd");
   if (laplace())
     Fatal("a Gaussian process beside grouped random effects (gp_coords with group_data) is not supported for "
           "likelihood '%s' by gpboost_amd", likelihood_.c_str());
@@ -264,9 +314,9 @@ void GroupedModel::SetOptimSettings(const double* init_cov_pars, double lr, int 
                                     const char* optimizer, int m_lbfgs) {
   if (optimizer != nullptr && optimizer[0] != '\0') {
     const std::string o(optimizer);
-    if (laplace() && o != "lbfgs")
+    if (laplace() && o != "lbfgs" && o != "gradient_descent")
       Fatal("Optimizer option '%s' is not supported for covariance parameters of grouped random effects with "
-            "likelihood '%s' by gpboost_amd (supported: lbfgs)", optimizer, likelihood_.c_str());
+            "likelihood '%s' by gpboost_amd (supported: lbfgs, gradient_descent)", optimizer, likelihood_.c_str());
     if (o != "lbfgs" && o != "nelder_mead" && !is_internal_optimizer(o))
       Fatal("Optimizer option '%s' is not supported for covariance parameters by gpboost_amd (supported: lbfgs, "
             "gradient_descent, fisher_scoring, nelder_mead)", optimizer);
@@ -514,7 +564,7 @@ void GroupedModel::PredictTrainingDataRandomEffects(const double* cov_pars, cons
     std::vector<double> b(re_->M());
     lap_->GetMode(b.data());
     int off = 0;
-    for (int k = 0; k < K; ++k) {
+    for (int k = 0; k < K; ++k) {   // a slope's block holds the slope effect itself (re_model_template.h:4266-4280)
       for (int i = 0; i < n_; ++i) out[(size_t)k * n_ + i] = b[off + levels_[k][i]];
       off += re_->levels_per_effect()[k];
     }
@@ -533,10 +583,58 @@ void GroupedModel::PredictTrainingDataRandomEffects(const double* cov_pars, cons
   }
 }
 
+void GroupedModel::PredComponents(int n_pred, const char* re_group_data_pred, const double* slope_data_pred,
+                                  std::vector<int>& idx, std::vector<double>& wt,
+                                  std::vector<std::vector<int>>* fresh) const {
+  const int K = re_->K();
+  if ((int)label_index_.size() != G_) Fatal("the model has no label index (created without re_group_data)");
+  if (has_slopes() && slope_data_pred == nullptr)   // re_model_template.h:3086-3089
+    Fatal("No random coefficient data 'group_rand_coef_data_pred' has been provided for making predictions with a "
+          "model that has grouped random coefficients (group_rand_coef_data)");
+  if (!has_slopes() && slope_data_pred != nullptr)
+    Fatal("group_rand_coef_data_pred is given but the model has no grouped random coefficients");
+  if (has_slopes())
+    for (size_t e = 0; e < (size_t)n_pred * num_slopes(); ++e)
+      if (std::isnan(slope_data_pred[e]) || std::isinf(slope_data_pred[e]))
+        Fatal("NaN or Inf in group_rand_coef_data_pred");
+  // labels column-major, as re_group_data (re_model_template.h:3081-3085): seen levels to their level, new labels
+  // to -1 - id; the id numbers the distinct new labels of a grouping variable (the same-new-label covariance terms
+  // compare these ids, not the strings)
+  std::vector<std::vector<int>> glev(G_, std::vector<int>(n_pred));
+  const char* p = re_group_data_pred;
+  for (int g = 0; g < G_; ++g) {
+    std::unordered_map<std::string, int> fresh_ids;
+    for (int i = 0; i < n_pred; ++i) {
+      std::string label(p);
+      p += label.size() + 1;
+      auto it = label_index_[g].find(label);
+      if (it != label_index_[g].end()) glev[g][i] = it->second;
+      else glev[g][i] = -1 - fresh_ids.emplace(std::move(label), (int)fresh_ids.size()).first->second;
+    }
+  }
+  idx.assign((size_t)n_pred * K, -1);
+  wt.clear();
+  if (has_slopes()) wt.assign((size_t)n_pred * K, 1.);
+  if (fresh) fresh->assign(K, std::vector<int>(n_pred, -1));
+  int off = 0;
+  for (int c = 0; c < K; ++c) {
+    const int g = comp_group_[c];
+    for (int i = 0; i < n_pred; ++i) {
+      if (glev[g][i] >= 0) idx[(size_t)i * K + c] = off + glev[g][i];
+      else if (fresh) (*fresh)[c][i] = -1 - glev[g][i];
+      if (comp_slope_[c] >= 0) wt[(size_t)i * K + c] = slope_data_pred[(size_t)comp_slope_[c] * n_pred + i];
+    }
+    off += re_->levels_per_effect()[c];
+  }
+}
+
 void GroupedModel::Predict(const double* y, int n_pred, const char* re_group_data_pred, const double* gp_coords_pred,
                            const double* cov_pars, bool predict_cov_mat, bool predict_var, bool predict_response,
-                           const double* fixed_effects, const double* fixed_effects_pred, double* out) {
+                           const double* fixed_effects, const double* fixed_effects_pred, double* out,
+                           const double* slope_data_pred) {
   if (has_gp()) {
+    if (slope_data_pred != nullptr)
+      Fatal("group_rand_coef_data_pred is given but the model has no grouped random coefficients");
     PredictCombined(y, n_pred, re_group_data_pred, gp_coords_pred, cov_pars, predict_cov_mat, predict_var,
                     predict_response, fixed_effects, fixed_effects_pred, out);
     return;
@@ -547,7 +645,7 @@ void GroupedModel::Predict(const double* y, int n_pred, const char* re_group_dat
       Fatal("predictive covariance matrices (predict_cov_mat) are not supported for likelihood '%s' with grouped "
             "random effects by gpboost_amd (use predict_var)", likelihood_.c_str());
     PredictLaplace(y, n_pred, re_group_data_pred, cov_pars, predict_var, predict_response, fixed_effects,
-                   fixed_effects_pred, out);
+                   fixed_effects_pred, out, slope_data_pred);
     return;
   }
   if ((predict_cov_mat || predict_var) && iterative())
@@ -556,35 +654,21 @@ void GroupedModel::Predict(const double* y, int n_pred, const char* re_group_dat
   if (n_pred <= 0) Fatal("num_data_pred must be > 0");
   if (re_group_data_pred == nullptr) Fatal("re_group_data_pred must be provided for grouped random effects");
   const int K = re_->K();
-  if ((int)label_index_.size() != K) Fatal("the model has no label index (created without re_group_data)");
   const bool want_unc = predict_cov_mat || predict_var;
   if (predict_cov_mat && n_pred > 40000)
     Fatal("predictive covariance matrices are limited to 40000 prediction points by gpboost_amd");
+  std::vector<int> idx;
+  std::vector<double> wt;
+  std::vector<std::vector<int>> fresh;
+  PredComponents(n_pred, re_group_data_pred, slope_data_pred, idx, wt, want_unc ? &fresh : nullptr);
+  const bool wtd = !wt.empty();
   const std::vector<double> b = Blup(cov_pars, y, fixed_effects, nullptr);
-  // labels column-major, as re_group_data (re_model_template.h:3081-3085): seen levels to their global
-  // index, new labels to -1; fresh[k][i] numbers the distinct new labels (the same-new-label covariance terms
-  // compare these ids, not the strings)
-  std::vector<int> idx((size_t)n_pred * K, -1);
-  std::vector<std::vector<int>> fresh(want_unc ? K : 0);
   std::vector<double> mu(n_pred, 0.);
-  const char* p = re_group_data_pred;
-  int off = 0;
-  for (int k = 0; k < K; ++k) {
-    std::unordered_map<std::string, int> fresh_ids;
-    if (want_unc) fresh[k].assign(n_pred, -1);
+  for (int k = 0; k < K; ++k)
     for (int i = 0; i < n_pred; ++i) {
-      std::string label(p);
-      p += label.size() + 1;
-      auto it = label_index_[k].find(label);
-      if (it != label_index_[k].end()) {
-        mu[i] += b[off + it->second];   // a new level contributes 0
-        idx[(size_t)i * K + k] = off + it->second;
-      } else if (want_unc) {
-        fresh[k][i] = fresh_ids.emplace(std::move(label), (int)fresh_ids.size()).first->second;
-      }
+      const int a = idx[(size_t)i * K + k];
+      if (a >= 0) mu[i] += wtd ? wt[(size_t)i * K + k] * b[a] : b[a];   // a new level contributes 0
     }
-    off += re_->levels_per_effect()[k];
-  }
   for (int i = 0; i < n_pred; ++i) out[i] = mu[i] + (fixed_effects_pred ? fixed_effects_pred[i] : 0.);
   if (!want_unc) return;
   std::vector<double> cp;
@@ -594,20 +678,21 @@ void GroupedModel::Predict(const double* y, int n_pred, const char* re_group_dat
   for (int k = 0; k < K; ++k) tau[k] = cp[1 + k] / cp[0];
   const double nug = predict_response ? 1. : 0., s2 = cp[0];
   double* o = out + n_pred;
-  re_->PredCov(n_pred, idx, predict_cov_mat, o);
+  re_->PredCov(n_pred, idx, predict_cov_mat, o, nullptr, wtd ? wt.data() : nullptr);
   if (predict_cov_mat) {
     for (int q = 0; q < n_pred; ++q)
       for (int i = 0; i < n_pred; ++i) {
         double v = o[(size_t)q * n_pred + i] + (i == q ? nug : 0.);
         for (int k = 0; k < K; ++k)
-          if (fresh[k][i] >= 0 && fresh[k][i] == fresh[k][q]) v += tau[k];
+          if (fresh[k][i] >= 0 && fresh[k][i] == fresh[k][q])
+            v += wtd ? tau[k] * wt[(size_t)i * K + k] * wt[(size_t)q * K + k] : tau[k];
         o[(size_t)q * n_pred + i] = v * s2;
       }
   } else {
     for (int i = 0; i < n_pred; ++i) {
       double v = o[i] + nug;
       for (int k = 0; k < K; ++k)
-        if (idx[(size_t)i * K + k] < 0) v += tau[k];
+        if (idx[(size_t)i * K + k] < 0) v += wtd ? tau[k] * wt[(size_t)i * K + k] * wt[(size_t)i * K + k] : tau[k];
       o[i] = v * s2;
     }
   }
@@ -912,6 +997,13 @@ void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effec
     }
     return;
   }
+  if (isettings_.optimizer == "gradient_descent") {
+    if (with_coef)
+      Fatal("optimizer_cov = 'gradient_descent' together with linear regression covariates is not supported for "
+            "likelihood '%s' with grouped random effects by gpboost_amd (use 'lbfgs')", likelihood_.c_str());
+    GradientDescentLaplace(s2, with_aux);
+    return;
+  }
   std::vector<double> x(K);
   for (int k = 0; k < K; ++k) x[k] = std::log(s2[k]);
   x.insert(x.end(), beta_scaled.begin(), beta_scaled.end());
@@ -943,6 +1035,101 @@ void GroupedModel::OptimCovParLaplace(const double* y, const double* fixed_effec
   }
   cov_pars_initialized_ = true;
   last_nll_ = fx;
+  last_cov_pars_ = cov_pars_orig_;
+}
+
+void GroupedModel::GradientDescentLaplace(const std::vector<double>& start, bool with_aux) {
+  // OptimLinRegrCoefCovPar's loop without profiling (re_model_template.h:1290-1549), as REModelAMD runs it for the GP
+  // Laplace models (optim.cpp): the variances and the auxiliary parameter on the log scale with their own learning
+  // rates (AvoidTooLargeLearningRatesCovAuxPars :7539-7560), separate Armijo conditions for both blocks
+  // (UpdateCovAuxPars :7850-7990), Nesterov momentum over all of them (ApplyMomentumStep), the Laplace mode continued
+  // across evaluations and put back to its previous value after a rejected trial.
+  const int nc = re_->K(), na = with_aux ? 1 : 0, P = nc + na;
+  std::vector<double> pars = start;
+  if (with_aux) pars.push_back(aux_pars_[0]);
+  const double kMaxLog = std::log(100.);   // MAX_GRADIENT_UPDATE_LOG_SCALE_
+  double lr_cov = isettings_.lr < 0. ? 0.1 : isettings_.lr, lr_aux = lr_cov;   // SetInitialValueLRCov :7505-7521
+  const bool nest = isettings_.nesterov;
+  if (nest && isettings_.schedule != 0) Fatal("NesterovSchedule: version = %d is not supported ", isettings_.schedule);
+  auto sched = [&](int it, double acc) { return it < isettings_.momentum_offset ? 0. : acc; };
+  auto eval_nll = [&](const std::vector<double>& v) {
+    if (with_aux) SetAuxPars(&v[nc]);
+    return EvalLaplace(v.data(), false, GroupedLaplace::Start::kWarm, /*fatal_on_nan=*/false).nll;
+  };
+  lap_->ClearModePrevious();
+  double nll = eval_nll(pars);
+  if (!std::isfinite(nll)) Fatal("NaN or Inf occurred in initial approximate negative marginal log-likelihood");
+  std::vector<double> after = pars, after_lag1 = pars;
+  num_it_ = isettings_.max_iter;
+  for (int it = 0; it < isettings_.max_iter; ++it) {
+    num_iter_ = it;
+    const double nll_lag1 = nll;
+    const std::vector<double> pars_lag1 = pars;
+    if (with_aux) SetAuxPars(&pars[nc]);
+    std::vector<double> g = EvalLaplace(pars.data(), true, GroupedLaplace::Start::kKeep, false).grad;   // at the mode
+    if ((int)g.size() < P) Fatal("internal error: the Laplace gradient has %d entries", (int)g.size());
+    g.resize(P);
+    double mc = 0., ma = 0.;
+    for (int k = 0; k < nc; ++k) mc = std::max(mc, std::fabs(g[k]));
+    for (int k = nc; k < P; ++k) ma = std::max(ma, std::fabs(g[k]));
+    if (mc > 0. && lr_cov > kMaxLog / mc) lr_cov = kMaxLog / mc;
+    if (na && ma > 0. && lr_aux > kMaxLog / ma) lr_aux = kMaxLog / ma;
+    double dd_c = 0., dd_a = 0., md_c = 0., md_a = 0.;
+    for (int k = 0; k < nc; ++k) dd_c -= g[k] * g[k];
+    for (int k = nc; k < P; ++k) dd_a -= g[k] * g[k];
+    if (nest) {
+      for (int k = 0; k < nc; ++k) md_c += g[k] * (std::log(pars[k]) - std::log(after[k]));
+      for (int k = nc; k < P; ++k) md_a += g[k] * (std::log(pars[k]) - std::log(after[k]));
+    }
+    double lc = lr_cov, la = lr_aux, acc = isettings_.acc_rate;
+    bool halving = false;
+    std::vector<double> np(P);
+    for (int ih = 0; ih < 30; ++ih) {   // MAX_NUMBER_LR_SHRINKAGE_STEPS_DEFAULT_
+      for (int k = 0; k < P; ++k) np[k] = std::exp(std::log(pars[k]) - (k < nc ? lc : la) * g[k]);
+      const double mu = nest ? sched(it, acc) : 0.;
+      if (nest) {
+        after = np;
+        for (int k = 0; k < P; ++k) np[k] = std::exp((mu + 1.) * std::log(after[k]) - mu * std::log(after_lag1[k]));
+      }
+      nll = eval_nll(np);
+      bool ok = nll <= nll_lag1 + 1e-4 * lc * dd_c + 1e-4 * mu * md_c;
+      if (na) ok = ok && nll <= nll_lag1 + 1e-4 * la * dd_a + 1e-4 * mu * md_a;
+      if (ok) break;
+      halving = true;
+      lc *= 0.5;
+      la *= 0.5;
+      acc *= 0.5;
+      lap_->ResetModeToPrevious();
+    }
+    if (halving) {   // permanently decreased for gradient descent (:7978-7979)
+      lr_cov = lc;
+      lr_aux = la;
+    }
+    if (nest) after_lag1 = after;
+    pars = np;
+    bool bad = !std::isfinite(nll);
+    for (double v : pars) bad = bad || !std::isfinite(v);
+    if (bad) Fatal("NaN or Inf occurred in covariance parameter optimization using 'gradient_descent'");
+    bool conv;
+    if (isettings_.crit_params) {
+      double dn = 0., ln = 0.;
+      for (int k = 0; k < P; ++k) {
+        dn += (pars[k] - pars_lag1[k]) * (pars[k] - pars_lag1[k]);
+        ln += pars_lag1[k] * pars_lag1[k];
+      }
+      conv = std::sqrt(dn) <= isettings_.delta * std::sqrt(ln);
+    } else {
+      conv = (nll_lag1 - nll) <= isettings_.delta * std::max(std::fabs(nll_lag1), 1.);
+    }
+    if (conv) {
+      num_it_ = it + 1;
+      break;
+    }
+  }
+  cov_pars_orig_.assign(pars.begin(), pars.begin() + nc);
+  if (with_aux) aux_pars_[0] = pars[nc];
+  cov_pars_initialized_ = true;
+  last_nll_ = nll;
   last_cov_pars_ = cov_pars_orig_;
 }
 
@@ -978,7 +1165,7 @@ void GroupedModel::GetLaplaceInfo(int* dims, int* rowptr, int* col, double* diag
 
 void GroupedModel::PredictLaplace(const double* y, int n_pred, const char* re_group_data_pred, const double* cov_pars,
                                   bool predict_var, bool predict_response, const double* fixed_effects,
-                                  const double* fixed_effects_pred, double* out) {
+                                  const double* fixed_effects_pred, double* out, const double* slope_data_pred) {
   // PredictLaplaceApproxGroupedRE (likelihoods.h:5696-5953) / ...OnlyOneGroupedRECalculationsOnREScale (:5973-6032):
   // latent mean = sum_k mode_k[level] (0 for a level not in the training data); latent variance = sum_k sigma_k^2
   // [level not seen] + e_p^T A^-1 e_p, e_p the indicator of p's seen levels (the posterior covariance of the
@@ -986,29 +1173,22 @@ void GroupedModel::PredictLaplace(const double* y, int n_pred, const char* re_gr
   if (n_pred <= 0) Fatal("num_data_pred must be > 0");
   if (re_group_data_pred == nullptr) Fatal("re_group_data_pred must be provided for grouped random effects");
   const int K = re_->K();
-  if ((int)label_index_.size() != K) Fatal("the model has no label index (created without re_group_data)");
+  std::vector<int> idx;
+  std::vector<double> wt;
+  PredComponents(n_pred, re_group_data_pred, slope_data_pred, idx, wt, nullptr);
+  const bool wtd = !wt.empty();
   const std::vector<double> cp = LaplaceCovPars(cov_pars);
   if (y != nullptr || fixed_effects != nullptr) SetResponseAndOffset(y, fixed_effects);
   if (!y_set_) Fatal("Response variable data is not provided and has not been set before");
   EvalLaplace(cp.data(), false, GroupedLaplace::Start::kZero, true);
   std::vector<double> b(re_->M());
   lap_->GetMode(b.data());
-  std::vector<int> idx((size_t)n_pred * K, -1);
   std::vector<double> mu(n_pred, 0.);
-  const char* p = re_group_data_pred;
-  int off = 0;
-  for (int k = 0; k < K; ++k) {
+  for (int k = 0; k < K; ++k)
     for (int i = 0; i < n_pred; ++i) {
-      std::string label(p);
-      p += label.size() + 1;
-      auto it = label_index_[k].find(label);
-      if (it != label_index_[k].end()) {
-        mu[i] += b[off + it->second];
-        idx[(size_t)i * K + k] = off + it->second;
-      }
+      const int a = idx[(size_t)i * K + k];
+      if (a >= 0) mu[i] += wtd ? wt[(size_t)i * K + k] * b[a] : b[a];
     }
-    off += re_->levels_per_effect()[k];
-  }
   for (int i = 0; i < n_pred; ++i) mu[i] += fixed_effects_pred ? fixed_effects_pred[i] : 0.;
   const bool want_var = predict_var || predict_response;
   if (want_var && iterative())
@@ -1017,10 +1197,10 @@ void GroupedModel::PredictLaplace(const double* y, int n_pred, const char* re_gr
           "gpboost_amd (use 'cholesky' or predict_response = false)");
   std::vector<double> var(n_pred, 0.);
   if (want_var) {
-    lap_->PredVar(n_pred, idx, var.data());
+    lap_->PredVar(n_pred, idx, var.data(), wtd ? wt.data() : nullptr);
     for (int i = 0; i < n_pred; ++i)
       for (int k = 0; k < K; ++k)
-        if (idx[(size_t)i * K + k] < 0) var[i] += cp[k];
+        if (idx[(size_t)i * K + k] < 0) var[i] += wtd ? cp[k] * wt[(size_t)i * K + k] * wt[(size_t)i * K + k] : cp[k];
   }
   if (predict_response)
     response_transform(lik_, aux_pars_.empty() ? 1. : aux_pars_[0], 0., iter.delta_conv_mode_finding, stream_, n_pred,

@@ -22,6 +22,18 @@
 
 namespace gpb_amd {
 
+// Random slopes (group_rand_coef_data; re_model_template.h:246-273, 6845-6872): R covariates (data column-major
+// n x R), slope r on grouping variable ind[r] (counted from 1); drop[k] > 0 (nullable, K entries) removes the
+// intercept of grouping variable k, which must have a slope. The model's components are then the K intercepts in
+// column order, the R slopes in column order, minus the dropped intercept: component c has the levels of its
+// grouping variable, the value z_c[i] of Z (1 or the covariate) and one variance.
+struct GroupedSlopes {
+  int R = 0;
+  const double* data = nullptr;
+  const int32_t* ind = nullptr;
+  const int* drop = nullptr;
+};
+
 class GroupedModel {
  public:
   // levels: K x n level indices (order of first appearance, as RECompGroup numbers its labels,
@@ -33,7 +45,12 @@ class GroupedModel {
   // shape of gamma / negative_binomial is the auxiliary parameter.
   GroupedModel(int n, const std::vector<std::vector<int>>& levels, const std::string& matrix_inversion_method,
                int seed, std::vector<std::unordered_map<std::string, int>> label_index = {},
-               const std::string& likelihood = "gaussian");
+               const std::string& likelihood = "gaussian", const GroupedSlopes& slopes = GroupedSlopes());
+  // K(): the components (one variance each); num_groups(): the grouping variables (the label columns of
+  // re_group_data and re_group_data_pred); num_slopes(): the columns of the slope data
+  int num_groups() const { return G_; }
+  int num_slopes() const { return (int)slope_data_.size(); }
+  bool has_slopes() const { return !slope_data_.empty(); }
   ~GroupedModel();
   // Combined model (re_model_template.h:236-239 allows grouped random effects beside a GP for
   // gp_approx = "none"): one dense GP component on coords (host column-major n x d, as GPB_CreateREModel passes
@@ -142,6 +159,7 @@ class GroupedModel {
   // grouped branch re_model_template.h:4065-4167): out[k n + i] = posterior mean of effect k at
   // observation i's level; calc_var (cholesky only, as the reference's iterative branch refuses it):
   // out[K n + k n + i] = its posterior variance. cov_pars original scale (null: the last ones).
+  // With random slopes: one block per component; a slope's block holds the slope effect b, not x b.
   void PredictTrainingDataRandomEffects(const double* cov_pars, const double* y, double* out,
                                         const double* fixed_effects, bool calc_var);
   // GPB_PredictREModel with re_group_data_pred (re_model_template.h:3146 -> CalcPred :10026-10535, Woodbury branch): means; with
@@ -150,9 +168,12 @@ class GroupedModel {
   // e_p the indicator of p's seen levels (derivation in grouped.h), times sigma^2.
   // Combined models: gp_coords_pred (column-major n_pred x d) required; mean = Sigma_po Psi^-1 y, (co)variances
   // from the dense factor with the grouped cross-covariances (DenseSolver::Predict).
+  // Random slopes: slope_data_pred (column-major n_pred x R, required then) gives Z's values z_c(p) of the
+  // prediction points: mean = sum_c z_c(p) b_c[level], e_p holds z_c(p), and a new label adds tau_c z_c(p) z_c(q).
   void Predict(const double* y, int n_pred, const char* re_group_data_pred, const double* gp_coords_pred,
                const double* cov_pars, bool predict_cov_mat, bool predict_var, bool predict_response,
-               const double* fixed_effects, const double* fixed_effects_pred, double* out);
+               const double* fixed_effects, const double* fixed_effects_pred, double* out,
+               const double* slope_data_pred = nullptr);
   // GPB_GetCovPar(calc_std_dev) (CalcStdDevCovPar re_model_template.h:9775-9789 ->
   // CalcFisherInformation_Only_Grouped_REs_Woodbury :9559-9651): sqrt(diag(FI^-1)) at the original-scale
   // cov_pars; cholesky only (the iterative branch is a stochastic estimate: refused)
@@ -189,9 +210,17 @@ class GroupedModel {
   bool aux_pars_set_ = false;
   // with_coef: coef_ holds the covariates of this fit and beta joins the optimizer's vector
   void OptimCovParLaplace(const double* y, const double* fixed_effects, bool with_coef = false);
+  // optimizer_cov = "gradient_descent" for Laplace models (with or without Nesterov acceleration; no covariates):
+  // start = the initial variances, the auxiliary parameter from aux_pars_
+  void GradientDescentLaplace(const std::vector<double>& start, bool with_aux);
   void PredictLaplace(const double* y, int n_pred, const char* re_group_data_pred, const double* cov_pars,
                       bool predict_var, bool predict_response, const double* fixed_effects,
-                      const double* fixed_effects_pred, double* out);
+                      const double* fixed_effects_pred, double* out, const double* slope_data_pred);
+  // The prediction points per component: idx (np x C, global level index or -1 for a label not in the training
+  // data), wt (np x C, Z's values; empty without slopes) and, when asked, fresh (C x np: ids of the new labels,
+  // equal for equal labels of one grouping variable, -1 for seen ones)
+  void PredComponents(int n_pred, const char* re_group_data_pred, const double* slope_data_pred, std::vector<int>& idx,
+                      std::vector<double>& wt, std::vector<std::vector<int>>* fresh) const;
   std::vector<double> LaplaceCovPars(const double* cov_pars) const;
   // linear regression coefficients (Laplace models): the layer of the last fit and its coefficients (original scale)
   std::unique_ptr<CoefLayer> coef_;
@@ -199,8 +228,11 @@ class GroupedModel {
   void RefreshCoefOffset();   // the device offset := F of the fit + X beta
   std::string optimizer_coef_ = "lbfgs";
   bool cov_par_index_given_ = false, init_coef_given_ = false;
-  std::vector<std::vector<int>> levels_;                       // K x n
-  std::vector<std::unordered_map<std::string, int>> label_index_;   // label -> level, per effect
+  std::vector<std::vector<int>> levels_;                       // C x n, per component
+  std::vector<std::unordered_map<std::string, int>> label_index_;   // label -> level, per grouping variable
+  int G_ = 0;                                  // grouping variables
+  std::vector<int> comp_group_, comp_slope_;   // per component: its grouping variable, its slope column (-1: intercept)
+  std::vector<std::vector<double>> slope_data_;   // R x n
   std::vector<double> y_raw_, y_;
   bool y_set_ = false;
 

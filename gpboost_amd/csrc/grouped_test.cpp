@@ -94,16 +94,27 @@ void GroupedTestAccess::Precond(GroupedRE& re, const double* R, double* Z, doubl
 const std::vector<int>& GroupedTestAccess::Cum(const GroupedRE& re) { return re.cum_; }
 const int* GroupedTestAccess::ObsPtr(const GroupedRE& re) { return re.d_obs_ptr_.get(); }
 const int* GroupedTestAccess::Obs(const GroupedRE& re) { return re.d_obs_.get(); }
+const double* GroupedTestAccess::ObsW(const GroupedRE& re) { return re.weighted_ ? re.d_obs_w_.get() : nullptr; }
 const int* GroupedTestAccess::DevCum(const GroupedRE& re) { return re.d_cum_.get(); }
 const int* GroupedTestAccess::Split(const GroupedRE& re) { return re.d_split_.get(); }
 const double* GroupedTestAccess::Val(const GroupedRE& re) { return re.d_val_.get(); }
 const double* GroupedTestAccess::Cnt(const GroupedRE& re) { return re.d_cnt_.get(); }
 
-GroupedTest::GroupedTest(int n, int K, const int32_t* levels) : n_(n), K_(K) {
+GroupedTest::GroupedTest(int n, int K, const int32_t* levels, const double* weights, const int32_t* has_weight)
+    : n_(n), K_(K) {
   levels_.resize(K);
   for (int k = 0; k < K; ++k) levels_[k].assign(levels + (size_t)k * n, levels + (size_t)(k + 1) * n);
+  if (weights != nullptr) {
+    weights_.resize(K);
+    wptr_.assign(K, nullptr);
+    for (int k = 0; k < K; ++k) {
+      if (has_weight != nullptr && has_weight[k] == 0) continue;
+      weights_[k].assign(weights + (size_t)k * n, weights + (size_t)(k + 1) * n);
+      wptr_[k] = weights_[k].data();
+    }
+  }
   HIP_CHECK(hipStreamCreate(&s_));
-  re_.reset(new GroupedRE(n, levels_, s_));
+  re_.reset(new GroupedRE(n, levels_, s_, wptr_));
 }
 
 GroupedTest::~GroupedTest() {
@@ -114,7 +125,7 @@ GroupedTest::~GroupedTest() {
 
 GroupedLaplace& GroupedTest::Laplace() {
   if (K_ > kGlpMaxK) Fatal("GPB_TestGrouped: the Laplace kernels take at most %d effects", kGlpMaxK);
-  if (!glp_) glp_.reset(new GroupedLaplace(re_.get(), levels_, kLikPoisson));
+  if (!glp_) glp_.reset(new GroupedLaplace(re_.get(), levels_, kLikPoisson, wptr_));
   return *glp_;
 }
 
@@ -249,7 +260,8 @@ void GroupedTest::Small(int op, const double* const* in, const int64_t* in_len, 
   for (int k = 0; k < no; ++k) g[k].make((size_t)wo[k]);
   switch (op) {
     case kGreZty:
-      launch_gre_zty(M, GroupedTestAccess::ObsPtr(*re_), GroupedTestAccess::Obs(*re_), d[0].get(), g[0].p(), s_);
+      launch_gre_zty(M, GroupedTestAccess::ObsPtr(*re_), GroupedTestAccess::Obs(*re_), GroupedTestAccess::ObsW(*re_),
+                     d[0].get(), g[0].p(), s_);
       break;
     case kGreDiag:
       launch_gre_diag(K, GroupedTestAccess::DevCum(*re_), d[0].get(), d[1].get(), g[0].p(), g[1].p(), g[2].p(), s_);
@@ -291,9 +303,15 @@ void GroupedTest::Dense(int op, int ld, int np, const int32_t* idx, const double
     case kGrePredVar: ni = 1; wi[0] = mm; no = 1; wo[0] = np; break;
     default: ni = 2; wi[0] = M; wi[1] = mm; no = 2; wo[0] = (int64_t)M * K; wo[1] = M;
   }
+  const bool pred_wt = pred && re_->weighted();   // one more input: wt (np K)
+  if (pred_wt) {
+    ni = 2;
+    wi[1] = (int64_t)np * K;
+  }
   check_arrays(fn, op, reinterpret_cast<const void* const*>(in), in_len, n_in, wi, ni, "input");
   check_arrays(fn, op, reinterpret_cast<const void* const*>(out), out_len, n_out, wo, no, "output");
   DevBuf<double> d[2];
+  const double* dwt = pred_wt ? upload(d[1], in[1], (size_t)np * K) : nullptr;
   DevBuf<int> didx;
   Guarded g[2];
   g[0].make((size_t)wo[0], op == kGreDenseBuild ? 0. : kNaN);   // the build writes into a zero-filled matrix
@@ -311,10 +329,10 @@ void GroupedTest::Dense(int op, int ld, int np, const int32_t* idx, const double
     }
     case kGreInvDiag: launch_gre_inv_diag(M, ld, upload_dense(d[0], in[0], M, ld), g[0].p(), s_); break;
     case kGrePredE:
-      launch_gre_pred_cols(M, ld, K, np, didx.get(), upload_dense(d[0], in[0], M, ld), g[0].p(), nullptr, s_);
+      launch_gre_pred_cols(M, ld, K, np, didx.get(), dwt, upload_dense(d[0], in[0], M, ld), g[0].p(), nullptr, s_);
       break;
     case kGrePredVar:
-      launch_gre_pred_cols(M, ld, K, np, didx.get(), upload_dense(d[0], in[0], M, ld), nullptr, g[0].p(), s_);
+      launch_gre_pred_cols(M, ld, K, np, didx.get(), dwt, upload_dense(d[0], in[0], M, ld), nullptr, g[0].p(), s_);
       break;
     default:
       launch_gre_fisher_cols(M, ld, K, GroupedTestAccess::DevCum(*re_), upload(d[0], in[0], M),
@@ -400,6 +418,7 @@ void GroupedTest::LaplaceOps(int op, int sub, int t, int ld, double alpha, const
       if (!(in[0][k] > 0.) || !std::isfinite(in[0][k])) Fatal("%s: sigma2[%d] must be finite and > 0", fn, k);
   GroupedLaplace& glp = Laplace();
   const int* glev = GroupedTestAccess::Glev(glp);
+  const double* zw = GroupedTestAccess::Zw(glp);
   DevBuf<double> d[kGroupedMaxArrays];
   const double* p[kGroupedMaxArrays] = {nullptr};
   for (int k = 0; k < ni; ++k) {
@@ -414,10 +433,10 @@ void GroupedTest::LaplaceOps(int op, int sub, int t, int ld, double alpha, const
     case kGlpAssemble: GroupedTestAccess::Assemble(glp, p[0], g[0].p(), flag); break;
     case kGlpQ:
       gpart.make((size_t)(K + 1) * test_glp_blocks(n));
-      test_glp_q(n, K, glev, p[0], ld, p[1], p[2], p[3], p[4], flag, g[0].p(), gpart.p(), g[1].p(), s_);
+      test_glp_q(n, K, glev, zw, p[0], ld, p[1], p[2], p[3], p[4], flag, g[0].p(), gpart.p(), g[1].p(), s_);
       break;
-    case kGlpRowTrace: test_glp_row_trace(n, K, t, glev, p[0], p[1], p[2], g[0].p(), s_); break;
-    case kGlpGradF: test_glp_grad_f(n, K, glev, p[0], p[1], p[2], p[3], g[0].p(), s_); break;
+    case kGlpRowTrace: test_glp_row_trace(n, K, t, glev, zw, p[0], p[1], p[2], g[0].p(), s_); break;
+    case kGlpGradF: test_glp_grad_f(n, K, glev, zw, p[0], p[1], p[2], p[3], g[0].p(), s_); break;
     case kGlpVec: test_glp_vec(sub, v, in[0], alpha, p[1], p[2], g[0].p(), s_); break;
     default: test_glp_effect_dots(sub, v, in[0], p[1], p[2], g[0].p(), s_);
   }

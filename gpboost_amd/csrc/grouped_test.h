@@ -40,7 +40,9 @@ struct GroupedTestAccess;   // friend of GroupedRE and GroupedLaplace
 
 // the handle of GPB_TestGroupedCreate: a GroupedRE on a stream of its own and, on first use, a GroupedLaplace on it
 struct GroupedTest {
-  GroupedTest(int n, int K, const int32_t* levels);
+  // weights (nullable): K x n values of Z, has_weight (K): 0 = effect k has none (all ones, a null array to the
+  // engine). With weights every op runs the weighted kernels; the prediction ops take wt (np K) as one more input.
+  GroupedTest(int n, int K, const int32_t* levels, const double* weights = nullptr, const int32_t* has_weight = nullptr);
   ~GroupedTest();
   GroupedTest(const GroupedTest&) = delete;
   GroupedTest& operator=(const GroupedTest&) = delete;
@@ -62,6 +64,8 @@ struct GroupedTest {
   GroupedLaplace& Laplace();
   int n_, K_;
   std::vector<std::vector<int>> levels_;
+  std::vector<std::vector<double>> weights_;
+  std::vector<const double*> wptr_;   // empty: unweighted
   hipStream_t s_ = nullptr;
   std::unique_ptr<GroupedRE> re_;
   std::unique_ptr<GroupedLaplace> glp_;
@@ -70,12 +74,14 @@ struct GroupedTest {
 // ---- launchers at the end of grouped_laplace.hip (device pointers)
 // glp_q_kernel<aux> on the constructor's block count, then glp_finish_kernel as Eval runs it: out[0 .. K) = the
 // sums of W_i q_ij, (aux) out[K] = the sum of Wa_i q_i. partial: (K + 1) test_glp_blocks(n) doubles
-void test_glp_q(int n, int K, const int* glev, const double* Ainv, int ld, const double* D, const double* W,
-                const double* dW, const double* Wa, bool aux, double* dwq, double* partial, double* out, hipStream_t s);
-void test_glp_row_trace(int n, int K, int t, const int* glev, const double* U, const double* V, const double* dW,
-                        double* dwq, hipStream_t s);
-void test_glp_grad_f(int n, int K, const int* glev, const double* d1, const double* dwq, const double* W,
-                     const double* v, double* out, hipStream_t s);
+// zw: the K x n table of Z's values (null: the unweighted instantiation)
+void test_glp_q(int n, int K, const int* glev, const double* zw, const double* Ainv, int ld, const double* D,
+                const double* W, const double* dW, const double* Wa, bool aux, double* dwq, double* partial, double* out,
+                hipStream_t s);
+void test_glp_row_trace(int n, int K, int t, const int* glev, const double* zw, const double* U, const double* V,
+                        const double* dW, double* dwq, hipStream_t s);
+void test_glp_grad_f(int n, int K, const int* glev, const double* zw, const double* d1, const double* dwq,
+                     const double* W, const double* v, double* out, hipStream_t s);
 // form: VecOp of grouped_laplace.hip (0 sigi + x, 1 x - sigi y, 2 x / y, 3 x + alpha y, 4 sqrt(1 / x)); sigma2: host, K
 void test_glp_vec(int form, const GroupedRE::View& v, const double* sigma2, double alpha, const double* x,
                   const double* y, double* out, hipStream_t s);
@@ -87,6 +93,7 @@ struct GroupedTestAccess {
   // GroupedLaplace (defined in grouped_laplace.hip)
   static void Assemble(GroupedLaplace& g, const double* w, double* out, bool diag_only);
   static const int* Glev(const GroupedLaplace& g);
+  static const double* Zw(const GroupedLaplace& g);   // null without weights
   static void SegCounts(const GroupedLaplace& g, int out[4]);   // long levels, their chunks, all long, all chunks
   // GroupedRE (defined in grouped_test.cpp)
   static GroupedOp Op(GroupedRE& re, int t);
@@ -95,6 +102,7 @@ struct GroupedTestAccess {
   static const std::vector<int>& Cum(const GroupedRE& re);
   static const int* ObsPtr(const GroupedRE& re);
   static const int* Obs(const GroupedRE& re);
+  static const double* ObsW(const GroupedRE& re);   // null without weights
   static const int* DevCum(const GroupedRE& re);
   static const int* Split(const GroupedRE& re);
   static const double* Val(const GroupedRE& re);

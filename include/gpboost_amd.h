@@ -63,7 +63,12 @@ GPBOOST_AMD_EXPORT int LGBM_RegisterLogCallback(void (*callback)(const char*));
 
 /* ---------------------------------------------------------------- model lifecycle */
 
-/* replaces GPB_CreateREModel (include/LightGBM/c_api.h:1358-1390; c_api.cpp:2693-2762) */
+/* replaces GPB_CreateREModel (include/LightGBM/c_api.h:1358-1390; c_api.cpp:2693-2762).
+ * Grouped random slopes: re_group_rand_coef_data is column-major num_data x num_re_group_rand_coef (0: none),
+ * ind_effect_group_rand_coef the grouping variable of every slope, counted from 1. The components (one variance
+ * each) are the intercepts, then the slopes, minus the intercept dropped by drop_intercept_group_rand_effect
+ * (num_re_group entries, nullable; at most one, of a variable that has a slope). Not with gp_coords or several
+ * clusters. */
 GPBOOST_AMD_EXPORT int GPB_CreateREModel(int32_t num_data,
     const int32_t* cluster_ids_data,
     const char* re_group_data,
@@ -689,6 +694,16 @@ GPBOOST_AMD_EXPORT int GPB_TestLikPath(int path, int kernel, int n, int lik, dou
  * count each) and ptr (M + 1) of the full, the lower and the upper plan, lower_q and upper_q (K + 1 each), all as
  * the device holds them; dbls: val (nnz), cnt (M). */
 GPBOOST_AMD_EXPORT int GPB_TestGroupedCreate(int n, int K, const int32_t* levels, int64_t levels_len, void** out);
+/* GPB_TestGroupedCreateWeighted: the same with the values of Z (random slopes): weights (K x n, finite) gives
+ * Z[i, level of i in effect k] = weights[k n + i] for every effect with has_weight[k] != 0; an effect with
+ * has_weight[k] == 0 is an intercept (all ones, no array). Two effects may share their levels. Every op of the
+ * GPB_TestGrouped* entries then runs the weighted kernels: op 0 of Small gives Z^T y with Z's values, the assembly
+ * of LaplaceOps the sums of z_k[i] w_i (diag_only) or of z_a[i] z_b[i] w_i (full), q / row trace / grad_F the weighted
+ * gathers, and ops 2 and 3 of Dense take one more input, wt (np K): column k of point p enters with wt[p K + k].
+ * dbls of Info then holds the weighted values of Z^T Z. */
+GPBOOST_AMD_EXPORT int GPB_TestGroupedCreateWeighted(int n, int K, const int32_t* levels, int64_t levels_len,
+                                                     const double* weights, int64_t weights_len,
+                                                     const int32_t* has_weight, void** out);
 GPBOOST_AMD_EXPORT int GPB_TestGroupedFree(void* handle);
 GPBOOST_AMD_EXPORT int GPB_TestGroupedInfo(void* handle, int t, int64_t* stats, int64_t stats_len, int32_t* ints,
                                            int64_t ints_len, double* dbls, int64_t dbls_len);
@@ -780,7 +795,11 @@ GPBOOST_AMD_EXPORT int GPB_SetPredictionData(REModelHandle handle,
  * covariance matrix are returned in prediction-point order (row p = the p-th prediction point); the
  * reference returns them in the order of its sparse factor's AMD permutation (an artefact of its
  * SimplicialLLT; the means are in prediction-point order on both sides). Unsupported inputs (clusters,
- * random coefficients, full_scale_vecchia, num_neighbors_pred > 64) return -1 with a message. */
+ * GP random coefficients, full_scale_vecchia, num_neighbors_pred > 64) return -1 with a message.
+ * Grouped models with random slopes need re_group_rand_coef_data_pred (column-major num_data_pred x
+ * num_re_group_rand_coef; also accepted and saved by GPB_SetPredictionData): the values of Z at the prediction
+ * points. GPB_PredictREModelTrainingDataRandomEffects returns one block of num_data means per component (a
+ * slope's block holds the slope effect, not its product with the covariate), then the variances where supported. */
 GPBOOST_AMD_EXPORT int GPB_PredictREModel(REModelHandle handle,
     const double* y_data,
     int32_t num_data_pred,
