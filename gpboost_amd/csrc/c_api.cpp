@@ -24,6 +24,7 @@
 #include "sparse_chol.h"
 #include "grouped_test.h"
 #include "lik_test.h"
+#include "fitc_test.h"
 #include "vif_test.h"
 
 using gpb_amd::GroupedModel;
@@ -1093,6 +1094,33 @@ int GPB_TestVifVector(int op, int n, int m, int d, int cov_type, double var, dou
   API_BEGIN();
   gpb_amd::test_vif_vector(op, n, m, d, cov_type, var, phi, pad_fill, arrays, lens, n_arrays, sum_ops, nt, out, out_len,
                            guard_flag);
+  API_END();
+}
+
+int GPB_TestFitcVector(int op, int n, int m, int d, int cov_type, double var, double phi, double extra, double pad_fill,
+                       const double* const* arrays, const int64_t* lens, int n_arrays, const int32_t* ints,
+                       int64_t ints_len, double* const* outs, const int64_t* out_lens, int n_outs, int* guard_flag) {
+  API_BEGIN();
+  gpb_amd::test_fitc_vector(op, n, m, d, cov_type, var, phi, extra, pad_fill, arrays, lens, n_arrays, ints, ints_len,
+                            outs, out_lens, n_outs, guard_flag);
+  API_END();
+}
+
+int GPB_TestFitcKmeans(int op, int n, int k, int d, const double* X, int64_t x_len, const double* mu, const double* mu_a,
+                       const double* mu_b, int64_t mu_len, const int32_t* cluster_in, int64_t cluster_len, int scan,
+                       int max_it, double* mu_out, int32_t* ints_out, int64_t ints_len, int* its, int* guard_flag) {
+  API_BEGIN();
+  gpb_amd::test_fitc_kmeans(op, n, k, d, X, x_len, mu, mu_a, mu_b, mu_len, cluster_in, cluster_len, scan, max_it, mu_out,
+                            ints_out, ints_len, its, guard_flag);
+  API_END();
+}
+
+int GPB_TestFitcStages(int stage, int n, int m, int d, int cov_type, double var, double phi, double var2, double phi2,
+                       const double* X, const double* Z, const double* y, int np, const double* Xp, const int32_t* match,
+                       double* const* outs, const int64_t* out_lens, int n_outs) {
+  API_BEGIN();
+  gpb_amd::test_fitc_stages(stage, n, m, d, cov_type, var, phi, var2, phi2, X, Z, y, np, Xp, match, outs, out_lens,
+                            n_outs);
   API_END();
 }
 

@@ -61,6 +61,67 @@ void fitc_mm_terms(hipStream_t s, const double* Kinv, const double* Winv, const 
                    const double* a, int m, int ldm, double* part, double* out6);
 void fitc_kmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm, double var,
               double phi, double* Kmn);
+// fitc_mm_terms' kernel alone: the six sums per block of 4 columns (part: 6 (m + 3) / 4 doubles)
+void fitc_mm_parts(hipStream_t s, const double* Kinv, const double* Winv, const double* Kmm, const double* dK,
+                   const double* a, int m, int ldm, double* part);
+
+// The launch functions of the remaining FITC kernels (fitc_kernels.hip, fitc_fisher.hip): the only places where
+// these kernels are launched, by FitcSolver, fitc_inducing_points and the test entries (fitc_test.cpp) alike.
+// K_mm (diagonal var), K_mm,s (diagonal var (1 + 1e-6)) and dK_mm / dlog(range) (diagonal 0), m x m full (ld ldm)
+void fitc_kmm(hipStream_t s, int cov_type, const double* Z, int m, int d, int ldm, double var, double phi, double* Kmm,
+              double* Ks, double* dK);
+// d_i = dvar - |V_i|^2, K_d = K_mn diag(1 / d), logd_sum = sum log d (part: (n + 3) / 4 doubles)
+void fitc_diag(hipStream_t s, const double* V, const double* Kmn, int n, int m, int ldm, double dvar, double* dvec,
+               double* Kd, double* part, double* logd_sum);
+// Dy_i = (1 / d_i) y_i
+void fitc_dy(hipStream_t s, const double* dvec, const double* y, int n, double* Dy);
+// out = M x (M m x n, ld ldm; part: ((n + 63) / 64) ldm doubles)
+void fitc_gemv(hipStream_t s, const double* M, const double* x, int n, int m, int ldm, double* part, double* out);
+// y_aux_i = Dy_i - (K_nm w)_i / d_i, q_sum = y^T y_aux (part: (n + 3) / 4 doubles)
+void fitc_yaux(hipStream_t s, const double* Kmn, const double* w, const double* y, const double* Dy, const double* dvec,
+               int n, int m, int ldm, double* yaux, double* part, double* q_sum);
+// the per-observation gradient terms [s1v, s1r, s2v, s2r] summed per block of 4 observations (part: 4 ((n + 3) / 4)
+// doubles, which launch_sum_blocks(part, (n + 3) / 4, 4, ...) adds up)
+void fitc_grad_parts(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
+                     double var, double phi, double delta, const double* Kmn, const double* A, const double* Gt,
+                     const double* Mr, const double* a, const double* dvec, const double* yaux, double* part);
+// out_i = sum_j M[j, i] v_j, or sum_j M[j, i]^2 with v = nullptr (M m x np, ld ldm)
+void fitc_coldot(hipStream_t s, const double* M, const double* v, int np, int m, int ldm, double* out);
+// the prediction correction of npairs (prediction point, training point) pairs (pairs: 2 npairs ints, every
+// prediction point at most once): corr_q = sii - P_pi . K_mn,oj, Maux[:, pi] -= K_mn[:, oj] corr_q / d_oj; no pair,
+// no launch
+void fitc_pred_corr(hipStream_t s, const int* pairs, int npairs, const double* P, const double* Kmn,
+                    const double* dvec, int m, int ldm, double sii, double* Maux, double* corr);
+// k-means (Lloyd) steps on the device points X (n x d row-major) and centres mu (k x d): the nearest centre of every
+// point; the clusters' new means (scan: one wave per cluster scans the assignment; otherwise from member lists
+// built in w); flags[0] = any(mu != a), flags[1] = any(mu != b)
+struct KmeansWork {   // the member-list path's buffers
+  int* cnt;    // nbk x k, nbk = (n + 255) / 256 partition blocks
+  int* off;    // nbk x k
+  int* tot;    // k
+  int* base;   // k + 1
+  int* list;   // n
+};
+void fitc_kmeans_assign(hipStream_t s, const double* X, const double* mu, int n, int k, int d, int* cluster);
+void fitc_kmeans_means(hipStream_t s, bool scan, const double* X, const int* cluster, int n, int k, int d,
+                       const double* mu_old, double* mu_new, const KmeansWork& w);
+void fitc_kmeans_cmp(hipStream_t s, const double* mu, const double* a, const double* b, int cnt, int* flags);
+// Lloyd iterations from the seeds Z (host m x d, replaced by the final means) over the host points coords (n x d)
+// until the means repeat the previous or the one-before-previous iterate or max_it iterations ran; returns the
+// number of iterations
+int fitc_kmeans_lloyd(hipStream_t s, const double* coords, int n, int d, int m, double* Z, bool scan, int max_it);
+// the Fisher information's kernels (fitc_fisher.hip): dK_mn / dlog(range); dd_i = base - (2 A_i . dK_i - A_i . M_i);
+// y = 1 / x; Y = alpha s .* X (+ Yin) over column-major n x t blocks (Y may alias Yin); out = sum_e a_e b_e
+// (part: kFitcDotBlocks doubles)
+constexpr int kFitcDotBlocks = 512;
+void fitc_ff_dkmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
+                  double var, double phi, double* dK);
+void fitc_ff_diag_grad(hipStream_t s, const double* A, const double* dK, const double* M, int n, int m, int ldm,
+                       double base, double* dd);
+void fitc_ff_recip(hipStream_t s, int n, const double* x, double* y);
+void fitc_ff_rowscale(hipStream_t s, int n, int t, const double* sc, const double* X, double alpha, const double* Yin,
+                      double* Y);
+void fitc_ff_dot(hipStream_t s, size_t count, const double* a, const double* b, double* part, double* out);
 
 class FitcSolver {
  public:
@@ -98,6 +159,7 @@ class FitcSolver {
   friend class FitcLaplace;   // the Laplace approximation (fitc_laplace.h) works on these buffers
   friend class VifSolver;     // the full-scale Vecchia approximation (vif.h) reuses the low-rank part
   friend class VifLaplace;    // and its Laplace approximation (vif_laplace.h)
+  friend struct FitcTestAccess;   // the stage test entry (fitc_test.cpp) runs Factor and copies the buffers out
   // K_mn, K_mm, K_mm,s, dK_mm, L = chol(K_mm,s) (red[0] = 2 sum log L_ii), L^-1 (Li_), V = L^-1 K_mn,
   // K_mm,s^-1 (Kinv_): the part of the factorization that does not depend on the likelihood
   void Prior(int cov_type, double var, double phi, double* red);

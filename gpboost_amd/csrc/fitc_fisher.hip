@@ -84,7 +84,6 @@ __global__ void __launch_bounds__(256) ff_rowscale_kernel(int n, int t, const do
 }
 
 // block partials of sum_e a_e b_e (fixed order: per-thread strided sums, then a wave / block tree)
-constexpr int kDotBlocks = 512;
 __global__ void __launch_bounds__(256) ff_dot_kernel(size_t count, const double* __restrict__ a,
                                                      const double* __restrict__ b, double* __restrict__ part) {
   __shared__ double red[4];
@@ -100,6 +99,34 @@ __global__ void __launch_bounds__(256) ff_dot_kernel(size_t count, const double*
 
 }  // namespace
 
+void fitc_ff_dkmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
+                  double var, double phi, double* dK) {
+  dispatch_cov(cov_type, [&](auto c) {
+    hipLaunchKernelGGL((ff_dkmn_kernel<decltype(c)::value>), dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, s, X, Z, n,
+                       m, d, ldm, var, phi, dK);
+  });
+}
+
+void fitc_ff_diag_grad(hipStream_t s, const double* A, const double* dK, const double* M, int n, int m, int ldm,
+                       double base, double* dd) {
+  hipLaunchKernelGGL(ff_diag_grad_kernel, dim3((n + 3) / 4), dim3(256), 0, s, A, dK, M, n, m, ldm, base, dd);
+}
+
+void fitc_ff_recip(hipStream_t s, int n, const double* x, double* y) {
+  hipLaunchKernelGGL(ff_recip_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, x, y);
+}
+
+void fitc_ff_rowscale(hipStream_t s, int n, int t, const double* sc, const double* X, double alpha, const double* Yin,
+                      double* Y) {
+  const int eb = (int)std::min<size_t>(((size_t)n * t + 255) / 256, 4096);
+  hipLaunchKernelGGL(ff_rowscale_kernel, dim3(eb), dim3(256), 0, s, n, t, sc, X, alpha, Yin, Y);
+}
+
+void fitc_ff_dot(hipStream_t s, size_t count, const double* a, const double* b, double* part, double* out) {
+  hipLaunchKernelGGL(ff_dot_kernel, dim3(kFitcDotBlocks), dim3(256), 0, s, count, a, b, part);
+  launch_sum_blocks(part, kFitcDotBlocks, 1, out, s);
+}
+
 void FitcSolver::Fisher(int cov_type, const double* orig, const double* trafo, int t, int seed, uint64_t run_id,
                         double* FI) {
   const int n = n_, m = m_, ldm = ldm_, d = d_;
@@ -107,7 +134,7 @@ void FitcSolver::Fisher(int cov_type, const double* orig, const double* trafo, i
   if (!(orig[0] > 0. && orig[1] > 0. && orig[2] > 0.)) Fatal("covariance parameters must be > 0");
   const double var = trafo[1], phi = trafo[2];
   const size_t nt = (size_t)n * t, mt = (size_t)ldm * t;
-  DevBuf<double> blk(9 * nt), mblk(4 * mt), nv(4 * (size_t)n), part(kDotBlocks), dots(8);
+  DevBuf<double> blk(9 * nt), mblk(4 * mt), nv(4 * (size_t)n), part(kFitcDotBlocks), dots(8);
   double* Zc = blk.get();
   double* X0 = Zc + nt;
   double* Y = X0 + nt;
@@ -131,35 +158,20 @@ void FitcSolver::Fisher(int cov_type, const double* orig, const double* trafo, i
   HIP_CHECK(hipMemcpyAsync(&info, info_.get(), sizeof(int), hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
   if (info != 0) Fatal("the FITC factor is not positive definite at these covariance parameters");
-  const int nb4 = (n + 3) / 4;
   // A = K_mm,s^-1 K_mn = L^-T V (LiT: the clean upper triangle of L^-T); dK_mn / dlog(phi) into Kd_
   gemm_f64(stream_, m, n, m, 1., LiT_.get(), ldm, 0, V_.get(), ldm, 0, 0., A_.get(), ldm, 0, 0, 1, 0);
-  switch (cov_type) {
-#define GPB_FF_DKMN(C)                                                                                             \
-  case C:                                                                                                          \
-    hipLaunchKernelGGL((ff_dkmn_kernel<C>), dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, stream_, d_X_, dZ_.get(), \
-                       n, m, d, ldm, var, phi, Kd_.get());                                                         \
-    break;
-    GPB_FF_DKMN(kMatern05)
-    GPB_FF_DKMN(kMatern15)
-    GPB_FF_DKMN(kMatern25)
-    GPB_FF_DKMN(kGaussian)
-#undef GPB_FF_DKMN
-    default: Fatal("unsupported covariance type %d", cov_type);
-  }
-  hipLaunchKernelGGL(ff_recip_kernel, dim3((n + 255) / 256), dim3(256), 0, stream_, n, vec_.get(), dinv);
+  fitc_ff_dkmn(stream_, cov_type, d_X_, dZ_.get(), n, m, d, ldm, var, phi, Kd_.get());
+  fitc_ff_recip(stream_, n, vec_.get(), dinv);
   const double* dK[2] = {Kmn_.get(), Kd_.get()};
   const double* dKmm[2] = {Kmm_.get(), dKmm_.get()};
   const double base[2] = {var, 0.};
   for (int k = 0; k < 2; ++k) {   // dK_mm,k A into V_ (free after A), then the diagonal derivative
     gemm_f64(stream_, m, n, m, 1., dKmm[k], ldm, 0, A_.get(), ldm, 0, 0., V_.get(), ldm);
-    hipLaunchKernelGGL(ff_diag_grad_kernel, dim3(nb4), dim3(256), 0, stream_, A_.get(), dK[k], V_.get(), n, m, ldm,
-                       base[k], dd[k]);
+    fitc_ff_diag_grad(stream_, A_.get(), dK[k], V_.get(), n, m, ldm, base[k], dd[k]);
   }
   HIP_CHECK(hipGetLastError());
-  const int eb = (int)std::min<size_t>((nt + 255) / 256, 4096);
   auto rowscale = [&](const double* s, const double* X, double alpha, const double* Yin, double* Yo) {
-    hipLaunchKernelGGL(ff_rowscale_kernel, dim3(eb), dim3(256), 0, stream_, n, t, s, X, alpha, Yin, Yo);
+    fitc_ff_rowscale(stream_, n, t, s, X, alpha, Yin, Yo);
   };
   // Y = Psi^-1 X
   auto psi_inv = [&](const double* X, double* Yo) {
@@ -196,8 +208,7 @@ void FitcSolver::Fisher(int cov_type, const double* orig, const double* trafo, i
   const double* da[6] = {X0, X0, X0, Rk[0], Rk[0], Rk[1]};
   const double* db[6] = {X0, S[0], S[1], S[0], S[1], S[1]};
   for (int q = 0; q < 6; ++q) {
-    hipLaunchKernelGGL(ff_dot_kernel, dim3(kDotBlocks), dim3(256), 0, stream_, nt, da[q], db[q], part.get());
-    launch_sum_blocks(part.get(), kDotBlocks, 1, dots.get() + q, stream_);
+    fitc_ff_dot(stream_, nt, da[q], db[q], part.get(), dots.get() + q);
   }
   HIP_CHECK(hipGetLastError());
   double h[6];

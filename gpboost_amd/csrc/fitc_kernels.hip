@@ -638,15 +638,47 @@ std::vector<double> fitc_inducing_points(const std::vector<double>& coords, int 
   // Lloyd iterations (kmeans_plusplus, GP_utils.cpp:280-294) on the GPU: stop when the means repeat
   // the previous or the one-before-previous iterate, or after max_it = 1000
   // (re_model_template.h:6995)
-  const int max_it = 1000;
+  static const bool scan_means = std::getenv("GPBOOST_AMD_KMEANS_SCAN") != nullptr;   // A/B: the scanning kernel
+  fitc_kmeans_lloyd(s, coords.data(), n, d, m, Z.data(), scan_means, 1000);
+  return Z;
+}
+
+void fitc_kmeans_assign(hipStream_t s, const double* X, const double* mu, int n, int k, int d, int* cluster) {
+  if (d == 2)
+    hipLaunchKernelGGL(kmeans_assign_kernel<2>, dim3((n + 255) / 256), dim3(256), 0, s, X, mu, n, k, d, cluster);
+  else
+    hipLaunchKernelGGL(kmeans_assign_kernel<0>, dim3((n + 255) / 256), dim3(256), 0, s, X, mu, n, k, d, cluster);
+}
+
+void fitc_kmeans_means(hipStream_t s, bool scan, const double* X, const int* cluster, int n, int k, int d,
+                       const double* mu_old, double* mu_new, const KmeansWork& w) {
+  if (scan) {
+    hipLaunchKernelGGL(kmeans_means_kernel, dim3(k), dim3(64), 0, s, X, cluster, n, k, d, mu_old, mu_new);
+    return;
+  }
+  const int nbk = (n + kKmP - 1) / kKmP;
+  hipLaunchKernelGGL(kmeans_count_kernel, dim3(nbk), dim3(256), sizeof(int) * k, s, cluster, n, k, w.cnt);
+  hipLaunchKernelGGL(kmeans_offsets_kernel, dim3((k + 63) / 64), dim3(64), 0, s, w.cnt, nbk, k, w.off, w.tot);
+  hipLaunchKernelGGL(kmeans_bases_kernel, dim3(1), dim3(64), 0, s, w.tot, k, w.base);
+  hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(nbk), dim3(64), sizeof(int) * k, s, cluster, n, k, w.off, w.base,
+                     w.list);
+  hipLaunchKernelGGL(kmeans_means_list_kernel, dim3((k + 63) / 64), dim3(64), 0, s, X, w.list, w.base, k, d, mu_old,
+                     mu_new);
+}
+
+void fitc_kmeans_cmp(hipStream_t s, const double* mu, const double* a, const double* b, int cnt, int* flags) {
+  hipLaunchKernelGGL(kmeans_cmp_kernel, dim3(1), dim3(256), 0, s, mu, a, b, cnt, flags);
+}
+
+int fitc_kmeans_lloyd(hipStream_t s, const double* coords, int n, int d, int m, double* Z, bool scan, int max_it) {
   const size_t cnt = (size_t)m * d;
   DevBuf<double> dX((size_t)n * d), b0(cnt), b1(cnt), b2(cnt);
   DevBuf<int> cl(n), flags(2);
   const int nbk = (n + kKmP - 1) / kKmP;
   DevBuf<int> kcnt((size_t)nbk * m), koff((size_t)nbk * m), ktot(m), kbase(m + 1), klist(n);
-  static const bool scan_means = std::getenv("GPBOOST_AMD_KMEANS_SCAN") != nullptr;   // A/B: the scanning kernel
-  HIP_CHECK(hipMemcpyAsync(dX.get(), coords.data(), sizeof(double) * n * d, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b0.get(), Z.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, s));
+  const KmeansWork work{kcnt.get(), koff.get(), ktot.get(), kbase.get(), klist.get()};
+  HIP_CHECK(hipMemcpyAsync(dX.get(), coords, sizeof(double) * n * d, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b0.get(), Z, sizeof(double) * cnt, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemsetAsync(b1.get(), 0, sizeof(double) * cnt, s));
   HIP_CHECK(hipMemsetAsync(b2.get(), 0, sizeof(double) * cnt, s));
   double* mu = b0.get();
@@ -660,31 +692,17 @@ std::vector<double> fitc_inducing_points(const std::vector<double>& coords, int 
     old_old = old;
     old = mu;
     mu = free_buf;
-    if (d == 2)
-      hipLaunchKernelGGL(kmeans_assign_kernel<2>, dim3((n + 255) / 256), dim3(256), 0, s, dX.get(), old, n, m, d, cl.get());
-    else
-      hipLaunchKernelGGL(kmeans_assign_kernel<0>, dim3((n + 255) / 256), dim3(256), 0, s, dX.get(), old, n, m, d, cl.get());
-    if (scan_means) {
-      hipLaunchKernelGGL(kmeans_means_kernel, dim3(m), dim3(64), 0, s, dX.get(), cl.get(), n, m, d, old, mu);
-    } else {
-      hipLaunchKernelGGL(kmeans_count_kernel, dim3(nbk), dim3(256), sizeof(int) * m, s, cl.get(), n, m, kcnt.get());
-      hipLaunchKernelGGL(kmeans_offsets_kernel, dim3((m + 63) / 64), dim3(64), 0, s, kcnt.get(), nbk, m, koff.get(),
-                         ktot.get());
-      hipLaunchKernelGGL(kmeans_bases_kernel, dim3(1), dim3(64), 0, s, ktot.get(), m, kbase.get());
-      hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(nbk), dim3(64), sizeof(int) * m, s, cl.get(), n, m, koff.get(),
-                         kbase.get(), klist.get());
-      hipLaunchKernelGGL(kmeans_means_list_kernel, dim3((m + 63) / 64), dim3(64), 0, s, dX.get(), klist.get(), kbase.get(),
-                         m, d, old, mu);
-    }
-    hipLaunchKernelGGL(kmeans_cmp_kernel, dim3(1), dim3(256), 0, s, mu, old, old_old, (int)cnt, flags.get());
+    fitc_kmeans_assign(s, dX.get(), old, n, m, d, cl.get());
+    fitc_kmeans_means(s, scan, dX.get(), cl.get(), n, m, d, old, mu, work);
+    fitc_kmeans_cmp(s, mu, old, old_old, (int)cnt, flags.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(h_flags, flags.get(), sizeof(int) * 2, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     ++count;
   } while (h_flags[0] && h_flags[1] && count != max_it);
-  HIP_CHECK(hipMemcpyAsync(Z.data(), mu, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(Z, mu, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  return Z;
+  return count;
 }
 
 FitcSolver::FitcSolver(int n, int d, const double* d_X, const std::vector<double>& Z, hipStream_t stream)
@@ -720,14 +738,8 @@ void FitcSolver::Prior(int cov_type, double var, double phi, double* red) {
   const int n = n_, m = m_, ldm = ldm_, d = d_;
   kept_ = false;
   HIP_CHECK(hipMemsetAsync(info_.get(), 0, sizeof(int), stream_));
-  dispatch_cov(cov_type, [&](auto c) {
-    constexpr int COV = decltype(c)::value;
-    hipLaunchKernelGGL((fitc_kmn_kernel<COV>), dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, stream_, d_X_, dZ_.get(),
-                       n, m, d, ldm, var, phi, Kmn_.get());
-    hipLaunchKernelGGL((fitc_kmm_kernel<COV>), dim3((m + 63) / 64, (m + 3) / 4), dim3(256), 0, stream_, dZ_.get(), m, d,
-                       ldm, var, phi, Kmm_.get(), Ks_.get(), dKmm_.get());
-  });
-  HIP_CHECK(hipGetLastError());
+  fitc_kmn(stream_, cov_type, d_X_, dZ_.get(), n, m, d, ldm, var, phi, Kmn_.get());
+  fitc_kmm(stream_, cov_type, dZ_.get(), m, d, ldm, var, phi, Kmm_.get(), Ks_.get(), dKmm_.get());
   // L = chol(K_mm,s) in Li_ (lower), L^-1 in Wi_ -> copied to Li_'s role below
   HIP_CHECK(hipMemcpyAsync(Li_.get(), Ks_.get(), sizeof(double) * ldm * ldm, hipMemcpyDeviceToDevice, stream_));
   chol_lower(stream_, Li_.get(), Wi_.get(), m, ldm, info_.get());
@@ -746,18 +758,12 @@ void FitcSolver::FactorCommon(int cov_type, double var, double phi, double* red)
   const int n = n_, m = m_, ldm = ldm_;
   double* dvec = vec_.get();
   Prior(cov_type, var, phi, red);
-  const int nb4 = (n + 3) / 4;
-  hipLaunchKernelGGL(fitc_diag_kernel, dim3(nb4), dim3(256), 0, stream_, V_.get(), Kmn_.get(), n, m, ldm,
-                     1. + var * kJitterMult, dvec, Kd_.get(), part_.get());
-  HIP_CHECK(hipGetLastError());
-  launch_sum_blocks(part_.get(), nb4, 1, red + 2, stream_);
+  fitc_diag(stream_, V_.get(), Kmn_.get(), n, m, ldm, 1. + var * kJitterMult, dvec, Kd_.get(), part_.get(), red + 2);
   // W = K_mn K_d^T + K_mm,s (split K over the n observations), Lw = chol(W), Lw^-1, W^-1
   const long mm = (long)ldm * ldm;
   const int chunks = gemm_f64_splitk(stream_, m, m, n, Kmn_.get(), ldm, 0, Kd_.get(), ldm, 1, part_.get(), ldm, mm,
                                      2048, max_chunks_);
-  hipLaunchKernelGGL(fitc_wsum_kernel, dim3((m + 63) / 64, (m + 3) / 4), dim3(256), 0, stream_, part_.get(), chunks, mm,
-                     m, ldm, Ks_.get(), W_.get());
-  HIP_CHECK(hipGetLastError());
+  fitc_wsum(stream_, part_.get(), chunks, mm, m, ldm, Ks_.get(), W_.get());
   chol_lower(stream_, W_.get(), Wi_.get(), m, ldm, info_.get());
   launch_logdet_chol(stream_, W_.get(), ldm, m, red + 1);
   trtri_lower(stream_, W_.get(), Wi_.get(), T_.get(), 0, m, ldm);
@@ -775,18 +781,11 @@ void FitcSolver::Factor(int cov_type, double var, double phi, const double* d_y,
   const bool kept = kept_ && kept_cov_ == cov_type && kept_var_ == var && kept_phi_ == phi && kept_red_ == red;
   if (!kept) FactorCommon(cov_type, var, phi, red);
   kept_ = false;   // the gradient of the evaluation that follows overwrites V and K_d
-  const int nb4 = (n + 3) / 4;
-  hipLaunchKernelGGL(fitc_dy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream_, dvec, d_y, n, Dy);
+  fitc_dy(stream_, dvec, d_y, n, Dy);
   // u = K_mn (y / d), w = W^-1 u = Lw^-T (Lw^-1 u) (fitc_chol_solve; the a slot as scratch), y_aux, q
-  const int chunk = 64, nbg = (n + chunk - 1) / chunk;
-  hipLaunchKernelGGL(fitc_gemv_part_kernel, dim3(nbg), dim3(256), 0, stream_, Kmn_.get(), Dy, n, m, ldm, chunk,
-                     part_.get());
-  hipLaunchKernelGGL(fitc_gemv_reduce_kernel, dim3((m + 3) / 4), dim3(256), 0, stream_, part_.get(), nbg, m, ldm, u);
+  fitc_gemv(stream_, Kmn_.get(), Dy, n, m, ldm, part_.get(), u);
   fitc_chol_solve(stream_, Wi_.get(), WiT_.get(), u, m, ldm, w + ldm, w);
-  hipLaunchKernelGGL(fitc_yaux_kernel, dim3(nb4), dim3(256), 0, stream_, Kmn_.get(), w, d_y, Dy, dvec, n, m, ldm, yaux,
-                     part_.get());
-  HIP_CHECK(hipGetLastError());
-  launch_sum_blocks(part_.get(), nb4, 1, red + 3, stream_);
+  fitc_yaux(stream_, Kmn_.get(), w, d_y, Dy, dvec, n, m, ldm, yaux, part_.get(), red + 3);
 }
 
 void FitcSolver::Gram(int cov_type, double var, double phi, const double* d_Z, int c, double* G_host,
@@ -833,20 +832,13 @@ void FitcSolver::Eval(int cov_type, double var, double phi, const double* d_y, b
     gemm_f64(stream_, m, m, m, 1., Wi_.get(), ldm, 1, Wi_.get(), ldm, 0, 0., Winv_.get(), ldm, 0, 0, 1, 1);
     fitc_solve_kmn(stream_, Wi_.get(), Winv_.get(), Kmn_.get(), m, n, ldm, V_.get(), Kd_.get());
     gemm_f64(stream_, m, n, m, 1., dKmm_.get(), ldm, 0, A_.get(), ldm, 0, 0., V_.get(), ldm);
-    const int chunk = 64, nbg = (n + chunk - 1) / chunk;
-    hipLaunchKernelGGL(fitc_gemv_part_kernel, dim3(nbg), dim3(256), 0, stream_, A_.get(), yaux, n, m, ldm, chunk,
-                       part_.get());
-    hipLaunchKernelGGL(fitc_gemv_reduce_kernel, dim3((m + 3) / 4), dim3(256), 0, stream_, part_.get(), nbg, m, ldm, a);
+    fitc_gemv(stream_, A_.get(), yaux, n, m, ldm, part_.get(), a);
     const int nb4 = (n + 3) / 4;
     const double delta = var * kJitterMult - var;
-    dispatch_cov(cov_type, [&](auto c) {
-      hipLaunchKernelGGL((fitc_grad_kernel<decltype(c)::value>), dim3(nb4), dim3(256), 0, stream_, d_X_, dZ_.get(), n, m,
-                         d, ldm, var, phi, delta, Kmn_.get(), A_.get(), Kd_.get(), V_.get(), a, dvec, yaux, part_.get());
-    });
+    fitc_grad_parts(stream_, cov_type, d_X_, dZ_.get(), n, m, d, ldm, var, phi, delta, Kmn_.get(), A_.get(), Kd_.get(),
+                    V_.get(), a, dvec, yaux, part_.get());
     const int mb4 = (m + 3) / 4;
-    hipLaunchKernelGGL(fitc_mm_kernel, dim3(mb4), dim3(256), 0, stream_, Kinv_.get(), Winv_.get(), Kmm_.get(),
-                       dKmm_.get(), a, m, ldm, mmpart);
-    HIP_CHECK(hipGetLastError());
+    fitc_mm_parts(stream_, Kinv_.get(), Winv_.get(), Kmm_.get(), dKmm_.get(), a, m, ldm, mmpart);
     launch_sum_blocks(part_.get(), nb4, 4, red + 4, stream_);
     launch_sum_blocks(mmpart, mb4, 6, red + 8, stream_);
   }
@@ -894,14 +886,9 @@ void FitcSolver::Predict(int cov_type, double var, double phi, const double* d_y
   const double* w = yaux + n + ldm;
   DevBuf<double> dXp((size_t)np * d), Kmp((size_t)ldm * np), out((size_t)3 * np);
   HIP_CHECK(hipMemcpyAsync(dXp.get(), Xp, sizeof(double) * np * d, hipMemcpyHostToDevice, stream_));
-  dispatch_cov(cov_type, [&](auto c) {
-    hipLaunchKernelGGL((fitc_kmn_kernel<decltype(c)::value>), dim3((m + 63) / 64, (np + 3) / 4), dim3(256), 0, stream_,
-                       dXp.get(), dZ_.get(), np, m, d, ldm, var, phi, Kmp.get());
-  });
-  const int nb4 = (np + 3) / 4;
+  fitc_kmn(stream_, cov_type, dXp.get(), dZ_.get(), np, m, d, ldm, var, phi, Kmp.get());
   // mean = K_pm W^-1 K_mn (y / d)  (:10705)
-  hipLaunchKernelGGL(fitc_coldot_kernel, dim3(nb4), dim3(256), 0, stream_, Kmp.get(), w, np, m, ldm, out.get());
-  HIP_CHECK(hipGetLastError());
+  fitc_coldot(stream_, Kmp.get(), w, np, m, ldm, out.get());
   // coincident prediction / training coordinates: the FITC diagonal correction
   std::vector<int> pairs;
   for (int i = 0; i < np; ++i)
@@ -925,9 +912,7 @@ void FitcSolver::Predict(int cov_type, double var, double phi, const double* d_y
     corr.alloc(npairs);
     HIP_CHECK(hipMemcpyAsync(dpairs.get(), pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, stream_));
     gemm_f64(stream_, m, np, m, 1., Kinv_.get(), ldm, 0, Kmp.get(), ldm, 0, 0., P.get(), ldm);
-    hipLaunchKernelGGL(fitc_pred_corr_kernel, dim3(npairs), dim3(64), 0, stream_, dpairs.get(), npairs, P.get(),
-                       Kmn_.get(), dvec, m, ldm, sii, Maux.get(), corr.get());
-    HIP_CHECK(hipGetLastError());
+    fitc_pred_corr(stream_, dpairs.get(), npairs, P.get(), Kmn_.get(), dvec, m, ldm, sii, Maux.get(), corr.get());
     h_yaux.resize(n);
     h_d.resize(n);
     HIP_CHECK(hipMemcpyAsync(h_corr.data(), corr.get(), sizeof(double) * npairs, hipMemcpyDeviceToHost, stream_));
@@ -942,11 +927,8 @@ void FitcSolver::Predict(int cov_type, double var, double phi, const double* d_y
     U.alloc((size_t)ldm * np);
     gemm_f64(stream_, m, np, m, 1., Li_.get(), ldm, 0, Kmp.get(), ldm, 0, 0., Vp.get(), ldm, 0, 1, 0, 0);
     gemm_f64(stream_, m, np, m, 1., Wi_.get(), ldm, 0, Maux.get(), ldm, 0, 0., U.get(), ldm, 0, 1, 0, 0);
-    hipLaunchKernelGGL(fitc_coldot_kernel, dim3(nb4), dim3(256), 0, stream_, Vp.get(), nullptr, np, m, ldm,
-                       out.get() + np);
-    hipLaunchKernelGGL(fitc_coldot_kernel, dim3(nb4), dim3(256), 0, stream_, U.get(), nullptr, np, m, ldm,
-                       out.get() + 2 * (size_t)np);
-    HIP_CHECK(hipGetLastError());
+    fitc_coldot(stream_, Vp.get(), nullptr, np, m, ldm, out.get() + np);
+    fitc_coldot(stream_, U.get(), nullptr, np, m, ldm, out.get() + 2 * (size_t)np);
   }
   std::vector<double> h((size_t)3 * np);
   HIP_CHECK(hipMemcpyAsync(h.data(), out.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
@@ -1031,12 +1013,73 @@ void fitc_wsum(hipStream_t s, const double* P, int chunks, long stride, int m, i
   HIP_CHECK(hipGetLastError());
 }
 
+void fitc_mm_parts(hipStream_t s, const double* Kinv, const double* Winv, const double* Kmm, const double* dK,
+                   const double* a, int m, int ldm, double* part) {
+  hipLaunchKernelGGL(fitc_mm_kernel, dim3((m + 3) / 4), dim3(256), 0, s, Kinv, Winv, Kmm, dK, a, m, ldm, part);
+  HIP_CHECK(hipGetLastError());
+}
+
 void fitc_mm_terms(hipStream_t s, const double* Kinv, const double* Winv, const double* Kmm, const double* dK,
                    const double* a, int m, int ldm, double* part, double* out6) {
-  const int mb4 = (m + 3) / 4;
-  hipLaunchKernelGGL(fitc_mm_kernel, dim3(mb4), dim3(256), 0, s, Kinv, Winv, Kmm, dK, a, m, ldm, part);
+  fitc_mm_parts(s, Kinv, Winv, Kmm, dK, a, m, ldm, part);
+  launch_sum_blocks(part, (m + 3) / 4, 6, out6, s);
+}
+
+void fitc_kmm(hipStream_t s, int cov_type, const double* Z, int m, int d, int ldm, double var, double phi, double* Kmm,
+              double* Ks, double* dK) {
+  dispatch_cov(cov_type, [&](auto c) {
+    hipLaunchKernelGGL((fitc_kmm_kernel<decltype(c)::value>), dim3((m + 63) / 64, (m + 3) / 4), dim3(256), 0, s, Z, m, d,
+                       ldm, var, phi, Kmm, Ks, dK);
+  });
   HIP_CHECK(hipGetLastError());
-  launch_sum_blocks(part, mb4, 6, out6, s);
+}
+
+void fitc_diag(hipStream_t s, const double* V, const double* Kmn, int n, int m, int ldm, double dvar, double* dvec,
+               double* Kd, double* part, double* logd_sum) {
+  const int nb4 = (n + 3) / 4;
+  hipLaunchKernelGGL(fitc_diag_kernel, dim3(nb4), dim3(256), 0, s, V, Kmn, n, m, ldm, dvar, dvec, Kd, part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nb4, 1, logd_sum, s);
+}
+
+void fitc_dy(hipStream_t s, const double* dvec, const double* y, int n, double* Dy) {
+  hipLaunchKernelGGL(fitc_dy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, dvec, y, n, Dy);
+}
+
+void fitc_gemv(hipStream_t s, const double* M, const double* x, int n, int m, int ldm, double* part, double* out) {
+  const int chunk = 64, nbg = (n + chunk - 1) / chunk;
+  hipLaunchKernelGGL(fitc_gemv_part_kernel, dim3(nbg), dim3(256), 0, s, M, x, n, m, ldm, chunk, part);
+  hipLaunchKernelGGL(fitc_gemv_reduce_kernel, dim3((m + 3) / 4), dim3(256), 0, s, part, nbg, m, ldm, out);
+}
+
+void fitc_yaux(hipStream_t s, const double* Kmn, const double* w, const double* y, const double* Dy, const double* dvec,
+               int n, int m, int ldm, double* yaux, double* part, double* q_sum) {
+  const int nb4 = (n + 3) / 4;
+  hipLaunchKernelGGL(fitc_yaux_kernel, dim3(nb4), dim3(256), 0, s, Kmn, w, y, Dy, dvec, n, m, ldm, yaux, part);
+  HIP_CHECK(hipGetLastError());
+  launch_sum_blocks(part, nb4, 1, q_sum, s);
+}
+
+void fitc_grad_parts(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm,
+                     double var, double phi, double delta, const double* Kmn, const double* A, const double* Gt,
+                     const double* Mr, const double* a, const double* dvec, const double* yaux, double* part) {
+  dispatch_cov(cov_type, [&](auto c) {
+    hipLaunchKernelGGL((fitc_grad_kernel<decltype(c)::value>), dim3((n + 3) / 4), dim3(256), 0, s, X, Z, n, m, d, ldm,
+                       var, phi, delta, Kmn, A, Gt, Mr, a, dvec, yaux, part);
+  });
+}
+
+void fitc_coldot(hipStream_t s, const double* M, const double* v, int np, int m, int ldm, double* out) {
+  hipLaunchKernelGGL(fitc_coldot_kernel, dim3((np + 3) / 4), dim3(256), 0, s, M, v, np, m, ldm, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void fitc_pred_corr(hipStream_t s, const int* pairs, int npairs, const double* P, const double* Kmn,
+                    const double* dvec, int m, int ldm, double sii, double* Maux, double* corr) {
+  if (npairs < 1) return;
+  hipLaunchKernelGGL(fitc_pred_corr_kernel, dim3(npairs), dim3(64), 0, s, pairs, npairs, P, Kmn, dvec, m, ldm, sii,
+                     Maux, corr);
+  HIP_CHECK(hipGetLastError());
 }
 
 void fitc_kmn(hipStream_t s, int cov_type, const double* X, const double* Z, int n, int m, int d, int ldm, double var,

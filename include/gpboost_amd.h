@@ -633,6 +633,46 @@ GPBOOST_AMD_EXPORT int GPB_TestVifVector(int op, int n, int m, int d, int cov_ty
                                          double pad_fill, const double* const* arrays, const int64_t* lens,
                                          int n_arrays, const int32_t* sum_ops, int nt, double* out, int64_t out_len,
                                          int* guard_flag);
+/* The FITC kernels (csrc/fitc_kernels.hip, csrc/fitc_fisher.hip) on host arrays, launched by the host launch
+ * functions FitcSolver and fitc_inducing_points use (csrc/fitc.h). No reference counterpart (tests). Everything is
+ * checked on the host before any device call, a violation being an error return. Matrices that the device holds as
+ * m x n with leading dimension ldm = round_up(m, 64) are host arrays n x m row-major, the m x m ones m x m row-major
+ * (row k = the device's column k); the hook fills the padding of every input with pad_fill, and outputs of these
+ * shapes come back as n x ldm / m x ldm with the padding as it was left. Outputs and scratch start as NaN between 64
+ * guard doubles on either side; guard_flag = 1 when a guard word changed.
+ *
+ * GPB_TestFitcVector: one kernel per op (FitcVecOp in csrc/fitc_test.h, which lists every op's arrays, ints, extra
+ * and outs). n in 1..2^22 - 1, m in 1..4096, d in 1..3 and cov_type 0..3 for the ops that take coordinates; lens[k]:
+ * the entries of arrays[k] (0 for NULL), out_lens[k] those of outs[k]. The pairs of op pred_corr name prediction
+ * points in 0..np - 1, each at most once, and training points in 0..n - 1. */
+GPBOOST_AMD_EXPORT int GPB_TestFitcVector(int op, int n, int m, int d, int cov_type, double var, double phi,
+                                          double extra, double pad_fill, const double* const* arrays,
+                                          const int64_t* lens, int n_arrays, const int32_t* ints, int64_t ints_len,
+                                          double* const* outs, const int64_t* out_lens, int n_outs, int* guard_flag);
+/* The k-means steps of the inducing-point search on the points X (n x d) and the centres mu (k x d, k <= n <
+ * 2^22, k <= 4096, d in 1..3, all finite); ops: FitcKmeansOp in csrc/fitc_test.h. 0 assign: ints_out = the cluster of
+ * every point (n). 1 means: the new means of the assignment cluster_in (n entries in 0..k - 1) in mu_out, mu being
+ * the old means; scan = 1: the scanning kernel (ints_len = 0), scan = 0: the member-list path, ints_out = cnt, off
+ * (nbk x k each, nbk = ceil(n / 256)), tot (k), base (k + 1), list (n). 2 cmp: ints_out = [any(mu != mu_a), any(mu
+ * != mu_b)]. 3 lloyd: the whole loop of fitc_inducing_points from the seeds mu with at most max_it (1..1000)
+ * iterations; mu_out = the final means, its = the iterations run (no guard bands: the loop owns its buffers).
+ * Integer outputs start as a negative fill between guard words. */
+GPBOOST_AMD_EXPORT int GPB_TestFitcKmeans(int op, int n, int k, int d, const double* X, int64_t x_len, const double* mu,
+                                          const double* mu_a, const double* mu_b, int64_t mu_len,
+                                          const int32_t* cluster_in, int64_t cluster_len, int scan, int max_it,
+                                          double* mu_out, int32_t* ints_out, int64_t ints_len, int* its,
+                                          int* guard_flag);
+/* A FitcSolver on the points X (n x d, n <= 65536), the inducing points Z (m x d, m <= min(n, 1024)) and the response
+ * y (n) runs one stage (FitcStage in csrc/fitc_test.h: 0 Factor, 1 Eval with the gradient, 2 Gram then Eval at the
+ * same parameters, 3 Gram at (var2, phi2) then Eval at (var, phi), 4 Predict at Xp (np x d, np <= 4096) with match
+ * (np entries in -1..n - 1)); then the solver's buffers are copied out as they stand into the non-NULL outs[k]
+ * (FitcStageOut of csrc/fitc_test.h names them; n_outs = 24; matrices with their padding, n x ldm or m x ldm; sums
+ * = Eval's six; mean / var / cov (np, np, np x np column-major) are Predict's, var and cov computed when asked for).
+ * Everything is checked on the host before any device call. */
+GPBOOST_AMD_EXPORT int GPB_TestFitcStages(int stage, int n, int m, int d, int cov_type, double var, double phi,
+                                          double var2, double phi2, const double* X, const double* Z, const double* y,
+                                          int np, const double* Xp, const int32_t* match, double* const* outs,
+                                          const int64_t* out_lens, int n_outs);
 /* The likelihood layer of the Laplace paths (csrc/lik_device.h) on host arrays. No reference counterpart (tests).
  * Everything is checked on the host before any device call, a violation being an error return; outputs and
  * scratch start as NaN between 64 guard doubles on either side; guard_flag = 1 when a guard word changed or a
