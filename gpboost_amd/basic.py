@@ -128,8 +128,10 @@ class GPModel:
         self.likelihood = likelihood
         coords_cm = np.ascontiguousarray(coords.T).reshape(-1)  # column-major, as the reference passes it
         cluster = None
+        self._cluster_map = None
         if cluster_ids is not None:
-            cluster = np.ascontiguousarray(np.asarray(cluster_ids), dtype=np.int32)
+            cluster = self._cluster_codes(cluster_ids, self.num_data, "cluster_ids", training=True)
+        self.num_clusters = 1 if cluster is None else int(np.unique(cluster).size)
         handle = ctypes.c_void_p()
         _safe_call(lib().GPB_CreateREModel(
             ctypes.c_int32(self.num_data),
@@ -147,6 +149,25 @@ class GPModel:
         self.handle = handle
         self.num_group_re = 0
         self._post_init()
+
+    def _cluster_codes(self, ids, n, name, training=False):
+        """Cluster ids as int32. Integers pass as they are; anything else (strings) is numbered from 0 in order of
+        first appearance over the training ids, then over the prediction ids (the reference's Python package does
+        the same, basic.py:4466-4480, 5923-5937), so an id not seen in training gets a number no training id has."""
+        a = np.asarray(ids)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"Incorrect number of data points in '{name}'")
+        if np.issubdtype(a.dtype, np.integer) and self._cluster_map is None:
+            return np.ascontiguousarray(a, dtype=np.int32)
+        if training:
+            self._cluster_map = {}
+        elif self._cluster_map is None:
+            raise ValueError(f"'{name}' must be integers when 'cluster_ids' are integers")
+        cmap = self._cluster_map if training else dict(self._cluster_map)   # prediction ids do not stay
+        out = np.empty(n, dtype=np.int32)
+        for i, v in enumerate(a.tolist()):
+            out[i] = cmap.setdefault(v, len(cmap))
+        return out
 
     def _init_grouped(self, group_data, likelihood, matrix_inversion_method, seed, cluster_ids, weights,
                       gp_coords=None, cov_function="matern", cov_fct_shape=1.5, gp_approx="none",
@@ -738,6 +759,13 @@ class GPModel:
         _safe_call(lib().GPB_GetGroupedLaplaceInfo(self.handle, _ip(dims), _ip(rowptr), _ip(col), _dp(diag), _dp(vals)))
         return rowptr, col[:nnz], diag, vals[:nnz]
 
+    def cluster_info(self):
+        """(clusters, clusters served by the batched dense kernel, clusters with an engine of their own) of a GP
+        model (GPB_GetClusterInfo); GPBOOST_AMD_NO_CLUSTER_BATCH=1 at construction gives every cluster an engine."""
+        out = np.zeros(3, dtype=np.int32)
+        _safe_call(lib().GPB_GetClusterInfo(self.handle, _ip(out)))
+        return tuple(int(v) for v in out)
+
     def set_prediction_data(self, vecchia_pred_type=None, num_neighbors_pred=None, cg_delta_conv_pred=None,
                             nsim_var_pred=None, rank_pred_approx_matrix_lanczos=None, group_data_pred=None,
                             group_rand_coef_data_pred=None, gp_coords_pred=None, gp_rand_coef_data_pred=None,
@@ -745,12 +773,16 @@ class GPModel:
         """Prediction settings and data (reference basic.py:6095-6190, GPB_SetPredictionData): the data is
         saved in the model for predict(use_saved_data=True) (gp_coords_pred / X_pred for GP models,
         group_data_pred for grouped random effects)."""
-        if gp_rand_coef_data_pred is not None or cluster_ids_pred is not None or (
+        clusters_ok = getattr(self, "num_clusters", 1) > 1 and not getattr(self, "num_group_re", 0)
+        if gp_rand_coef_data_pred is not None or (cluster_ids_pred is not None and not clusters_ok) or (
                 group_rand_coef_data_pred is not None and not getattr(self, "num_group_rand_coef", 0)):
             raise GPBoostError("set_prediction_data: GP random coefficients, grouped random coefficients of a model "
                                "without them and clusters are not supported by gpboost_amd")
         num_data_pred = 0
-        gbuf = xcol = xpc = slc = None
+        gbuf = xcol = xpc = slc = cl = None
+        if cluster_ids_pred is not None:
+            num_data_pred = len(cluster_ids_pred)
+            cl = self._cluster_codes(cluster_ids_pred, num_data_pred, "cluster_ids_pred")
         if group_data_pred is not None:
             g = np.asarray(group_data_pred)
             if g.ndim == 1:
@@ -782,7 +814,8 @@ class GPModel:
             num_data_pred = Xp.shape[0]
             xpc = np.ascontiguousarray(Xp.T).reshape(-1)
         _safe_call(lib().GPB_SetPredictionData(
-            self.handle, ctypes.c_int32(num_data_pred), None, gbuf, _dp(slc) if slc is not None else None,
+            self.handle, ctypes.c_int32(num_data_pred), _ip(cl) if cl is not None else None, gbuf,
+            _dp(slc) if slc is not None else None,
             _dp(xcol) if xcol is not None else None,
             None, _dp(xpc) if xpc is not None else None, c_str(vecchia_pred_type),
             ctypes.c_int(int(num_neighbors_pred) if num_neighbors_pred is not None else -1),
@@ -828,10 +861,14 @@ class GPModel:
                                          group_rand_coef_data_pred)
         if vecchia_pred_type is not None or num_neighbors_pred is not None:
             self.set_prediction_data(vecchia_pred_type=vecchia_pred_type, num_neighbors_pred=num_neighbors_pred)
+        clustered = getattr(self, "num_clusters", 1) > 1
         if any(v is not None for v in (group_data_pred, group_rand_coef_data_pred, gp_rand_coef_data_pred,
-                                       cluster_ids_pred)):
+                                       None if clustered else cluster_ids_pred)):
             raise GPBoostError("predictions with grouped random effects, random coefficients or clusters are not "
                                "supported by gpboost_amd for GP models")
+        if clustered and cluster_ids_pred is None:
+            raise GPBoostError("'cluster_ids_pred' is missing: a model with several clusters (cluster_ids) needs the "
+                               "cluster of every prediction point")
         xpc = None
         if X_pred is not None:
             Xp = np.asarray(X_pred, dtype=np.float64)
@@ -849,6 +886,7 @@ class GPModel:
             raise ValueError("'gp_coords_pred' contains NaN or Inf")
         n_pred = xp.shape[0]
         xcol = np.ascontiguousarray(xp.T.reshape(-1))   # column-major, as the reference passes it
+        cl = self._cluster_codes(cluster_ids_pred, n_pred, "cluster_ids_pred") if clustered else None
         yv = self._check_y(y)
         if offset is not None:
             fixed_effects = offset if fixed_effects is None else np.asarray(fixed_effects) + np.asarray(offset)
@@ -863,7 +901,7 @@ class GPModel:
         _safe_call(lib().GPB_PredictREModel(
             self.handle, _dp(yv) if yv is not None else None, ctypes.c_int32(n_pred), _dp(out),
             ctypes.c_bool(bool(predict_cov_mat)), ctypes.c_bool(bool(predict_var)),
-            ctypes.c_bool(bool(predict_response)), None, None, None, _dp(xcol), None,
+            ctypes.c_bool(bool(predict_response)), _ip(cl) if cl is not None else None, None, None, _dp(xcol), None,
             _dp(cp) if cp is not None else None, _dp(xpc) if xpc is not None else None, ctypes.c_bool(bool(use_saved_data)),
             _dp(fe) if fe is not None else None, _dp(fep) if fep is not None else None))
         mu = out[:n_pred].copy()

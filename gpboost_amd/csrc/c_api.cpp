@@ -50,6 +50,7 @@ struct SavedPred {
   std::vector<double> covariates;    // column-major num_data_pred x p
   std::vector<char> re_group;        // num_data_pred x K NUL-terminated level strings, effect-major
   std::vector<double> re_group_rand_coef;   // column-major num_data_pred x R (grouped models with random slopes)
+  std::vector<int32_t> cluster_ids;         // num_data_pred (GP models with several clusters)
 };
 std::mutex g_saved_mu;
 std::unordered_map<const void*, SavedPred> g_saved;
@@ -167,9 +168,12 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
     gpb_amd::Fatal("cluster_ids together with grouped random coefficients (group_rand_coef_data) are not supported "
                    "by gpboost_amd");
   if (has_weights) gpb_amd::Fatal("'weights' are not supported by gpboost_amd");
-  if (cluster_ids_data != nullptr) {
+  // several clusters: GP models only (REModelAMD, re_model_cluster.cpp)
+  if (cluster_ids_data != nullptr && (num_re_group > 0 || re_group_data != nullptr)) {
     for (int32_t i = 1; i < num_data; ++i)
-      if (cluster_ids_data[i] != cluster_ids_data[0]) gpb_amd::Fatal("multiple clusters (cluster_ids) are out of scope for gpboost_amd");
+      if (cluster_ids_data[i] != cluster_ids_data[0])
+        gpb_amd::Fatal("multiple clusters (cluster_ids) with grouped random effects (group_data) are out of scope for "
+                       "gpboost_amd");
   }
   if (seed < 0) gpb_amd::Fatal("seed must be >= 0");
   if (num_re_group > 0 || re_group_data != nullptr) {   // grouped random effects (GroupedModel)
@@ -229,7 +233,7 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
   cfg.num_ind_points = num_ind_points;
   cfg.cover_tree_radius = cover_tree_radius;
   cfg.ind_points_selection = str_or(ind_points_selection, "kmeans++");
-  *out = new REModelAMD(cfg, gp_coords_data);
+  *out = new REModelAMD(cfg, gp_coords_data, cluster_ids_data);
   API_END();
 }
 
@@ -383,13 +387,16 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
   (void)rank_pred_approx_matrix_lanczos;
   if (handle == nullptr) gpb_amd::Fatal("REModelHandle is NULL");
   GroupedModel* g = as_grouped(handle);
-  if (cluster_ids_data_pred != nullptr || gp_rand_coef_data_pred != nullptr ||
+  // cluster ids: saved for GP models with several clusters only
+  const bool clusters_ok = cluster_ids_data_pred != nullptr && g == nullptr && model(handle)->clustered();
+  if ((cluster_ids_data_pred != nullptr && !clusters_ok) || gp_rand_coef_data_pred != nullptr ||
       (re_group_rand_coef_data_pred != nullptr && g == nullptr))
     gpb_amd::Fatal("GPB_SetPredictionData: clusters and random coefficients are not supported by gpboost_amd");
   if (re_group_rand_coef_data_pred != nullptr && !g->has_slopes())
     gpb_amd::Fatal("group_rand_coef_data_pred is given but the model has no grouped random coefficients");
   const bool has_data = re_group_data_pred != nullptr || gp_coords_data_pred != nullptr ||
-                        covariate_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr;
+                        covariate_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr ||
+                        cluster_ids_data_pred != nullptr;
   if (has_data) {
     if (num_data_pred <= 0) gpb_amd::Fatal("num_data_pred must be > 0 when prediction data is given");   // CHECK :3075
     if (g != nullptr && gp_coords_data_pred != nullptr && !g->has_gp())
@@ -409,8 +416,11 @@ int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int
       if (covariate_data_pred == nullptr) sp.covariates.clear();
       if (re_group_data_pred == nullptr) sp.re_group.clear();
       if (re_group_rand_coef_data_pred == nullptr) sp.re_group_rand_coef.clear();
+      if (cluster_ids_data_pred == nullptr) sp.cluster_ids.clear();
     }
     sp.num_data_pred = num_data_pred;
+    if (cluster_ids_data_pred != nullptr)
+      sp.cluster_ids.assign(cluster_ids_data_pred, cluster_ids_data_pred + num_data_pred);
     if (gp_coords_data_pred != nullptr) {
       const size_t cnt = (size_t)num_data_pred * (g != nullptr ? g->gp_dim() : model(handle)->config().d);
       sp.gp_coords.assign(gp_coords_data_pred, gp_coords_data_pred + cnt);
@@ -456,7 +466,7 @@ int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_d
     if (num_data_pred > 0 && num_data_pred != saved.num_data_pred)
       gpb_amd::Fatal("num_data_pred (%d) differs from the saved prediction data (%d)", num_data_pred, saved.num_data_pred);
     num_data_pred = saved.num_data_pred;
-    cluster_ids_data_pred = nullptr;
+    cluster_ids_data_pred = saved.cluster_ids.empty() ? nullptr : saved.cluster_ids.data();
     re_group_rand_coef_data_pred = saved.re_group_rand_coef.empty() ? nullptr : saved.re_group_rand_coef.data();
     gp_rand_coef_data_pred = nullptr;
     re_group_data_pred = saved.re_group.empty() ? nullptr : saved.re_group.data();
@@ -487,11 +497,13 @@ int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_d
                predict_response, fixed_effects, fixed_effects_pred, out_predict, re_group_rand_coef_data_pred);
     return 0;
   }
-  if (cluster_ids_data_pred != nullptr || re_group_data_pred != nullptr || re_group_rand_coef_data_pred != nullptr ||
-      gp_rand_coef_data_pred != nullptr)
+  REModelAMD* m = model(handle);
+  if ((cluster_ids_data_pred != nullptr && !m->clustered()) || re_group_data_pred != nullptr ||
+      re_group_rand_coef_data_pred != nullptr || gp_rand_coef_data_pred != nullptr)
     gpb_amd::Fatal("predictions with clusters, grouped random effects or random coefficients are not "
                    "supported by gpboost_amd");
-  REModelAMD* m = model(handle);
+  if (m->clustered() && covariate_data_pred != nullptr)
+    m->RefuseClusters("linear regression covariates (X_pred)");
   std::vector<double> r;
   const double* y = y_data;
   if (m->has_covariates()) {   // y - X beta - offset (SetYCalcCovCalcYAuxForPred, re_model_template.h:3386-3410)
@@ -517,6 +529,11 @@ int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_d
     if (m->has_covariates()) m->AddLinearPredictor(covariate_data_pred, num_data_pred, mean_add.data());
     if (fixed_effects_pred != nullptr)
       for (int i = 0; i < num_data_pred; ++i) mean_add[i] += fixed_effects_pred[i];
+  }
+  if (m->clustered()) {   // a missing cluster_ids_data_pred fails there, naming it
+    m->PredictClusters(y, num_data_pred, gp_coords_data_pred, cluster_ids_data_pred, cov_pars, predict_cov_mat,
+                       predict_var, predict_response, out_predict, mean_add.empty() ? nullptr : mean_add.data());
+    return 0;
   }
   m->Predict(y, num_data_pred, gp_coords_data_pred, cov_pars, predict_cov_mat, predict_var, predict_response,
              out_predict, mean_add.empty() ? nullptr : mean_add.data());
@@ -634,6 +651,7 @@ int GPB_OptimCovParBoosting(REModelHandle handle, const double* y_data, const do
   if (as_grouped(handle) != nullptr)
     gpb_amd::Fatal("the GPBoost-algorithm covariance update (GPB_OptimCovParBoosting) is not supported for grouped "
                    "random effects models by gpboost_amd");
+  model(handle)->RefuseClusters("the GPBoost-algorithm covariance update (GPB_OptimCovParBoosting)");
   model(handle)->OptimCovPar(y_data, fixed_effects, called_in_GPBoost_algorithm, reuse_learning_rates_from_previous_call);
   API_END();
 }
@@ -1121,6 +1139,22 @@ int GPB_TestFitcStages(int stage, int n, int m, int d, int cov_type, double var,
   API_BEGIN();
   gpb_amd::test_fitc_stages(stage, n, m, d, cov_type, var, phi, var2, phi2, X, Z, y, np, Xp, match, outs, out_lens,
                             n_outs);
+  API_END();
+}
+
+int GPB_TestDenseBatch(int cov_type, int C, int d, const int32_t* ptr, int64_t ptr_len, const double* X, int64_t x_len,
+                       const double* y, int64_t y_len, double var, double phi, int want_grad, double* sums,
+                       int64_t sums_len, double* u, int64_t u_len, int32_t* info, int64_t info_len) {
+  API_BEGIN();
+  gpb_amd::test_dense_batch(cov_type, C, d, ptr, ptr_len, X, x_len, y, y_len, var, phi, want_grad, sums, sums_len, u,
+                            u_len, info, info_len);
+  API_END();
+}
+
+int GPB_GetClusterInfo(REModelHandle handle, int32_t* out) {
+  API_BEGIN();
+  if (out == nullptr) gpb_amd::Fatal("out is NULL");
+  model(handle)->GetClusterInfo(out);
   API_END();
 }
 

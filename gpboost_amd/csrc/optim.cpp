@@ -424,8 +424,15 @@ double REModelAMD::InitialRangeTrafo() const {
   // FITC: the inducing points' component (re_comps_ip_, re_model_template.h:4474-4476), the draws
   // continuing the generator after the inducing-point selection; full_scale_vecchia: the Vecchia component
   // (all points in the model order, :4452-4456) with the generator after the shuffle and the selection
-  const std::vector<double>& X = fitc_ ? fitc_->inducing_points() : coords_vo_;
   std::mt19937 rng(cfg_.seed);
+  if (clustered()) {   // the first cluster's component (re_comps_[unique_clusters_[0]], re_model_template.h:4452-4476)
+    const int d = cfg_.d, n0 = cl_.size(0);
+    std::vector<double> X0((size_t)n0 * d);
+    for (int i = 0; i < n0; ++i)
+      for (int q = 0; q < d; ++q) X0[(size_t)i * d + q] = coords_[(size_t)cl_.rows[i] * d + q];
+    return init_range_trafo(X0, d, cfg_.cov_type, rng);
+  }
+  const std::vector<double>& X = fitc_ ? fitc_->inducing_points() : coords_vo_;
   if ((int)(X.size() / cfg_.d) > 1000) {
     if (fitc_ || vif_) rng = fitc_rng_;   // full_scale_vecchia: after the shuffle and the inducing points
     if (vecchia_ && cfg_.vecchia_ordering == "random") {   // the ordering shuffle of the n observations
@@ -762,6 +769,8 @@ std::vector<double> REModelAMD::FisherTrafo(const double* trafo) {
 void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool called_in_boosting, bool reuse_lr) {
   // REModel::OptimCovPar (re_model.cpp:339-401) -> OptimLinRegrCoefCovPar without covariates
   // (re_model_template.h:846-1700) -> OptimExternal "lbfgs" (optim_utils.h:561-706)
+  if (called_in_boosting) RefuseClusters("the GPBoost-algorithm covariance update (GPB_OptimCovParBoosting)");
+  if (isettings_.optimizer == "fisher_scoring") RefuseClusters("optimizer_cov = 'fisher_scoring'");
   UseDevice();
   const int n = cfg_.n;
   if (reuse_lr && !called_in_boosting)
@@ -1000,6 +1009,7 @@ void REModelAMD::InitializeOptimizerNames() {
 }
 
 void REModelAMD::OptimLinRegrCoefCovPar(const double* y, const double* X, int p, const double* fixed_effects) {
+  if (X != nullptr && p > 0) RefuseClusters("linear regression covariates (X)");
   if (!est_idx_.empty() && X != nullptr && p > 0)
     Fatal("estimate_cov_par_index (fixing covariance parameters) with linear regression covariates is not supported by "
           "gpboost_amd");
@@ -1145,6 +1155,7 @@ void REModelAMD::StdDevCovPars(const double* orig, double* sd) {
   // include_error_var = true: with Sigma^-1 = Psi^-1 / sigma^2 and dSigma_k on the original scale
   // (sigma^2: I; sigma1^2: the correlation matrix; rho: sigma1^2 dcorr/drho)
   //   FI_00 = tr(Sigma^-2) / 2, FI_0k = tr(Sigma^-2 dSigma_k) / 2, FI_kl = tr(Sigma^-1 dSigma_k Sigma^-1 dSigma_l) / 2
+  RefuseClusters("standard deviations of the covariance parameters (std_err)");
   if (cfg_.latent || vif_)
     Fatal("standard deviations of covariance parameters are supported by gpboost_amd only for gp_approx = 'none', "
           "'vecchia' and 'fitc' with the Gaussian likelihood");

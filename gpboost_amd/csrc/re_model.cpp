@@ -76,8 +76,14 @@ double range_back(int cov_type, double phi) {
   }
 }
 
-REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor) : cfg_(cfg) {
+REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor, const int32_t* cluster_ids,
+                       std::mt19937* order_rng)
+    : cfg_(cfg) {
+  cfg_in_ = cfg;
   if (cfg_.n <= 0) Fatal("num_data must be > 0");
+  bool several = false;   // more than one distinct id: independent realisations (SetUpClusters)
+  if (cluster_ids != nullptr)
+    for (int i = 1; i < cfg_.n && !several; ++i) several = cluster_ids[i] != cluster_ids[0];
   if (cfg_.d <= 0 || cfg_.d > 3) Fatal("dim_gp_coords = %d not supported (1..3)", cfg_.d);
   cfg_.cov_type = parse_cov(cfg_.cov_fct, cfg_.shape);
   // likelihood and approximation (re_model_template.h:207-211, 563; likelihoods.h:240-257)
@@ -130,6 +136,16 @@ REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor) : 
     Fatal("matrix_inversion_method '%s' is not supported for likelihood 'gaussian' in gpboost_amd (supported: cholesky)", mim.c_str());
   if (cfg_.latent && (cfg_.lik == kLikGaussian || cfg_.lik == kLikGamma))
     aux_pars_ = {1.};   // likelihoods.h:241 (error_variance), :181-186 (gamma shape)
+  if (several) {
+    if (cfg_.lik != kLikGaussian)
+      Fatal("likelihood = '%s' with several clusters (cluster_ids) is not supported by gpboost_amd (supported: "
+            "gaussian)", cfg_.likelihood.c_str());
+    if (cfg_.gp_approx != "none" && cfg_.gp_approx != "vecchia")
+      Fatal("gp_approx = '%s' with several clusters (cluster_ids) is not supported by gpboost_amd (supported: none, "
+            "vecchia)", cfg_.gp_approx.c_str());
+    if (vecchia_ && cfg_.vecchia_ordering != "random" && cfg_.vecchia_ordering != "none")
+      Fatal("vecchia_ordering '%s' is not supported (supported: none, random)", cfg_.vecchia_ordering.c_str());
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     Fatal("no HIP device visible: gpboost_amd has no CPU fallback");
@@ -159,10 +175,22 @@ REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor) : 
   row_end_ = n;
   num_neighbors_pred_ = 2 * cfg_.num_neighbors;   // re_model_template.h:299
   nu_ = n;
+  if (several) {   // the engines live in the clusters; this object keeps the partition and the optimizer state
+    SetUpClusters(cluster_ids);
+    d_sums_.alloc(16);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    return;
+  }
   if (vecchia_) {
-    perm_ = vecchia_order(n, cfg_.seed, cfg_.vecchia_ordering == "random");
     if (cfg_.vecchia_ordering != "random" && cfg_.vecchia_ordering != "none")
       Fatal("vecchia_ordering '%s' is not supported (supported: none, random)", cfg_.vecchia_ordering.c_str());
+    if (order_rng != nullptr && cfg_.vecchia_ordering == "random") {
+      perm_.resize(n);
+      std::iota(perm_.begin(), perm_.end(), 0);
+      std::shuffle(perm_.begin(), perm_.end(), *order_rng);
+    } else {
+      perm_ = vecchia_order(n, cfg_.seed, cfg_.vecchia_ordering == "random");
+    }
     coords_vo_.resize((size_t)n * d);
     for (int i = 0; i < n; ++i)
       for (int q = 0; q < d; ++q) coords_vo_[(size_t)i * d + q] = coords_[(size_t)perm_[i] * d + q];
@@ -277,6 +305,7 @@ std::mt19937* REModelAMD::RefDraws() {
 }
 
 void REModelAMD::EnsureStructure() {
+  if (clustered()) return;   // every engine builds its own
   if (vecchia_ && !structure_built_) {
     BuildVecchiaStructure();
     if (cfg_.latent) {
@@ -302,6 +331,8 @@ void REModelAMD::SetAuxPars(const double* aux) {
 REModelAMD::~REModelAMD() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize(stream_);
+  cl_engines_.clear();
+  cl_batch_.reset();
   dense_.reset();
   dense_lap_.reset();
   vfisher_.reset();
@@ -362,6 +393,7 @@ void REModelAMD::ApplyPartition(int rank, int world) {
 
 void REModelAMD::SetDistributed(int rank, int world, const ncclUniqueId& id, bool use_comm) {
   if (world < 1 || rank < 0 || rank >= world) Fatal("invalid rank %d / world_size %d", rank, world);
+  RefuseClusters("multi-rank models (GPB_SetDistributed)");
   UseDevice();
   latent_.reset();   // holds a pointer to the collective
   coll_.reset();
@@ -376,6 +408,7 @@ void REModelAMD::SetDistributed(int rank, int world, const ncclUniqueId& id, boo
 
 void REModelAMD::SetDistributedHost(int rank, int world, HostAllReduceFn fn, void* user) {
   if (fn == nullptr) Fatal("SetDistributedHost: the all-reduce function is NULL");
+  RefuseClusters("multi-rank models (GPB_SetDistributedHostReduce)");
   UseDevice();
   latent_.reset();
   coll_.reset();
@@ -454,6 +487,8 @@ std::vector<double> gauss_hermite_adaptive(int order) {
 void REModelAMD::Predict(const double* y, int n_pred, const double* coords_pred, const double* cov_pars,
                          bool predict_cov_mat, bool predict_var, bool predict_response, double* out,
                          const double* mean_add) {
+  if (clustered())
+    Fatal("cluster_ids_pred (cluster_ids_data_pred) must be provided for predictions of a model with several clusters");
   if (vif_) {
     PredictVif(y, n_pred, coords_pred, cov_pars, predict_cov_mat, predict_var, predict_response, out, mean_add);
     return;
@@ -1281,6 +1316,10 @@ void REModelAMD::TransformCovPars(const double* orig, double* trafo) const {
 void REModelAMD::SetY(const double* y) {
   // re_model_template.h:5689-5726: y is copied (and permuted into Vecchia order)
   UseDevice();
+  if (clustered()) {
+    SetYClusters(y);
+    return;
+  }
   const int n = cfg_.n;
   std::vector<double> yv(n);
   if (vecchia_ || vif_) for (int i = 0; i < n; ++i) yv[i] = y[perm_[i]];
@@ -1458,6 +1497,7 @@ void REModelAMD::EvalVecchia(const double* trafo, double* sums) {
 }
 
 void REModelAMD::EvalVecchiaPartials(const double* cov_pars_orig, int r0, int r1, double* sums) {
+  RefuseClusters("row-range partial sums (GPB_EvalVecchiaPartials)");
   if (!vecchia_) Fatal("model does not use the Vecchia approximation");
   if (cfg_.latent) Fatal("row-range partial sums exist only for the exact Gaussian Vecchia likelihood");
   if (!y_set_) Fatal("response variable y has not been set");
@@ -1580,10 +1620,9 @@ EvalResult REModelAMD::Eval(const double* cov_pars_orig, bool want_grad, int pro
 EvalResult REModelAMD::EvalTrafo(const double* trafo, bool want_grad, int profile, bool fatal_on_nan) {
   if (!y_set_) Fatal("response variable y has not been set");
   UseDevice();
-  EnsureStructure();
   double sums[kVecchiaSums];
-  if (vecchia_) EvalVecchia(trafo, sums);
-  else EvalExactGaussian(trafo, want_grad, sums);
+  if (clustered()) EvalClusters(trafo, want_grad, sums);
+  else RawSums(trafo, want_grad, sums);
   if (fatal_on_nan && (!std::isfinite(sums[0]) || !std::isfinite(sums[1])))
     Fatal("NaN or Inf occurred in the negative log-likelihood (non-positive-definite covariance?)");
   EvalResult res;
@@ -1595,6 +1634,7 @@ EvalResult REModelAMD::EvalTrafo(const double* trafo, bool want_grad, int profil
 }
 
 void REModelAMD::GetVecchiaStructure(int* perm, int* nbr) const {
+  RefuseClusters("GPB_GetVecchiaStructure");
   if (!vecchia_) Fatal("model does not use the Vecchia approximation");
   if (has_dup()) Fatal("GetVecchiaStructure is not available for latent models with repeated coordinates");
   if (world_ > 1) Fatal("GetVecchiaStructure is only available on single-rank models");
@@ -1629,6 +1669,7 @@ void REModelAMD::GetLatentVecchiaFactor(const double* cov_pars_orig, double* Din
 }
 
 void REModelAMD::GetVecchiaFactor(const double* cov_pars_orig, double* Dinv, double* Bvals) {
+  RefuseClusters("GPB_GetVecchiaFactor");
   if (!vecchia_) Fatal("model does not use the Vecchia approximation");
   if (cfg_.latent) Fatal("latent Vecchia model: use GPB_GetLatentVecchiaFactor");
   if (world_ > 1) Fatal("GetVecchiaFactor is only available on single-rank models");

@@ -16,9 +16,11 @@
 #include <string>
 #include <vector>
 
+#include "cluster_partition.h"
 #include "collective.h"
 #include "common.h"
 #include "dense.h"
+#include "dense_batch.h"
 #include "fitc.h"
 #include "dense_laplace.h"
 #include "fitc_laplace.h"
@@ -80,8 +82,25 @@ struct EvalResult {
 
 class REModelAMD {
  public:
-  REModelAMD(const ModelConfig& cfg, const double* coords_colmajor);
+  // cluster_ids (nullable, n): more than one distinct value makes independent realisations of the process that
+  // share the covariance parameters (re_model_cluster.cpp); one distinct value is the model without ids.
+  // order_rng (nullable): the generator a random Vecchia ordering draws from instead of a fresh mt19937(seed)
+  // (the per-cluster engines of a clustered model continue their parent's generator in cluster order).
+  REModelAMD(const ModelConfig& cfg, const double* coords_colmajor, const int32_t* cluster_ids = nullptr,
+             std::mt19937* order_rng = nullptr);
   ~REModelAMD();
+
+  // several independent realisations (cluster_ids)
+  bool clustered() const { return cl_.num_clusters() > 1; }
+  // fails, naming the option, when the model has several clusters
+  void RefuseClusters(const char* option) const;
+  // GPB_PredictREModel of a clustered model: every prediction point uses the training data of its own cluster
+  // (re_model_template.h:3292-3420); an id not seen in training gets the prior. Arguments as Predict.
+  void PredictClusters(const double* y, int n_pred, const double* coords_pred, const int32_t* cluster_ids_pred,
+                       const double* cov_pars, bool predict_cov_mat, bool predict_var, bool predict_response,
+                       double* out, const double* mean_add);
+  // [clusters, clusters in the batched kernel, per-cluster engines] (EXTENSION: GPB_GetClusterInfo)
+  void GetClusterInfo(int32_t* out) const;
 
   int num_cov_pars() const { return cfg_.latent ? 2 : 3; }
   int num_aux_pars() const { return (int)aux_pars_.size(); }
@@ -215,7 +234,7 @@ class REModelAMD {
   const std::string& optimizer_coef() const { return optimizer_coef_; }
   std::string cg_preconditioner_type() const;
   // CanCalculateStandardErrorsCovPars (re_model_template.h:1630-1632)
-  bool CanCalculateStandardErrorsCovPars() const { return !cfg_.latent && !vif_; }
+  bool CanCalculateStandardErrorsCovPars() const { return !cfg_.latent && !vif_ && !clustered(); }
   // GLS evaluation on the transformed scale (optimizer): beta from the Gram of [X | y], then the
   // profiled L-BFGS unit on the residuals. beta_out (nullable) receives the coefficients.
   EvalResult EvalTrafoWls(const double* trafo, bool want_grad, bool fatal_on_nan, std::vector<double>* beta_out);
@@ -314,6 +333,21 @@ class REModelAMD {
 
   void EnsureStructure();
   void UseDevice() const;
+
+  // ---- clusters: the row partition, one batched launch for the small clusters and one engine (a single-cluster
+  // REModelAMD on the cluster's rows) for every other one; EvalTrafo adds their six sums before combine_partials
+  void SetUpClusters(const int32_t* cluster_ids);
+  void SetYClusters(const double* y);
+  void RawSums(const double* trafo, bool want_grad, double* sums);        // one realisation (this model's engine)
+  void EvalClusters(const double* trafo, bool want_grad, double* sums);   // batch, then the engines in cluster order
+  std::unique_ptr<REModelAMD> ClusterEngine(int c, std::mt19937* order_rng) const;
+  ModelConfig cfg_in_;                                 // as given (the engines' configuration)
+  ClusterPartition cl_;                                // empty: one realisation
+  std::unique_ptr<DenseBatch> cl_batch_;
+  std::vector<int> cl_batch_rows_;                     // observation of every batch row (cluster-major)
+  std::vector<int> cl_engine_of_;                      // cluster -> index into cl_engines_, or -1 (batched)
+  std::vector<std::unique_ptr<REModelAMD>> cl_engines_;
+  std::vector<double> cl_y_;                           // the likelihood's response, original order
   EvalResult EvalLatent(const double* cov_pars_orig, bool want_grad);
 
   ModelConfig cfg_;

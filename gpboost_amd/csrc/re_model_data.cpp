@@ -58,6 +58,7 @@ void REModelAMD::CalcGradientF(double* y, const double* fixed_effects, bool calc
   // (deterministic, so equal to the existing one). Latent: calc_cov_factor re-runs the mode finding
   // from the current mode (CalcModePostRandEffCalcMLL, no InitializeModeAvec); without it the mode
   // of the last evaluation (e.g. OptimCovPar's last objective call) is used as it stands.
+  RefuseClusters("the gradient wrt the fixed effects (GPB_CalcGradientF)");
   UseDevice();
   if (world_ > 1) Fatal("CalcGradientF is only available on single-rank models");
   if (y == nullptr) Fatal("the output array 'y' is NULL");
@@ -267,6 +268,7 @@ void REModelAMD::PredictTrainingDataRandomEffects(const double* cov_pars, const 
                                                   const double* fixed_effects, bool calc_var) {
   // re_model.cpp PredictTrainingDataRandomEffects: cov_pars on the original scale (NULL: the
   // estimated / last ones); y NULL: the response set before
+  RefuseClusters("predict_training_data_random_effects (GPB_PredictREModelTrainingDataRandomEffects)");
   UseDevice();
   if (world_ > 1) Fatal("PredictTrainingDataRandomEffects is only available on single-rank models");
   const int n = cfg_.n;
@@ -340,6 +342,9 @@ void REModelAMD::PsiInvVecchia(const double* trafo, double* yaux, double* diag) 
 
 void REModelAMD::SetLikelihood(const std::string& likelihood) {
   if (likelihood == cfg_.likelihood) return;
+  if (clustered())
+    Fatal("likelihood = '%s' with several clusters (cluster_ids) is not supported by gpboost_amd (supported: gaussian)",
+          likelihood.c_str());
   if (cov_pars_initialized_ && num_it_ > 0)   // re_model.cpp:142-147
     Fatal("Cannot change likelihood after a model has been estimated ");
   ModelConfig c = cfg_;

@@ -68,7 +68,14 @@ GPBOOST_AMD_EXPORT int LGBM_RegisterLogCallback(void (*callback)(const char*));
  * ind_effect_group_rand_coef the grouping variable of every slope, counted from 1. The components (one variance
  * each) are the intercepts, then the slopes, minus the intercept dropped by drop_intercept_group_rand_effect
  * (num_re_group entries, nullable; at most one, of a variable that has a slope). Not with gp_coords or several
- * clusters. */
+ * clusters.
+ * cluster_ids_data (nullable, num_data) with more than one distinct value: independent realisations of the GP that
+ * share the covariance parameters (clusters in order of first appearance, re_model_template.h:6211-6243), for GP
+ * models with likelihood "gaussian" and gp_approx "none" or "vecchia"; clusters of at most 64 points are evaluated
+ * by one launch of a batched kernel (GPBOOST_AMD_NO_CLUSTER_BATCH=1: one engine per cluster). Such a model refuses,
+ * naming the option: other likelihoods and approximations, covariates, optimizer "fisher_scoring", standard
+ * deviations of the covariance parameters, GPB_PredictREModelTrainingDataRandomEffects, GPB_OptimCovParBoosting,
+ * GPB_CalcGradientF, GPB_SetDistributed*, grouped random effects. One distinct value: the model without ids. */
 GPBOOST_AMD_EXPORT int GPB_CreateREModel(int32_t num_data,
     const int32_t* cluster_ids_data,
     const char* re_group_data,
@@ -673,6 +680,21 @@ GPBOOST_AMD_EXPORT int GPB_TestFitcStages(int stage, int n, int m, int d, int co
                                           double var2, double phi2, const double* X, const double* Z, const double* y,
                                           int np, const double* Xp, const int32_t* match, double* const* outs,
                                           const int64_t* out_lens, int n_outs);
+/* The batched dense kernel of models with several clusters (csrc/dense_batch.hip) on caller-given clusters. No
+ * reference counterpart (tests). C clusters, cluster c holding the rows ptr[c] .. ptr[c + 1] - 1 (ptr: C + 1 entries
+ * from 0, 1 .. 64 rows per cluster) of X (N x d row-major, d in 1..3) and y (N); cov_type 0..3, var and phi > 0 on
+ * the transformed scale. sums (C x 6): [log|Psi_c|, y_c' Psi_c^-1 y_c, -1/2 u' dPsi/dlog var u, -1/2 u' dPsi/dlog phi
+ * u, tr(Psi^-1 dPsi/dlog var), tr(Psi^-1 dPsi/dlog phi)] with Psi_c = var corr + I and u = Psi_c^-1 y_c (the last four
+ * 0 without want_grad); u (N, nullable); info (C): 1 for a cluster with a pivot that is not positive and finite (its
+ * sums and u are NaN), else 0. Every extent is checked on the host before the launch. */
+GPBOOST_AMD_EXPORT int GPB_TestDenseBatch(int cov_type, int C, int d, const int32_t* ptr, int64_t ptr_len,
+                                          const double* X, int64_t x_len, const double* y, int64_t y_len, double var,
+                                          double phi, int want_grad, double* sums, int64_t sums_len, double* u,
+                                          int64_t u_len, int32_t* info, int64_t info_len);
+/* EXTENSION (no reference counterpart): out = [clusters, clusters served by the batched kernel, clusters with an
+ * engine of their own] of a GP model (1, 0, 0 without several clusters). GPBOOST_AMD_NO_CLUSTER_BATCH=1, read when
+ * the model is created, gives every cluster an engine. */
+GPBOOST_AMD_EXPORT int GPB_GetClusterInfo(REModelHandle handle, int32_t* out);
 /* The likelihood layer of the Laplace paths (csrc/lik_device.h) on host arrays. No reference counterpart (tests).
  * Everything is checked on the host before any device call, a violation being an error return; outputs and
  * scratch start as NaN between 64 guard doubles on either side; guard_flag = 1 when a guard word changed or a
@@ -802,7 +824,8 @@ GPBOOST_AMD_EXPORT int GPB_GetVifFactor(REModelHandle handle, const double* cov_
  * default 2 * num_neighbors, :299) and nsim_var_pred (<= 0: unchanged; default 1000, :5374: draws of
  * the latent models' predictive-variance simulation). Prediction data must be NULL / 0 (pass it to
  * GPB_PredictREModel); cg_delta_conv_pred and rank_pred_approx_matrix_lanczos are accepted and
- * ignored (the Vecchia-Laplace draws use the model's cg_delta_conv, likelihoods.h:12043-12053). */
+ * ignored (the Vecchia-Laplace draws use the model's cg_delta_conv, likelihoods.h:12043-12053).
+ * cluster_ids_data_pred (num_data_pred) is saved for GP models with several clusters and refused otherwise. */
 GPBOOST_AMD_EXPORT int GPB_SetPredictionData(REModelHandle handle,
     int32_t num_data_pred,
     const int32_t* cluster_ids_data_pred,
@@ -836,6 +859,10 @@ GPBOOST_AMD_EXPORT int GPB_SetPredictionData(REModelHandle handle,
  * reference returns them in the order of its sparse factor's AMD permutation (an artefact of its
  * SimplicialLLT; the means are in prediction-point order on both sides). Unsupported inputs (clusters,
  * GP random coefficients, full_scale_vecchia, num_neighbors_pred > 64) return -1 with a message.
+ * GP models with several clusters need cluster_ids_data_pred and gp_coords_data_pred: every prediction point uses
+ * the training data of its own cluster, an id without training data gets mean 0 (or fixed_effects_pred) and the
+ * prior covariance (plus the nugget with predict_response), and covariances between clusters are 0
+ * (re_model_template.h:3292-3420); a call without the ids fails with a message naming them.
  * Grouped models with random slopes need re_group_rand_coef_data_pred (column-major num_data_pred x
  * num_re_group_rand_coef; also accepted and saved by GPB_SetPredictionData): the values of Z at the prediction
  * points. GPB_PredictREModelTrainingDataRandomEffects returns one block of num_data means per component (a
