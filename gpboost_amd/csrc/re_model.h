@@ -6,6 +6,9 @@
 // Host code keeps configuration, the Vecchia structure (built once) and scalar
 // assembly; every O(n) / O(n m^2) / O(n^3) step runs in HIP kernels on the model's
 // stream. Device buffers are allocated once at construction / SetY and reused.
+// Sources: re_model.cpp (construction, structure, SetY, the evaluations), re_model_predict.cpp (predictions at
+// new coordinates), re_model_data.cpp (covariates, stored data, likelihood switching, training-data predictions),
+// re_model_cluster.cpp (cluster_ids), optim.cpp (estimation).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,6 +81,22 @@ struct EvalResult {
   double nll = 0.;
   double sigma2 = 0.;
   std::vector<double> grad;
+};
+
+// One prediction call (REModelAMD::Predict's arguments after the response and the parameters)
+struct PredictCall {
+  int n_pred;
+  const double* coords_pred;     // column-major n_pred x d
+  bool cov_mat, var, response;   // predict_cov_mat, predict_var, predict_response
+  double* out;                   // means, then variances (var) or the n_pred x n_pred covariance (cov_mat)
+  const double* mean_add;        // nullable
+};
+
+// The covariance parameters of a prediction call: cp as given (original scale) and what the engines take.
+// Gaussian: sigma2 the error variance, var = sigma1^2 / sigma2; Laplace: sigma2 = 1, var = sigma1^2.
+struct PredictPars {
+  double cp[3];
+  double sigma2, var, phi;
 };
 
 class REModelAMD {
@@ -294,32 +313,34 @@ class REModelAMD {
 
  private:
   void TransformCovPars(const double* orig, double* trafo) const;
-  void PredictPredFirst(int n_pred, const double* coords_pred, const double* trafo, bool predict_cov_mat,
-                        bool predict_var, bool predict_response, double* out, const double* mean_add);
-  void PredictLatentGaussian(int n_pred, const double* coords_pred, const double* trafo, bool predict_cov_mat,
-                             bool predict_var, bool predict_response, double* out, const double* mean_add);
-  void PredictLatentSim(int n, int n_pred, int mp, const std::vector<int>& nb, const double* dB, const double* dDinv,
-                        bool cond_all, bool predict_cov_mat, bool predict_var, bool predict_response, double* out,
-                        const double* mean_add);
-  void PredictDense(const double* y, int n_pred, const double* coords_pred, const double* cov_pars, bool predict_cov_mat,
-                    bool predict_var, bool predict_response, double* out, const double* mean_add);
-  void PredictDenseLaplace(const double* y, int n_pred, const double* coords_pred, const double* cov_pars,
-                           bool predict_cov_mat, bool predict_var, bool predict_response, double* out,
-                           const double* mean_add);
-  void PredictVif(const double* y, int n_pred, const double* coords_pred, const double* cov_pars, bool predict_cov_mat,
-                  bool predict_var, bool predict_response, double* out, const double* mean_add);
-  void PredictVifLaplace(const double* y, int n_pred, const double* coords_pred, const double* cov_pars, bool predict_cov_mat,
-                  bool predict_var, bool predict_response, double* out, const double* mean_add);
-  void PredictFitc(const double* y, int n_pred, const double* coords_pred, const double* cov_pars, bool predict_cov_mat,
-                   bool predict_var, bool predict_response, double* out, const double* mean_add);
+  // ---- predictions (re_model_predict.cpp): the prologue every call runs once, the engine paths Predict chooses
+  // from, and the helpers they share
+  PredictPars PredictPrologue(const double* y, const double* cov_pars, const PredictCall& c);
+  void PredictDense(const PredictCall& c, const PredictPars& p);            // "none", Gaussian and Laplace
+  void PredictFitc(const PredictCall& c, const PredictPars& p);             // "fitc", Gaussian and Laplace
+  void PredictVif(const PredictCall& c, const PredictPars& p);              // "full_scale_vecchia", both
+  void PredictObsFirst(const PredictCall& c, const PredictPars& p);         // Vecchia, exact and Laplace
+  void PredictPredFirst(const PredictCall& c, const PredictPars& p);        // Vecchia, order_pred_first
+  void PredictLatentGaussian(const PredictCall& c, const PredictPars& p);   // Vecchia, latent_ types, Gaussian
+  struct FactorRows {   // device side of PredFactorRows: coordinates, neighbours, B rows, D^-1
+    DevBuf<double> X, B, Dinv;
+    DevBuf<int> nbr;
+  };
+  void PredictLatentSim(const PredictCall& c, int n, int mp, const std::vector<int>& nb, const FactorRows& f,
+                        bool cond_all);
+  void PredictCondAll(const PredictCall& c, int n, int mp, const std::vector<int>& nb, const FactorRows& f,
+                      std::vector<double>& mu, std::vector<double>& var, std::vector<double>& cov);
+  std::vector<double> PredCoords(const PredictCall& c, int n_obs = 0, bool pred_first = false) const;
+  std::vector<int> PredNeighbors(const std::vector<double>& xa, int na, int mp, int row_begin, int end_at);
+  void PredFactorRows(const std::vector<double>& xa, int na, const std::vector<int>& nb, int mp, int r0,
+                      const PredictPars& p, bool jitter, FactorRows& f);
+  void DownloadFactorRows(const FactorRows& f, std::vector<double>& B, std::vector<double>& Dinv,
+                          std::vector<double>* y);
+  void LaplaceTail(const PredictCall& c, std::vector<double>& mean, std::vector<double>& var, std::vector<double>& cov);
+  void GaussianTail(const PredictCall& c, const double* mean, const double* var, std::vector<double>& cov, double s2,
+                    double shift, bool scale_first);
   std::vector<int> FitcMatch(const std::vector<double>& xp_rowmajor, int n_pred) const;
   void ResponseTransform(int n_pred, double* mean, double* var, double* cov);
-  void PredictFitcLaplace(const double* y, int n_pred, const double* coords_pred, const double* cov_pars,
-                          bool predict_cov_mat, bool predict_var, bool predict_response, double* out,
-                          const double* mean_add);
-  void PredictCondAll(int n, int n_pred, int mp, const std::vector<int>& nb, const double* dB, const double* dDinv,
-                      double sigma2, double nugget_sub, bool want_var, bool want_cov, std::vector<double>& h,
-                      std::vector<double>& cov);
   double range_trafo_of(double rho) const { return range_trafo(cfg_.cov_type, rho); }
   void FindInitCovPar(const double* y, double* trafo) const;
   double InitialRangeTrafo() const;

@@ -125,19 +125,11 @@ void REModelAMD::PredictClusters(const double* y, int n_pred, const double* coor
                                  const int32_t* cluster_ids_pred, const double* cov_pars, bool predict_cov_mat,
                                  bool predict_var, bool predict_response, double* out, const double* mean_add) {
   if (!clustered()) Fatal("PredictClusters: the model has one cluster");
-  if (n_pred <= 0) Fatal("num_data_pred must be > 0");
-  if (coords_pred == nullptr) Fatal("gp_coords_data_pred must be provided");
+  const PredictPars pars = PredictPrologue(
+      y, cov_pars, {n_pred, coords_pred, predict_cov_mat, predict_var, predict_response, out, mean_add});
   if (cluster_ids_pred == nullptr)
     Fatal("cluster_ids_pred (cluster_ids_data_pred) must be provided for predictions of a model with several clusters");
-  UseDevice();
-  if (y != nullptr) SetY(y);
-  if (!y_set_) Fatal("response variable y has not been set (pass y or evaluate the likelihood first)");
-  double cp[3];
-  if (cov_pars != nullptr) std::copy(cov_pars, cov_pars + 3, cp);
-  else if ((int)last_cov_pars_.size() == 3) std::copy(last_cov_pars_.begin(), last_cov_pars_.end(), cp);
-  else Fatal("cov_pars must be provided (no previous evaluation)");
-  double trafo[3];
-  TransformCovPars(cp, trafo);
+  const double* cp = pars.cp;
   const int d = cfg_.d;
   const bool want_cov = predict_cov_mat, want_var = predict_var && !predict_cov_mat;
   const size_t extra = want_cov ? (size_t)n_pred * n_pred : (want_var ? (size_t)n_pred : 0);
@@ -167,7 +159,7 @@ void REModelAMD::PredictClusters(const double* y, int n_pred, const double* coor
                 s += df * df;
               }
               double cc, dc;
-              cov_dcov<COV>(std::sqrt(s), cp[1], trafo[2], cc, dc);
+              cov_dcov<COV>(std::sqrt(s), cp[1], pars.phi, cc, dc);
               res[(size_t)k + (size_t)b * k + a] = a == b ? cp[1] + nug : cc;
             }
         });
