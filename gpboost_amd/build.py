@@ -33,6 +33,10 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", f"--offload-arc
 LDFLAGS = ["-shared", "-fopenmp", f"--offload-arch={ARCH}", f"-L{ROCM}/lib", f"-L{ROCM}/llvm/lib",
            "-lrccl", f"-Wl,-rpath,{ROCM}/lib", f"-Wl,-rpath,{ROCM}/llvm/lib"]
 
+# Per-source device flags: the wide row kernel is built without packed fp32 arithmetic (it is fp64 throughout; the
+# flag keeps the compiler from forming v_pk_*_f32 in any helper code)
+EXTRA_FLAGS = {"vecchia_rows_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
 
 def sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith((".cpp", ".hip")))
@@ -49,7 +53,8 @@ def _compile(src: str) -> str:
     # MFMA accumulators in VGPRs (gfx950's unified register file): without this the compiler keeps loop-carried
     # accumulators in VGPRs and copies them to and from AGPRs around every MFMA loop iteration
     lang = ["-x", "hip", "-mllvm", "-amdgpu-mfma-vgpr-form"] if src.endswith(".hip") else []
-    cmd = [os.path.join(ROCM, "bin", "hipcc")] + CXXFLAGS + DEFS + lang + ["-c", path, "-o", obj]
+    lang += EXTRA_FLAGS.get(src, [])
+    cmd =[os.path.join(ROCM, "bin", "hipcc")] + CXXFLAGS + DEFS + lang + ["-c", path, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"compile failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

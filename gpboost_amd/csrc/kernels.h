@@ -45,6 +45,12 @@ int vecchia_rows_blocks(int rows, int m);   // upper bound of the grid (block-pa
 int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);   // returns the grid size
 // 16-lane form for m <= 30 (vecchia_rows16.hip; DPP broadcasts, four rows per wave), same contract
 int launch_vecchia_rows16(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);
+// Wide form for 64 < m <= kRowsWideMaxM (vecchia_rows_wide.hip; one workgroup per row, blocked Cholesky in LDS
+// with MFMA trailing updates), same contract; sched, R and prio are ignored. Its grid never exceeds
+// kRowsWideMaxBlocks, which vecchia_rows_blocks covers.
+constexpr int kRowsWideMaxM = 128;
+constexpr int kRowsWideMaxBlocks = 2048;
+int launch_vecchia_rows_wide(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);
 // The last 16-lane launch of this process: trips per wave R and VecchiaRowsArgs::prio as launched
 void vecchia_rows16_last_launch(int* trips, int* prio);
 // True when launch_vecchia_rows would run the 16-lane form for this m (the A/B environment switches included)

@@ -1015,6 +1015,7 @@ int blocks_for(int rows) {
 // Upper bound of any launch's grid (block-partial buffers are sized by it).
 constexpr int kMaxBlocksAny = 2048;
 static_assert(kMaxBlocks <= kMaxBlocksAny, "grid cap");
+static_assert(kRowsWideMaxBlocks <= kMaxBlocksAny, "grid cap of the wide form (vecchia_rows_wide.hip)");
 
 // Bordered forms: the grid is the resident capacity (blocks per CU from the occupancy calculator
 // for this instance's registers and LDS, times the CU count), so every block strides over an
@@ -1119,7 +1120,7 @@ int launch_cov(int cov, const VecchiaRowsArgs& a, hipStream_t s) {
 }  // namespace
 
 int vecchia_rows_blocks(int rows, int m) {
-  if (lanes_for_m(m) == 0) Fatal("num_neighbors = %d > 64 is not supported by the GPU Vecchia kernel", m);
+  if (m > kRowsWideMaxM) Fatal("num_neighbors = %d > %d is not supported by the GPU Vecchia kernel", m, kRowsWideMaxM);
   return std::min(std::max(rows, 1), kMaxBlocksAny);   // >= any launch's grid (one row group per block at least)
 }
 
@@ -1134,7 +1135,10 @@ int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s) {
     case 16: return launch_cov<16>(cov_type, a, s);
     case 32: return launch_cov<32>(cov_type, a, s);
     case 64: return launch_cov<64>(cov_type, a, s);
-    default: Fatal("num_neighbors = %d > 64 is not supported by the GPU Vecchia kernel", a.m);
+    default:   // 64 < m: one workgroup per row (vecchia_rows_wide.hip)
+      if (a.m > kRowsWideMaxM)
+        Fatal("num_neighbors = %d > %d is not supported by the GPU Vecchia kernel", a.m, kRowsWideMaxM);
+      return launch_vecchia_rows_wide(cov_type, a, s);
   }
   return 0;
 }
