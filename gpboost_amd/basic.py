@@ -1032,6 +1032,24 @@ class GPModel:
                                                       self._host_reduce, None))
 
 
+def vecchia_fisher_rows(X, nbr, cov_type: int, var: float, phi: float):
+    """GPB_TestVecchiaFisherRows: the row factor of the Vecchia Fisher information (transformed scale, nugget 1) for
+    the points X (n x d, Vecchia order) and the neighbour table nbr (n x m). Returns (Bv, dBv_var, dBv, Dinv,
+    dD_var, dD)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+    (n, d), m = X.shape, nbr.shape[1]
+    if nbr.shape[0] != n:
+        raise ValueError("nbr must have one row per point")
+    big = [np.empty((n, m)) for _ in range(3)]
+    small = [np.empty(n) for _ in range(3)]
+    fn = lib().GPB_TestVecchiaFisherRows
+    D, c = ctypes.POINTER(ctypes.c_double), ctypes
+    fn.argtypes = [D, c.POINTER(c.c_int32), c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double] + [D] * 6
+    _safe_call(fn(_dp(X), _ip(nbr), n, d, m, int(cov_type), float(var), float(phi), *map(_dp, big + small)))
+    return (*big, *small)
+
+
 def comm_create_id() -> bytes:
     n = lib().GPB_CommIdSize()
     buf = ctypes.create_string_buffer(n)

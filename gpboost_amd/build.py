@@ -33,9 +33,10 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", f"--offload-arc
 LDFLAGS = ["-shared", "-fopenmp", f"--offload-arch={ARCH}", f"-L{ROCM}/lib", f"-L{ROCM}/llvm/lib",
            "-lrccl", f"-Wl,-rpath,{ROCM}/lib", f"-Wl,-rpath,{ROCM}/llvm/lib"]
 
-# Per-source device flags: the wide row kernel is built without packed fp32 arithmetic (it is fp64 throughout; the
-# flag keeps the compiler from forming v_pk_*_f32 in any helper code)
-EXTRA_FLAGS = {"vecchia_rows_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# Per-source device flags: the wide row kernels are built without packed fp32 arithmetic (they are fp64 throughout;
+# the flag keeps the compiler from forming v_pk_*_f32 in any helper code)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"vecchia_rows_wide.hip": _NO_PK_F32, "vecchia_fisher_rows_wide.hip": _NO_PK_F32}
 
 
 def sources():

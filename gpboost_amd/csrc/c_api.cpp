@@ -1084,6 +1084,14 @@ int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, double delta, int pm
   API_END();
 }
 
+int GPB_TestVecchiaFisherRows(const double* X, const int32_t* nbr, int n, int d, int m, int cov_type, double var,
+                              double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                              double* dD) {
+  API_BEGIN();
+  gpb_amd::test_vecchia_fisher_rows(X, nbr, n, d, m, cov_type, var, phi, Bv, dBv_var, dBv, Dinv, dD_var, dD);
+  API_END();
+}
+
 int GPB_TestVifRows(int n_total, int d, int i0, int nn, int m, const double* X, int64_t x_len, const int32_t* nbr,
                     int64_t nbr_len, const double* V, const double* P0, const double* P1, int64_t mat_len, int cov_type,
                     double var, double phi, double nugget, double cjit, int grad, int form, int order, double pad_fill,

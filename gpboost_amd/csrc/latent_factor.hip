@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "cov.h"
+#include "kernels.h"
 #include "latent_kernels.h"
 
 namespace gpb_amd {
@@ -407,8 +408,13 @@ void launch_latent_factor(int cov_type, const LatentFactorArgs& a, hipStream_t s
     case 32: launch_cov<32>(cov_type, a, s); break;
     case 64: launch_cov<64>(cov_type, a, s); break;
     default:
+      if (a.dBv_var != nullptr) {   // the nugget form (Fisher information): the wide row kernel of its own
+        if (a.m > kRowsWideMaxM)
+          Fatal("num_neighbors = %d > %d is not supported for the Vecchia Fisher information", a.m, kRowsWideMaxM);
+        launch_vecchia_fisher_rows_wide(cov_type, a, s);
+        break;
+      }
       if (a.m > kWideMax) Fatal("num_neighbors = %d > %d is not supported by the GPU latent Vecchia kernel", a.m, kWideMax);
-      if (a.dBv_var != nullptr) Fatal("num_neighbors = %d > 64 is not supported for the Vecchia Fisher information", a.m);
       switch (cov_type) {
         case kMatern05: launch_wide<kMatern05>(a, s); break;
         case kMatern15: launch_wide<kMatern15>(a, s); break;

@@ -38,6 +38,10 @@ struct LatentFactorArgs {
   double* dD_var;
 };
 void launch_latent_factor(int cov_type, const LatentFactorArgs& a, hipStream_t s);
+// The nugget form (dBv_var != nullptr) for 64 < m <= kRowsWideMaxM (vecchia_fisher_rows_wide.hip: one workgroup per
+// row, blocked Cholesky in LDS with c as a border row, t = dC a on the whole workgroup, the two dependent solves in
+// one sweep). launch_latent_factor routes to it; dBv / dD stay nullable.
+void launch_vecchia_fisher_rows_wide(int cov_type, const LatentFactorArgs& a, hipStream_t s);
 
 struct SparseB {
   int n, m;

@@ -8,6 +8,7 @@
 #include <limits>
 #include <vector>
 
+#include "cov.h"
 #include "latent.h"
 #include "latent_test.h"
 
@@ -348,6 +349,56 @@ void test_latent_vector(int op, int n, int t, int np, int ia, int ib, double alp
   if (g1.len) fetch(g1, out1);
   if (gs.len) fetch(gs, small_out);
   *guard = touched;
+}
+
+void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int m, int cov_type, double var,
+                              double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                              double* dD) {
+  const char* fn = "GPB_TestVecchiaFisherRows";
+  test_latent_check_graph(fn, n, m, nbr, (int64_t)n * m, d, X, (int64_t)n * d);
+  if (d > 3) Fatal("%s: d = %d", fn, d);
+  if (cov_type < kMatern05 || cov_type > kGaussian) Fatal("%s: cov_type = %d", fn, cov_type);
+  if (!(var > 0.) || !(phi > 0.) || !std::isfinite(var) || !std::isfinite(phi))
+    Fatal("%s: var = %g, phi = %g", fn, var, phi);
+  if (Bv == nullptr || Dinv == nullptr) Fatal("%s: Bv or Dinv is NULL", fn);
+  if ((dBv_var == nullptr) != (dD_var == nullptr) || (dBv == nullptr) != (dD == nullptr))
+    Fatal("%s: dBv_var goes with dD_var and dBv with dD", fn);
+  const size_t nm = (size_t)n * m;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  DevBuf<double> dX((size_t)n * d);
+  DevBuf<int> dn(nm);
+  HIP_CHECK(hipMemcpy(dX.get(), X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dn.get(), nbr, sizeof(int) * nm, hipMemcpyHostToDevice));
+  // outputs: {Bv, dBv_var, dBv} n x m, {Dinv, dD_var, dD} n, each between guard bands
+  double* host[6] = {Bv, dBv_var, dBv, Dinv, dD_var, dD};
+  DevBuf<double> dev[6];
+  double* p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int q = 0; q < 6; ++q) {
+    if (host[q] == nullptr) continue;
+    const size_t len = (q < 3 ? nm : (size_t)n) + 2 * kGuard;
+    dev[q].alloc(len);
+    const std::vector<double> h(len, nan);
+    HIP_CHECK(hipMemcpy(dev[q].get(), h.data(), sizeof(double) * len, hipMemcpyHostToDevice));
+    p[q] = dev[q].get() + kGuard;
+  }
+  LatentFactorArgs fa{};
+  fa.X = dX.get(); fa.nbr = dn.get(); fa.n = n; fa.d = d; fa.m = m;
+  fa.var = var; fa.phi = phi;
+  fa.jitter = 1. + 1e-10;
+  fa.nugget = 1.;
+  fa.Bv = p[0]; fa.dBv_var = p[1]; fa.dBv = p[2];
+  fa.Dinv = p[3]; fa.dD_var = p[4]; fa.dD = p[5];
+  launch_latent_factor(cov_type, fa, nullptr);
+  HIP_CHECK(hipDeviceSynchronize());
+  for (int q = 0; q < 6; ++q) {
+    if (host[q] == nullptr) continue;
+    const size_t len = q < 3 ? nm : (size_t)n;
+    std::vector<double> h(len + 2 * kGuard);
+    HIP_CHECK(hipMemcpy(h.data(), dev[q].get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < kGuard; ++g)
+      if (!std::isnan(h[g]) || !std::isnan(h[kGuard + len + g])) Fatal("%s: output %d was written out of range", fn, q);
+    std::memcpy(host[q], h.data() + kGuard, sizeof(double) * len);
+  }
 }
 
 // ---------------------------------------------------------------- the C ABI's object

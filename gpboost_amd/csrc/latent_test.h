@@ -63,6 +63,13 @@ void test_latent_vector(int op, int n, int t, int np, int ia, int ib, double alp
 // n >= 1, 1 <= m, d >= 1, nbr_len = n m, x_len = n d, 0 <= nbr[i m + r] < i and distinct for r < min(i, m)
 void test_latent_check_graph(const char* fn, int n, int m, const int* nbr, int64_t nbr_len, int d, const double* X,
                              int64_t x_len);
+// GPB_TestVecchiaFisherRows: launch_latent_factor in the Fisher form (nugget 1, jitter 1 + 1e-10) on host arrays, for
+// every m (m <= 64: the lane-group kernel, 65 to 128: vecchia_fisher_rows_wide.hip). Bv and Dinv are required; dBv_var
+// with dD_var and dBv with dD are nullable pairs. Inputs are checked on the host first; outputs sit between guard
+// bands and start as NaN, and a changed guard word is an error.
+void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int m, int cov_type, double var,
+                              double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                              double* dD);
 // opts (nullable, 9 entries): {relabel, dense_rows, head_rows, tail_merge, seg_form, tail_order, tail_form, tail_w,
 // no_graph}, an entry < 0 = the environment's / the default
 LatentOptions test_latent_options(const char* fn, const int64_t* opts, int n);

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "cov.h"
+#include "kernels.h"
 #include "latent_kernels.h"
 #include "slq_host.h"
 
@@ -26,7 +27,8 @@ int env_rows(const char* name, int dflt) {
 VecchiaFisher::VecchiaFisher(int n, int d, int m, const double* d_X, const int* d_nbr, const std::vector<int>& nbr,
                              hipStream_t stream)
     : n_(n), d_(d), m_(m), s_(stream), d_X_(d_X), d_nbr_(d_nbr) {
-  if (m > 64) Fatal("standard deviations for the Vecchia approximation support num_neighbors <= 64, got %d", m);
+  if (m > kRowsWideMaxM)
+    Fatal("standard deviations for the Vecchia approximation support num_neighbors <= %d, got %d", kRowsWideMaxM, m);
   if ((int)nbr.size() != n * m) Fatal("VecchiaFisher: neighbour table of %zu entries, expected %d", nbr.size(), n * m);
   // B^T lists (column j -> rows ascending, value slot row * m + r), as LatentVecchia::BuildStructure
   std::vector<int> cnt(n + 1, 0);

@@ -13,7 +13,8 @@
 // The reference forms these with Eigen sparse triangular solves (TriangularSolve, one row at a time).
 //
 // This build: the factor and its two derivatives from one row kernel on the transformed scale (the
-// latent factor kernel in its nugget form, latent_factor.hip), rescaled to the original scale on the
+// latent factor kernel in its nugget form, latent_factor.hip; 65 to 128 neighbours: the workgroup-per-row
+// kernel of vecchia_fisher_rows_wide.hip), rescaled to the original scale on the
 // device (B is scale-free; D_o = sigma^2 D, dB_o / dsigma1^2 = dB / dlog(var) / sigma1^2, dD_o / dsigma1^2 =
 // dD / dlog(var) sigma^2 / sigma1^2, d / drho = dlog(phi) / drho d / dlog(phi), dD also times sigma^2);
 // Sigma z from ONE application of the VADU plan (vadu_precond.h: B^-1 diag(1/dw) B^-T with dw = D^-1 —

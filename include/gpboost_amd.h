@@ -596,6 +596,17 @@ GPBOOST_AMD_EXPORT int GPB_TestLatentOpsVector(int op, int n, int t, int np, int
 GPBOOST_AMD_EXPORT int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, double delta, int pmax_single,
                                             int pmax_block, const double* RHS, double* U, int64_t block_len,
                                             int* its, int* flags);
+/* The row factor of the Vecchia Fisher information (standard errors) on host arrays: launch_latent_factor in its
+ * Gaussian form on the transformed scale (nugget 1, between-neighbour diagonal var (1 + 1e-10) + 1) for the points X
+ * (n x d row-major, d in 1..3) and the neighbour table nbr (n x m, checked as for GPB_TestLatentOpsCreate). Every m
+ * is served: m <= 64 by the lane-group kernel, 65 to 128 by the workgroup-per-row kernel; m > 128 with dBv_var
+ * requested is an error return that names num_neighbors and 128. cov_type: 0 exponential, 1 / 2 Matern 1.5 / 2.5,
+ * 3 Gaussian; var, phi on the transformed scale. Outputs: Bv, dBv_var (d / dlog var), dBv (d / dlog phi) n x m with
+ * zeros in the slots r >= min(i, m); Dinv, dD_var, dD n. Bv and Dinv are required, dBv_var with dD_var and dBv with
+ * dD are nullable pairs. Outputs start as NaN between guard doubles; a changed guard word is an error return. */
+GPBOOST_AMD_EXPORT int GPB_TestVecchiaFisherRows(const double* X, const int32_t* nbr, int n, int d, int m,
+                                                 int cov_type, double var, double phi, double* Bv, double* dBv_var,
+                                                 double* dBv, double* Dinv, double* dD_var, double* dD);
 
 /* The full-scale Vecchia ("VIF") row factor, sparse products and vector kernels on host arrays, launched by the
  * host launch functions VifSolver uses (csrc/vif.h). No reference counterpart (tests). Everything is checked on
