@@ -47,7 +47,7 @@ int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s); 
 int launch_vecchia_rows16(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);
 // Wide form for 64 < m <= kRowsWideMaxM (vecchia_rows_wide.hip; one workgroup per row, blocked Cholesky in LDS
 // with MFMA trailing updates), same contract; sched, R and prio are ignored. Its grid never exceeds
-// kRowsWideMaxBlocks, which vecchia_rows_blocks covers.
+// kRowsWideMaxBlocks (the grid cap of both wide row kernels, vecchia_wide_core.h), which vecchia_rows_blocks covers.
 constexpr int kRowsWideMaxM = 128;
 constexpr int kRowsWideMaxBlocks = 2048;
 int launch_vecchia_rows_wide(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);

@@ -389,13 +389,7 @@ void launch_k(const LatentFactorArgs& a, hipStream_t s) {
 
 template <int K>
 void launch_cov(int cov, const LatentFactorArgs& a, hipStream_t s) {
-  switch (cov) {
-    case kMatern05: launch_k<K, kMatern05>(a, s); break;
-    case kMatern15: launch_k<K, kMatern15>(a, s); break;
-    case kMatern25: launch_k<K, kMatern25>(a, s); break;
-    case kGaussian: launch_k<K, kGaussian>(a, s); break;
-    default: Fatal("unsupported covariance type %d", cov);
-  }
+  dispatch_cov(cov, [&](auto c) { launch_k<K, decltype(c)::value>(a, s); });
 }
 
 }  // namespace
@@ -415,13 +409,7 @@ void launch_latent_factor(int cov_type, const LatentFactorArgs& a, hipStream_t s
         break;
       }
       if (a.m > kWideMax) Fatal("num_neighbors = %d > %d is not supported by the GPU latent Vecchia kernel", a.m, kWideMax);
-      switch (cov_type) {
-        case kMatern05: launch_wide<kMatern05>(a, s); break;
-        case kMatern15: launch_wide<kMatern15>(a, s); break;
-        case kMatern25: launch_wide<kMatern25>(a, s); break;
-        case kGaussian: launch_wide<kGaussian>(a, s); break;
-        default: Fatal("unsupported covariance type %d", cov_type);
-      }
+      dispatch_cov(cov_type, [&](auto c) { launch_wide<decltype(c)::value>(a, s); });
   }
 }
 

@@ -4,61 +4,28 @@
 // wavefront bounds them at m = 64. Here one 256-thread workgroup (four waves) owns a Vecchia row i with
 // k = min(i, m) neighbours, and C lives in LDS. The per-row quantities are those of vecchia_rows_kernel (steps 1-3
 // of its header) and the row's six sums those of the reduction contract; only the way they are computed
-// differs. With KP = k rounded up to a multiple of 16 (rows >= k are identity padding with zero right-hand sides,
-// which leaves every solution unchanged):
+// differs. The layout (one square LDS array A with C below and dC / dlog(phi) above the diagonal, KP = k rounded up
+// to a multiple of 16), the pair phase (stage 2), the blocked Cholesky (stage 3) and the column sweeps of stage 4 are
+// those of vecchia_wide_core.h, shared with the Fisher row kernel; here with reciprocal pivots and no border row.
+// What is this kernel's own:
 //
 //  1. gather: thread r < KP loads neighbour r (index, coordinates, response) and evaluates c_r and dc_r / dlog(phi);
-//  2. pairs: the KP (KP - 1) / 2 covariances are evaluated once, split evenly over the 256 threads (rows h and
-//     KP - 1 - h together hold KP - 1 pairs, so the pairs form a KP / 2 x (KP - 1) rectangle), and stored in ONE
-//     square array A (KP x KP, odd row stride S = MP + 1, MP = m rounded up to 16): C_rc in the lower triangle
-//     (r > c), dC_rc / dlog(phi) in the upper one (A[c][r]). No second matrix and no second exp pass;
-//  3. blocked right-looking Cholesky of the lower triangle in place, 16-column panels. Per panel: every wave loads
-//     the 16 x 16 diagonal block (lane & 15 = block row, 16 registers), factors it by a column sweep whose
-//     broadcasts are 16-lane shuffles, and solves X L_bb^T = P for the panel rows below with the same shuffles
-//     (thread = row, 16 registers; the four waves hold the same L_bb, so no barrier separates factor and solve);
-//     then the trailing update A_IJ -= P_I P_J^T runs as 16 x 16 tiles of four v_mfma_f64_16x16x4 each, the
-//     tiles I >= J dealt round-robin to the four waves. Diagonal tiles store only their lower half: the upper
-//     triangle keeps dC. Two barriers per panel;
-//  4. a = C^-1 c and v = C^-1 y_nbr together on wave 0: lane l holds entries l and l + 64 of both, forward and
-//     backward column sweeps with one wave shuffle per column and right-hand side, one load of L per column for
-//     both, and the reciprocal pivots from LDS (no barrier inside the solves);
+//  4. a = C^-1 c and v = C^-1 y_nbr together on wave 0: one forward and one backward sweep for both right-hand
+//     sides (no barrier inside the solves);
 //  5. still on wave 0 and in registers: t = dC a from the upper triangle (entries l and l + 64, four partial sums
 //     each, wave-uniform column loop), the eight dot products of the lane-group kernel by a fixed shuffle tree, and
 //     lane 0 forms D, u and the derivative terms and adds the row's six sums to its accumulators. Stages 4 and 5
 //     are latency chains of one wave; the other three wait at the next row's barrier.
 // Workgroups stride over rows; thread 0 writes the workgroup's six partials, which launch_sum_blocks adds in block
 // order. Every sum has a fixed order, there is no atomic, and a row's outputs depend only on its data and the
-// parameters (not on the grid). Every loop's trip count is uniform over the workgroup or the wave; where the work
-// per lane differs, the lanes are predicated instead. A failed pivot has no path of its own: sqrt of a negative
-// pivot is NaN, which reaches the sums, where the host's NaN check reports it.
+// parameters (not on the grid). A failed pivot's NaN reaches the sums, where the host's NaN check reports it.
 //
-// LDS per workgroup: MP S + 9 MP doubles (A, the coordinates and six vectors): 141312 bytes at m = 128,
-// 81408 at m = 96, 57600 at m = 80. The allocation is sized by the model's m and checked against the device's
-// per-workgroup limit, which bounds the largest m. The kernel's registers (256 VGPRs and 175 AGPRs per lane) allow
-// one workgroup per CU at every m; measurements are in DESIGN.md section 5.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-
-#include "common.h"
-#include "cov.h"
-#include "kernels.h"
+// LDS per workgroup: see the core header; the six vectors are c, dc, y_nbr, a, v and 1 / L_kk. The kernel's
+// registers allow one workgroup per CU at every m; measurements are in DESIGN.md section 5.
+#include "vecchia_wide_core.h"
 
 namespace gpb_amd {
 namespace {
-
-constexpr int kDMax = 3;
-constexpr int kWideThreads = 256;
-constexpr int kPanel = 16;   // panel width = MFMA tile edge
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-__host__ __device__ constexpr int wide_mp(int m) { return (m + kPanel - 1) & ~(kPanel - 1); }
-// A (MP x S) | coordinates (MP x 3) | c, dc, y_nbr, a, v, 1 / L_kk (6 MP)
-__host__ __device__ constexpr size_t wide_lds_doubles(int m) {
-  return (size_t)wide_mp(m) * (wide_mp(m) + 1) + (size_t)(kDMax + 6) * wide_mp(m);
-}
 
 template <int COV>
 __global__ void __launch_bounds__(kWideThreads) vecchia_rows_wide_kernel(VecchiaRowsArgs a) {
@@ -73,7 +40,7 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_rows_wide_kernel(Vecchia
   double* vv = av + MP;            // v = C^-1 y_nbr
   double* rd = vv + MP;            // 1 / L_kk
 
-  const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int d = a.d;
   const double var = a.var, phi = a.phi;
@@ -108,130 +75,19 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_rows_wide_kernel(Vecchia
     }
     __syncthreads();
 
-    // ---- 2. pairs: e -> (h, q); q < h: (row h, column q), else (row KP - 1 - h, column q - h)
-    const int npairs = (KP / 2) * (KP - 1);
-    for (int e0 = 0; e0 < npairs; e0 += kWideThreads) {   // workgroup-uniform trip count; the last trip is partial
-      const int e = min(e0 + tid, npairs - 1);
-      const int h = e / (KP - 1), q = e - h * (KP - 1);
-      const int r = q < h ? h : KP - 1 - h;
-      const int c = q < h ? q : q - h;
-      double s = 0.;
-#pragma unroll
-      for (int qq = 0; qq < kDMax; ++qq) {
-        const double t = nbx[r * kDMax + qq] - nbx[c * kDMax + qq];
-        s += t * t;
-      }
-      double cc, dc;
-      cov_dcov_sq<COV>(s, var, phi, cc, dc);
-      const bool valid = r < k;   // c < r
-      if (e0 + tid < npairs) {
-        A[r * S + c] = valid ? cc : 0.;
-        A[c * S + r] = valid ? dc : 0.;
-      }
-    }
+    wide_pairs<COV>(A, S, nbx, KP, k, var, phi, tid);   // ---- 2.
     __syncthreads();
-
-    // ---- 3. blocked Cholesky of the lower triangle
-    const int NB = KP / kPanel;
-    for (int p = 0; p < NB; ++p) {
-      const int j0 = p * kPanel;
-      double row[kPanel], rl[kPanel];   // block row lr (entries c > lr hold dC and are never used); 1 / L_jj
-#pragma unroll
-      for (int c = 0; c < kPanel; ++c) row[c] = A[(j0 + lr) * S + j0 + c];
-#pragma unroll
-      for (int j = 0; j < kPanel; ++j) {
-        const double l = sqrt(__shfl(row[j], j, kPanel));
-        rl[j] = 1. / l;
-        const double lik = row[j] * rl[j];   // L[lr][j] for lr > j
-        row[j] = lr == j ? l : lik;
-#pragma unroll
-        for (int jj = j + 1; jj < kPanel; ++jj) row[jj] = fma(-lik, __shfl(lik, jj, kPanel), row[jj]);   // lr >= jj
-      }
-      // panel rows below the block: x L_bb^T = P, thread = row (threads past the last row redo it and store nothing)
-      const int t = j0 + kPanel + tid;
-      const int tc = min(t, KP - 1);
-      double x[kPanel];
-#pragma unroll
-      for (int c = 0; c < kPanel; ++c) x[c] = A[tc * S + j0 + c];
-#pragma unroll
-      for (int j = 0; j < kPanel; ++j) {
-        double s = x[j];
-#pragma unroll
-        for (int q = 0; q < j; ++q) s = fma(-x[q], __shfl(row[q], j, kPanel), s);   // L[j][q] from lane j
-        x[j] = s * rl[j];
-      }
-      if (t < KP) {
-#pragma unroll
-        for (int c = 0; c < kPanel; ++c) A[t * S + j0 + c] = x[c];
-      }
-      __syncthreads();   // the panel is final; every wave has read the diagonal block
-      if (tid < kPanel) {
-#pragma unroll
-        for (int c = 0; c < kPanel; ++c) {
-          if (c <= lr) A[(j0 + lr) * S + j0 + c] = row[c];
-          if (c == lr) rd[j0 + c] = rl[c];
-        }
-      }
-      // trailing update, tiles I >= J > p round-robin over the waves. MFMA operands: a = P_I[lr][4 s + lq],
-      // b = P_J[lr][4 s + lq]; result entry rg of a lane is row lq + 4 rg, column lr of the tile
-      int cnt = 0;
-      for (int I = p + 1; I < NB; ++I) {
-        for (int J = p + 1; J <= I; ++J, ++cnt) {
-          if ((cnt & 3) != wave) continue;
-          const double* pa = A + (I * kPanel + lr) * S + j0 + lq;
-          const double* pb = A + (J * kPanel + lr) * S + j0 + lq;
-          double4_t u = {0., 0., 0., 0.};
-#pragma unroll
-          for (int s4 = 0; s4 < kPanel; s4 += 4) u = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[s4], pb[s4], u, 0, 0, 0);
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            const int ii = I * kPanel + lq + 4 * rg, jj = J * kPanel + lr;
-            if (jj <= ii) A[ii * S + jj] -= u[rg];
-          }
-        }
-      }
-      __syncthreads();
-    }
+    wide_chol<false, false>(A, S, KP, rd, nullptr, tid, lane, wave);   // ---- 3.
 
     // ---- 4. a = C^-1 c and v = C^-1 y_nbr on wave 0: entries lane and lane + 64 of both, one load of L per step
     if (wave == 0) {
       const int t0 = lane, t1 = lane + 64;
       const bool h0 = t0 < KP, h1 = t1 < KP;
-      const int K0 = min(KP, 64);
-      double z0 = h0 ? cv[t0] : 0., z1 = h1 ? cv[t1] : 0.;
-      double w0 = h0 ? yv[t0] : 0., w1 = h1 ? yv[t1] : 0.;
-      for (int c = 0; c < K0; ++c) {   // L z = rhs
-        const double xk = __shfl(z0, c) * rd[c], yk = __shfl(w0, c) * rd[c];
-        const double l0 = (h0 && t0 > c) ? A[t0 * S + c] : 0.;
-        const double l1 = h1 ? A[t1 * S + c] : 0.;
-        z0 = t0 == c ? xk : fma(-l0, xk, z0);
-        w0 = t0 == c ? yk : fma(-l0, yk, w0);
-        z1 = fma(-l1, xk, z1);
-        w1 = fma(-l1, yk, w1);
-      }
-      for (int c = 64; c < KP; ++c) {
-        const double xk = __shfl(z1, c - 64) * rd[c], yk = __shfl(w1, c - 64) * rd[c];
-        const double l1 = (h1 && t1 > c) ? A[t1 * S + c] : 0.;
-        z1 = t1 == c ? xk : fma(-l1, xk, z1);
-        w1 = t1 == c ? yk : fma(-l1, yk, w1);
-      }
-      for (int c = KP - 1; c >= 64; --c) {   // L^T x = z (row c of L is contiguous)
-        const double xk = __shfl(z1, c - 64) * rd[c], yk = __shfl(w1, c - 64) * rd[c];
-        const double l1 = t1 < c ? A[c * S + t1] : 0.;
-        const double l0 = A[c * S + t0];
-        z1 = t1 == c ? xk : fma(-l1, xk, z1);
-        w1 = t1 == c ? yk : fma(-l1, yk, w1);
-        z0 = fma(-l0, xk, z0);
-        w0 = fma(-l0, yk, w0);
-      }
-      for (int c = K0 - 1; c >= 0; --c) {
-        const double xk = __shfl(z0, c) * rd[c], yk = __shfl(w0, c) * rd[c];
-        const double l0 = t0 < c ? A[c * S + t0] : 0.;
-        z0 = t0 == c ? xk : fma(-l0, xk, z0);
-        w0 = t0 == c ? yk : fma(-l0, yk, w0);
-      }
-      if (h0) { av[t0] = z0; vv[t0] = w0; }
-      if (h1) { av[t1] = z1; vv[t1] = w1; }
+      double z0[2] = {h0 ? cv[t0] : 0., h0 ? yv[t0] : 0.}, z1[2] = {h1 ? cv[t1] : 0., h1 ? yv[t1] : 0.};
+      wide_forward<2, false>(A, S, KP, rd, lane, z0, z1);
+      wide_backward<2, false>(A, S, KP, rd, lane, z0, z1);
+      if (h0) { av[t0] = z0[0]; vv[t0] = z0[1]; }
+      if (h1) { av[t1] = z1[0]; vv[t1] = z1[1]; }
     }
     __syncthreads();
 
@@ -305,31 +161,10 @@ int launch_vecchia_rows_wide(int cov_type, const VecchiaRowsArgs& a, hipStream_t
   if (a.m < 1 || a.m > kRowsWideMaxM)
     Fatal("num_neighbors = %d > %d is not supported by the GPU Vecchia kernel", a.m, kRowsWideMaxM);
   if (a.r1 <= a.r0) return 0;
-  int dev = 0, cus = 0, lds_max = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-  const size_t bytes = wide_lds_doubles(a.m) * sizeof(double);
-  if (bytes > (size_t)lds_max)
-    Fatal("num_neighbors = %d needs %zu bytes of LDS per workgroup, this device has %d", a.m, bytes, lds_max);
   int blocks = 0;
   dispatch_cov(cov_type, [&](auto cov) {
-    constexpr int COV = decltype(cov)::value;
-    auto kern = vecchia_rows_wide_kernel<COV>;
-    if (bytes > 64 * 1024)   // above the default dynamic-LDS limit
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)bytes));
-    // the grid is the resident capacity, so every workgroup strides over an equal share of the rows in one round
-    int per_cu = 0;
-    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWideThreads, bytes));
-    blocks = std::min({a.r1 - a.r0, std::max(per_cu, 1) * std::max(cus, 1), kRowsWideMaxBlocks});
-    static const bool info = std::getenv("GPBOOST_AMD_ROWS_PROF") != nullptr;
-    if (info)
-      std::fprintf(stderr, "[rows wide] m=%d grid=%d workgroups/CU=%d LDS bytes/workgroup=%zu\n", a.m, blocks, per_cu,
-                   bytes);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWideThreads), bytes, s, a);
+    blocks = wide_launch(vecchia_rows_wide_kernel<decltype(cov)::value>, a, a.m, a.r1 - a.r0, "rows wide", "", s);
   });
-  HIP_CHECK(hipGetLastError());
   return blocks;
 }
 
