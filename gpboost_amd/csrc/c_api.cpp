@@ -22,6 +22,7 @@
 #include "latent_test.h"
 #include "re_model.h"
 #include "sparse_chol.h"
+#include "vecchia_host.h"
 #include "grouped_test.h"
 #include "lik_test.h"
 #include "fitc_test.h"
@@ -1089,6 +1090,13 @@ int GPB_TestVecchiaFisherRows(const double* X, const int32_t* nbr, int n, int d,
                               double* dD) {
   API_BEGIN();
   gpb_amd::test_vecchia_fisher_rows(X, nbr, n, d, m, cov_type, var, phi, Bv, dBv_var, dBv, Dinv, dD_var, dD);
+  API_END();
+}
+
+int GPB_TestVecchiaNeighbors(const double* x, int n, int d, int m, int row_begin, int row_end, int end_search_at,
+                             int use_gpu, int32_t* out, int64_t out_len) {
+  API_BEGIN();
+  gpb_amd::test_vecchia_neighbors(x, n, d, m, row_begin, row_end, end_search_at, use_gpu, out, out_len);
   API_END();
 }
 

@@ -243,7 +243,7 @@ REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor, co
     if (cfg_.num_neighbors < 1) Fatal("num_neighbors must be >= 1");
     const int m = cfg_.num_neighbors;
     std::vector<int> nbr((size_t)n * m, -1);
-    if (m > 64 || d > 3) vecchia_neighbors(coords_vo_.data(), n, d, m, 0, n, nbr.data());
+    if (m > 128 || d > 3) vecchia_neighbors(coords_vo_.data(), n, d, m, 0, n, nbr.data());
     else vecchia_neighbors_gpu(coords_vo_.data(), n, d, m, 0, n, nbr.data(), stream_);
     d_X_.alloc((size_t)n * d);
     HIP_CHECK(hipMemcpyAsync(d_X_.get(), coords_vo_.data(), sizeof(double) * n * d, hipMemcpyHostToDevice, stream_));
@@ -355,7 +355,7 @@ void REModelAMD::BuildVecchiaStructure() {
   nbr_row0_ = row_begin_;
   d_rows_dist_.release();   // distances of the old neighbour sets / row block; rebuilt at the next row launch
   static const bool host_knn = std::getenv("GPBOOST_AMD_HOST_KNN") != nullptr;   // A/B: host OpenMP search
-  if (host_knn || m > 64 || cfg_.d > 3)
+  if (host_knn || m > 128 || cfg_.d > 3)
     vecchia_neighbors(coords_vo_.data(), n, cfg_.d, m, row_begin_, row_end_, nbr_.data());
   else
     vecchia_neighbors_gpu(coords_vo_.data(), n, cfg_.d, m, row_begin_, row_end_, nbr_.data(), stream_);

@@ -158,13 +158,13 @@ std::vector<double> REModelAMD::PredCoords(const PredictCall& c, int n_obs, bool
 
 // mp neighbours of rows [row_begin, na) of xa among the earlier points up to end_at (-1: all of them), by the
 // reference's sweep on the GPU (find_nearest_neighbors_Vecchia_fast, Vecchia_utils.cpp:1729-1737). The Vecchia
-// paths' row kernel takes at most 64; the full-scale model searches on the host beyond that, and the unused
-// slots of its first rows (fewer candidates than mp) are -1.
+// paths' row kernel takes at most 64; the full-scale model takes more (the search is on the GPU up to 128, on the
+// host beyond that), and the unused slots of its first rows (fewer candidates than mp) are -1.
 std::vector<int> REModelAMD::PredNeighbors(const std::vector<double>& xa, int na, int mp, int row_begin, int end_at) {
   if (mp > 64 && !vif_) Fatal("num_neighbors_pred = %d > 64 is not supported by the GPU prediction kernel", mp);
   const int d = cfg_.d;
   std::vector<int> nb((size_t)(na - row_begin) * mp, -1);
-  if (d <= 3 && mp <= 64) vecchia_neighbors_gpu(xa.data(), na, d, mp, row_begin, na, nb.data(), stream_, end_at);
+  if (d <= 3 && mp <= 128) vecchia_neighbors_gpu(xa.data(), na, d, mp, row_begin, na, nb.data(), stream_, end_at);
   else vecchia_neighbors(xa.data(), na, d, mp, row_begin, na, nb.data(), end_at);
   if (vif_ && end_at < 0)
     for (int i = row_begin; i < na; ++i)

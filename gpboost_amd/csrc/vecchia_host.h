@@ -2,6 +2,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <vector>
 
 namespace gpb_amd {
@@ -17,10 +18,14 @@ std::vector<int> vecchia_order(int n, int seed, bool random);
 // Vecchia_utils.cpp:1716-1718, 751-753).
 void vecchia_neighbors(const double* x, int n, int d, int m, int row_begin, int row_end, int* nbr,
                        int end_search_at = -1);
-// Same lists, searched on the GPU (vecchia_knn.hip): one thread per row runs the identical
-// sweep; bit-identical output. Synchronous on stream s.
+// Same lists, searched on the GPU (vecchia_knn.hip): one thread per row (m <= 64) or one wave per
+// row (65 <= m <= 128) runs the identical sweep; bit-identical output. d in 1..3. Synchronous on stream s.
 void vecchia_neighbors_gpu(const double* x, int n, int d, int m, int row_begin, int row_end, int* nbr,
                            hipStream_t s, int end_search_at = -1);
+// GPB_TestVecchiaNeighbors (include/gpboost_amd.h): either search on caller-given points, on the default
+// stream; every extent is checked on the host before anything is launched.
+void test_vecchia_neighbors(const double* x, int n, int d, int m, int row_begin, int row_end, int end_search_at,
+                            int use_gpu, int32_t* out, int64_t out_len);
 
 // Unique locations among the rows of x (row-major n x d), the reference's
 // DetermineUniqueDuplicateCoordsFast (GP_utils.cpp:451-536): candidates grouped by their coordinate

@@ -607,6 +607,14 @@ GPBOOST_AMD_EXPORT int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, d
 GPBOOST_AMD_EXPORT int GPB_TestVecchiaFisherRows(const double* X, const int32_t* nbr, int n, int d, int m,
                                                  int cov_type, double var, double phi, double* Bv, double* dBv_var,
                                                  double* dBv, double* Dinv, double* dD_var, double* dD);
+/* The Vecchia neighbour search on host arrays: the lists of the rows [row_begin, row_end) of the points x (n x d
+ * row-major, finite) among the earlier points j <= end_search_at (-1: n - 2, the likelihood's setting; prediction
+ * rows after n_obs observed points pass n_obs - 1). use_gpu != 0: vecchia_neighbors_gpu (d in 1..3; m <= 64 one
+ * thread per row, 65 to 128 one wave per row, m > 128 an error return), else the host sweep vecchia_neighbors; the
+ * two are bit-identical. out: (row_end - row_begin) x m (out_len), row i holding min(i, m) indices by ascending
+ * distance and -1 after them for i <= m. 1 <= m <= n - 1. Every extent is checked on the host before any launch. */
+GPBOOST_AMD_EXPORT int GPB_TestVecchiaNeighbors(const double* x, int n, int d, int m, int row_begin, int row_end,
+                                                int end_search_at, int use_gpu, int32_t* out, int64_t out_len);
 
 /* The full-scale Vecchia ("VIF") row factor, sparse products and vector kernels on host arrays, launched by the
  * host launch functions VifSolver uses (csrc/vif.h). No reference counterpart (tests). Everything is checked on
