@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "coef.h"
+#include "cov.h"
+#include "kernels.h"
 #include "grouped_model.h"
 #include "laplace_newton.h"
 #include "latent_test.h"
@@ -208,9 +210,13 @@ int GPB_CreateREModel(int32_t num_data, const int32_t* cluster_ids_data, const c
     slopes.drop = drop_intercept_group_rand_effect;
     std::unique_ptr<GroupedModel> gm(
         new GroupedModel(num_data, levels, mim, seed, std::move(index), lik_name, slopes));
-    if (num_gp == 1)
-      gm->AttachGP(dim_gp_coords, gp_coords_data, gpb_amd::parse_cov(str_or(cov_fct, "exponential"), cov_fct_shape),
-                   seed);
+    if (num_gp == 1) {
+      const int cov_type = gpb_amd::parse_cov(str_or(cov_fct, "exponential"), cov_fct_shape);
+      if (cov_type == gpb_amd::kMaternGeneral)
+        gpb_amd::Fatal("cov_fct 'matern' with cov_fct_shape = %g is not supported for models that combine a Gaussian "
+                       "process with grouped random effects by gpboost_amd (supported shapes: 0.5, 1.5, 2.5)", cov_fct_shape);
+      gm->AttachGP(dim_gp_coords, gp_coords_data, cov_type, seed);
+    }
     auto* g = gm.release();
     {
       std::lock_guard<std::mutex> lk(g_grouped_mu);
@@ -1164,6 +1170,12 @@ int GPB_TestDenseBatch(int cov_type, int C, int d, const int32_t* ptr, int64_t p
   API_BEGIN();
   gpb_amd::test_dense_batch(cov_type, C, d, ptr, ptr_len, X, x_len, y, y_len, var, phi, want_grad, sums, sums_len, u,
                             u_len, info, info_len);
+  API_END();
+}
+
+int GPB_TestMaternGeneral(double nu, int n, const double* x, double* c, double* dc) {
+  API_BEGIN();
+  gpb_amd::test_matern_general(nu, n, x, c, dc);
   API_END();
 }
 

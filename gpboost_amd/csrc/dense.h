@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "matern_general.h"
 
 namespace gpb_amd {
 
@@ -35,6 +36,8 @@ class DenseSolver {
   // components): Psi gains sum_k tau_k [lev_k(i) == lev_k(j)] (d_lev: device K x n level indices, K <= 8)
   // in every build; K = 0 switches it off. Predictions then take the prediction points' levels (SetGroupedPred:
   // device K x np, -1 - id for a label not in the training data, equal ids for equal new labels).
+  // cov_type kMaternGeneral (Eval, Factor and what builds on them; Fisher and Predict do not serve it): the shape
+  void SetMaternGeneral(const MaternGeneralPars& mg) { mg_ = mg; }
   void SetGrouped(int K, const int* d_lev, const double* tau);
   void SetGroupedPred(int np, const int* d_plev);
   // After Eval(want_grad = true): tr(Psi^-1 dPsi / dlog tau_k) = tau_k sum_{lev_k(i) == lev_k(j)} (Psi^-1)_ij
@@ -57,6 +60,9 @@ class DenseSolver {
   const int* g_lev_ = nullptr;
   const int* g_plev_ = nullptr;
   double g_tau_[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+  MaternGeneralPars mg_{};
+  const MaternGeneralPars& MgShape() const;
+  void BuildPsi(int cov_type, double var, double phi);
   DevBuf<double> g_part_;
   DevBuf<int> info_;
   double* h_red_ = nullptr;

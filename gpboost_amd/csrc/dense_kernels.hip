@@ -280,7 +280,8 @@ gemm_f64_splitk_big_kernel(GemmArgs g, int kchunk, long cstride) {
 // Lower triangle (i >= j) of Psi = Sigma + I, tile-parallel, upper tiles skipped.
 template <int COV>
 __global__ void __launch_bounds__(256) build_psi_kernel(const double* __restrict__ X, int n, int d, int ld,
-                                                        double var, double phi, double* __restrict__ A) {
+                                                        double var, double phi, double* __restrict__ A,
+                                                        CovShape<COV> sh = {}) {
   const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
   if (j0 > i0 + 63) return;
   const int ti = threadIdx.x & 63;
@@ -294,7 +295,7 @@ __global__ void __launch_bounds__(256) build_psi_kernel(const double* __restrict
       double s = 0.;
       for (int q = 0; q < d; ++q) { const double t = X[(size_t)i * d + q] - X[(size_t)j * d + q]; s += t * t; }
       double dc;
-      cov_dcov<COV>(sqrt(s), var, phi, v, dc);
+      cov_dcov_s<COV>(sqrt(s), var, phi, sh, v, dc);
     }
     A[(size_t)i + (size_t)j * ld] = v;
   }
@@ -673,7 +674,8 @@ __global__ void __launch_bounds__(256) trmv_lower_t_kernel(const double* W, int 
 template <int COV>
 __global__ void __launch_bounds__(256) dense_grad_kernel(const double* __restrict__ X, int n, int d, int ld,
                                                          double var, double phi, const double* __restrict__ P,
-                                                         const double* __restrict__ yaux, double* __restrict__ part) {
+                                                         const double* __restrict__ yaux, double* __restrict__ part,
+                                                         CovShape<COV> sh = {}) {
   const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
   const int tile = blockIdx.y * gridDim.x + blockIdx.x;
   double s[4] = {0., 0., 0., 0.};
@@ -693,7 +695,7 @@ __global__ void __launch_bounds__(256) dense_grad_kernel(const double* __restric
       } else {
         double ss = 0.;
         for (int q = 0; q < d; ++q) { const double t = xi[q] - X[(size_t)j * d + q]; ss += t * t; }
-        cov_dcov<COV>(sqrt(ss), var, phi, c, dc);
+        cov_dcov_s<COV>(sqrt(ss), var, phi, sh, c, dc);
       }
       const double w = (i == j) ? 1. : 2.;
       const double yy = w * yi * yaux[j];
@@ -1258,6 +1260,27 @@ void DenseSolver::PotrfLookahead() {
 
 void DenseSolver::Trtri(int a, int b) { trtri_lower(stream_, A_.get(), W_.get(), T_.get(), a, b, ld_); }
 
+// The shape of a kMaternGeneral model (SetMaternGeneral); the engines that do not serve it stop at dispatch_cov
+const MaternGeneralPars& DenseSolver::MgShape() const {
+  if (!(mg_.nu > 0.)) Fatal("the Matern shape (cov_fct_shape) has not been set for the dense engine");
+  return mg_;
+}
+
+// Psi = Sigma + I (lower triangle) into A_; the general-shape Matern is a switch of its own, not one of dispatch_cov's
+void DenseSolver::BuildPsi(int cov_type, double var, double phi) {
+  const int n = n_, nt = (n + 63) / 64;
+  if (cov_type == kMaternGeneral) {
+    hipLaunchKernelGGL((build_psi_kernel<kMaternGeneral>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d_, ld_, var,
+                       phi, A_.get(), MgShape());
+  } else {
+    dispatch_cov(cov_type, [&](auto c) {
+      hipLaunchKernelGGL((build_psi_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d_, ld_,
+                         var, phi, A_.get(), NoShape{});
+    });
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 void DenseSolver::Eval(int cov_type, double var, double phi, const double* d_y, bool want_grad, double* sums,
                        double* kernel_ms) {
   const int n = n_, ld = ld_, d = d_;
@@ -1270,11 +1293,7 @@ void DenseSolver::Eval(int cov_type, double var, double phi, const double* d_y, 
   HIP_CHECK(hipMemsetAsync(info_.get(), 0, sizeof(int), stream_));
   HIP_CHECK(hipEventRecord(ev_[0], stream_));
   const int nt = (n + 63) / 64;
-  dispatch_cov(cov_type, [&](auto c) {
-    hipLaunchKernelGGL((build_psi_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld, var,
-                       phi, A);
-  });
-  HIP_CHECK(hipGetLastError());
+  BuildPsi(cov_type, var, phi);
   AddGrouped();
   static const bool no_lookahead = std::getenv("GPBOOST_AMD_DENSE_NO_LOOKAHEAD") != nullptr;   // A/B
   if (!no_lookahead)
@@ -1295,10 +1314,15 @@ void DenseSolver::Eval(int cov_type, double var, double phi, const double* d_y, 
     // y_aux = W^T z ; P = W^T W (lower) into A (L no longer needed)
     hipLaunchKernelGGL(trmv_lower_t_kernel, dim3((n + 3) / 4), dim3(256), 0, stream_, W, ld, n, z, yaux);
     gemm(stream_, n, n, n, 1., W, ld, 1, W, ld, 0, 0., A, ld, 1, 0, 1, 1);
-    dispatch_cov(cov_type, [&](auto c) {
-      hipLaunchKernelGGL((dense_grad_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld,
-                         var, phi, A, yaux, dred + 16);
-    });
+    if (cov_type == kMaternGeneral) {
+      hipLaunchKernelGGL((dense_grad_kernel<kMaternGeneral>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld, var,
+                         phi, A, yaux, dred + 16, MgShape());
+    } else {
+      dispatch_cov(cov_type, [&](auto c) {
+        hipLaunchKernelGGL((dense_grad_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld,
+                           var, phi, A, yaux, dred + 16, NoShape{});
+      });
+    }
     HIP_CHECK(hipGetLastError());
     ngrad = nt * nt;
     launch_sum_blocks(dred + 16, ngrad, 4, dred + 2, stream_);
@@ -1336,7 +1360,7 @@ void DenseSolver::Fisher(int cov_type, double var, double phi, double dscale, do
   const int nt = (n + 63) / 64;
   dispatch_cov(cov_type, [&](auto c) {
     hipLaunchKernelGGL((build_psi_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld, var,
-                       phi, A);
+                       phi, A, NoShape{});
   });
   HIP_CHECK(hipGetLastError());
   AddGrouped();
@@ -1402,14 +1426,9 @@ void DenseSolver::GroupedTraces(double* s2, double* yaux) {
 }
 
 void DenseSolver::Factor(int cov_type, double var, double phi) {
-  const int n = n_, ld = ld_, d = d_;
+  const int n = n_;
   HIP_CHECK(hipMemsetAsync(info_.get(), 0, sizeof(int), stream_));
-  const int nt = (n + 63) / 64;
-  dispatch_cov(cov_type, [&](auto c) {
-    hipLaunchKernelGGL((build_psi_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld, var,
-                       phi, A_.get());
-  });
-  HIP_CHECK(hipGetLastError());
+  BuildPsi(cov_type, var, phi);
   AddGrouped();
   PotrfLookahead();
   Trtri(0, n);

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "matern_general.h"
+
 namespace gpb_amd {
 
 // Number of partial sums per Vecchia row reduction:
@@ -33,6 +35,7 @@ struct VecchiaRowsArgs {
   int prio;              // 16-lane kernel: 1 = the two waves of a SIMD take turns at the higher issue priority, trip by
                          // trip, and every wave lowers its own for the elimination (vecchia_rows16.hip); set by
                          // the launcher, whatever the caller puts here is ignored
+  MaternGeneralPars mg;  // kMaternGeneral only (the wave-per-row and the wide kernel): the shape constants
 #ifdef GPBOOST_AMD_ROWS16_PHASE
   unsigned long long* phase;   // instrumented variant only: per-wave clock records (vecchia_rows16.hip)
 #endif
@@ -51,6 +54,11 @@ int launch_vecchia_rows16(int cov_type, const VecchiaRowsArgs& a, hipStream_t s)
 constexpr int kRowsWideMaxM = 128;
 constexpr int kRowsWideMaxBlocks = 2048;
 int launch_vecchia_rows_wide(int cov_type, const VecchiaRowsArgs& a, hipStream_t s);
+// Wave-per-row form for the Matern covariance with a general shape (kMaternGeneral, a.mg) and m <= 64
+// (vecchia_rows_bessel.hip), same contract; sched, R and prio are ignored. Its grid never exceeds kRowsWideMaxBlocks.
+int launch_vecchia_rows_bessel(const VecchiaRowsArgs& a, hipStream_t s);
+// cov.h matern_general as the device runs it, at var = 1 on n host arguments (GPB_TestMaternGeneral)
+void test_matern_general(double nu, int n, const double* x, double* c, double* dc);
 // The last 16-lane launch of this process: trips per wave R and VecchiaRowsArgs::prio as launched
 void vecchia_rows16_last_launch(int* trips, int* prio);
 // True when launch_vecchia_rows would run the 16-lane form for this m (the A/B environment switches included)

@@ -430,7 +430,7 @@ double REModelAMD::InitialRangeTrafo() const {
     std::vector<double> X0((size_t)n0 * d);
     for (int i = 0; i < n0; ++i)
       for (int q = 0; q < d; ++q) X0[(size_t)i * d + q] = coords_[(size_t)cl_.rows[i] * d + q];
-    return init_range_trafo(X0, d, cfg_.cov_type, rng);
+    return init_range_trafo(X0, d, cfg_.cov_type, rng, cfg_.shape);
   }
   const std::vector<double>& X = fitc_ ? fitc_->inducing_points() : coords_vo_;
   if ((int)(X.size() / cfg_.d) > 1000) {
@@ -441,10 +441,10 @@ double REModelAMD::InitialRangeTrafo() const {
       std::shuffle(dummy.begin(), dummy.end(), rng);
     }
   }
-  return init_range_trafo(X, cfg_.d, cfg_.cov_type, rng);
+  return init_range_trafo(X, cfg_.d, cfg_.cov_type, rng, cfg_.shape);
 }
 
-double init_range_trafo(const std::vector<double>& X, int d, int cov_type, std::mt19937& rng) {
+double init_range_trafo(const std::vector<double>& X, int d, int cov_type, std::mt19937& rng, double nu) {
   const int n = (int)(X.size() / d);
   const int kMaxPoints = 1000;
   const int nf = std::min(n, kMaxPoints);
@@ -476,6 +476,7 @@ double init_range_trafo(const std::vector<double>& X, int d, int cov_type, std::
     case kMatern05: return 2. * 3. / med;
     case kMatern15: return 2. * 4.7 / med;
     case kMatern25: return 2. * 5.9 / med;
+    case kMaternGeneral: return 2. * (nu <= 1. ? 3. : (nu <= 2. ? 4.7 : 5.9)) / med;   // cov_fcts.h:1440-1450
     default: return 3. / std::pow(med / 2., 2.);
   }
 }
@@ -521,8 +522,8 @@ void REModelAMD::InitCovParsIfNotDefined(const double* y, const double* fixed_ef
   }
   double trafo[3];
   FindInitCovPar(yv.data(), trafo);
-  if (cfg_.latent) cov_pars_orig_ = {trafo[0], range_back(cfg_.cov_type, trafo[1])};
-  else cov_pars_orig_ = {trafo[0], trafo[1] * trafo[0], range_back(cfg_.cov_type, trafo[2])};
+  if (cfg_.latent) cov_pars_orig_ = {trafo[0], range_back(cfg_.cov_type, trafo[1], cfg_.shape)};
+  else cov_pars_orig_ = {trafo[0], trafo[1] * trafo[0], range_back(cfg_.cov_type, trafo[2], cfg_.shape)};
   init_used_ = cov_pars_orig_;
   cov_pars_initialized_ = true;
 }
@@ -771,6 +772,7 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
   // (re_model_template.h:846-1700) -> OptimExternal "lbfgs" (optim_utils.h:561-706)
   if (called_in_boosting) RefuseClusters("the GPBoost-algorithm covariance update (GPB_OptimCovParBoosting)");
   if (isettings_.optimizer == "fisher_scoring") RefuseClusters("optimizer_cov = 'fisher_scoring'");
+  RefuseGeneralShapeFisher();
   UseDevice();
   const int n = cfg_.n;
   if (reuse_lr && !called_in_boosting)
@@ -834,8 +836,8 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
     aux_pars_set_ = true;   // SetAuxPars marks them set (likelihoods.h:1809): a refit continues from here
   }
   std::vector<double> start_orig;
-  if (cfg_.latent) start_orig = {trafo[0], range_back(cfg_.cov_type, trafo[1])};
-  else start_orig = {trafo[0], trafo[1] * trafo[0], range_back(cfg_.cov_type, trafo[2])};
+  if (cfg_.latent) start_orig = {trafo[0], range_back(cfg_.cov_type, trafo[1], cfg_.shape)};
+  else start_orig = {trafo[0], trafo[1] * trafo[0], range_back(cfg_.cov_type, trafo[2], cfg_.shape)};
   if (!cov_pars_initialized_) init_used_ = start_orig;   // FindInitCovPar's values (re_model.cpp:1159-1160)
   if (optim_.max_iterations <= 0) {   // max_iter_ = 0 (re_model_template.h:1223): the parameters stay at their initial values
     num_it_ = 0;
@@ -864,7 +866,7 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
       };
       num_it_ = nelder_mead(fn, x, isettings_.max_iter, tol_obj, tol_sol, &fx);
       fn(x);   // OptimExternal re-evaluates at the solution for the profiled sigma^2 (:683-686)
-      cov_pars_orig_ = {s2, std::exp(x[0]) * s2, range_back(cfg_.cov_type, std::exp(x[1]))};
+      cov_pars_orig_ = {s2, std::exp(x[0]) * s2, range_back(cfg_.cov_type, std::exp(x[1]), cfg_.shape)};
     } else {   // x = log(sigma1^2, phi[, aux]); the Laplace mode continues from the previous evaluation
       x = {std::log(trafo[0]), std::log(trafo[1])};
       if (with_aux) x.push_back(std::log(aux_pars_[0]));
@@ -879,7 +881,7 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
         return r.nll;
       };
       num_it_ = nelder_mead(fn, x, isettings_.max_iter, tol_obj, tol_sol, &fx);
-      cov_pars_orig_ = {std::exp(x[0]), range_back(cfg_.cov_type, std::exp(x[1]))};
+      cov_pars_orig_ = {std::exp(x[0]), range_back(cfg_.cov_type, std::exp(x[1]), cfg_.shape)};
       if (with_aux) aux_pars_[0] = std::exp(x[2]);
     }
   } else if (isettings_.optimizer == "gradient_descent" && cfg_.latent) {
@@ -966,7 +968,7 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
     }
     fx = nll;
     x = {std::log(pars[0]), std::log(pars[1])};
-    cov_pars_orig_ = {pars[0], range_back(cfg_.cov_type, pars[1])};
+    cov_pars_orig_ = {pars[0], range_back(cfg_.cov_type, pars[1], cfg_.shape)};
     if (with_aux) aux_pars_[0] = pars[2];
   } else if (!isettings_.optimizer.empty()) {   // "gradient_descent" / "fisher_scoring" (re_model_template.h:1287-1549)
     if (cfg_.latent)
@@ -977,19 +979,19 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
     std::vector<double> tv(trafo, trafo + 3);
     InternalAdapter obj(this);
     num_it_ = internal_optimize(obj, tv, isettings_, &fx);
-    cov_pars_orig_ = {tv[0], tv[1] * tv[0], range_back(cfg_.cov_type, tv[2])};
+    cov_pars_orig_ = {tv[0], tv[1] * tv[0], range_back(cfg_.cov_type, tv[2], cfg_.shape)};
   } else if (!cfg_.latent) {
     x = {std::log(trafo[1]), std::log(trafo[2])};
     GaussianProfiledObjective obj(this, est_idx_, trafo[0], trafo[1] * trafo[0]);
     num_it_ = lbfgs_minimize(obj, x, fx, optim_, &m_bfgs_, reuse_m_bfgs);
     const double s2 = obj.sigma2();
-    cov_pars_orig_ = {s2, obj.tau_at(x) * s2, range_back(cfg_.cov_type, std::exp(x[1]))};
+    cov_pars_orig_ = {s2, obj.tau_at(x) * s2, range_back(cfg_.cov_type, std::exp(x[1]), cfg_.shape)};
   } else {
     x = {std::log(trafo[0]), std::log(trafo[1])};
     if (with_aux) x.push_back(std::log(aux_pars_[0]));
     LatentObjective obj(this, with_aux, est_idx_);
     num_it_ = lbfgs_minimize(obj, x, fx, optim_, &m_bfgs_, reuse_m_bfgs);
-    cov_pars_orig_ = {std::exp(x[0]), range_back(cfg_.cov_type, std::exp(x[1]))};
+    cov_pars_orig_ = {std::exp(x[0]), range_back(cfg_.cov_type, std::exp(x[1]), cfg_.shape)};
     if (with_aux) aux_pars_[0] = std::exp(x[2]);
   }
   for (double v : x)
@@ -1008,7 +1010,14 @@ void REModelAMD::InitializeOptimizerNames() {
   if (optimizer_coef_.empty()) optimizer_coef_ = cfg_.latent ? "lbfgs" : "wls";
 }
 
+void REModelAMD::RefuseGeneralShapeFisher() const {
+  if (isettings_.optimizer == "fisher_scoring" && cfg_.cov_type == kMaternGeneral)
+    Fatal("optimizer_cov = 'fisher_scoring' is not supported for cov_fct 'matern' with cov_fct_shape = %g by gpboost_amd "
+          "(use 'lbfgs' or 'gradient_descent'; supported shapes: 0.5, 1.5, 2.5)", cfg_.shape);
+}
+
 void REModelAMD::OptimLinRegrCoefCovPar(const double* y, const double* X, int p, const double* fixed_effects) {
+  RefuseGeneralShapeFisher();
   if (X != nullptr && p > 0) RefuseClusters("linear regression covariates (X)");
   if (!est_idx_.empty() && X != nullptr && p > 0)
     Fatal("estimate_cov_par_index (fixing covariance parameters) with linear regression covariates is not supported by "
@@ -1064,7 +1073,7 @@ void REModelAMD::OptimLinRegrCoefCovPar(const double* y, const double* X, int p,
       for (int i = 0; i < n; ++i) yv[i] -= fixed_effects[i];
     FindInitCovPar(yv.data(), trafo);
   }
-  const std::vector<double> start_orig = {trafo[0], trafo[1] * trafo[0], range_back(cfg_.cov_type, trafo[2])};
+  const std::vector<double> start_orig = {trafo[0], trafo[1] * trafo[0], range_back(cfg_.cov_type, trafo[2], cfg_.shape)};
   if (!cov_pars_initialized_) init_used_ = start_orig;
   if (optim_.max_iterations <= 0) {   // parameters stay; coefficients by GLS at them
     num_it_ = 0;
@@ -1114,7 +1123,7 @@ void REModelAMD::OptimLinRegrCoefCovPar(const double* y, const double* X, int p,
     InternalAdapter obj(this);
     double fx = 0.;
     num_it_ = internal_optimize(obj, tv, isettings_, &fx, &hook);
-    cov_pars_orig_ = {tv[0], tv[1] * tv[0], range_back(cfg_.cov_type, tv[2])};
+    cov_pars_orig_ = {tv[0], tv[1] * tv[0], range_back(cfg_.cov_type, tv[2], cfg_.shape)};
     coef_ = hook.beta();
     for (double v : coef_)
       if (std::isnan(v) || std::isinf(v)) Fatal("NaN or Inf occurred in the linear regression coefficients");
@@ -1134,7 +1143,7 @@ void REModelAMD::OptimLinRegrCoefCovPar(const double* y, const double* X, int p,
     if (std::isnan(v) || std::isinf(v))
       Fatal("NaN or Inf occurred in covariance parameter optimization using 'lbfgs' (the reference's nelder_mead restart is not supported by gpboost_amd)");
   const double s2 = obj.sigma2();
-  cov_pars_orig_ = {s2, std::exp(x[0]) * s2, range_back(cfg_.cov_type, std::exp(x[1]))};
+  cov_pars_orig_ = {s2, std::exp(x[0]) * s2, range_back(cfg_.cov_type, std::exp(x[1]), cfg_.shape)};
   coef_ = obj.beta();
   for (double v : coef_)
     if (std::isnan(v) || std::isinf(v)) Fatal("NaN or Inf occurred in the linear regression coefficients");
@@ -1151,6 +1160,9 @@ void REModelAMD::GetInitCovPar(double* out) const {
 }
 
 void REModelAMD::StdDevCovPars(const double* orig, double* sd) {
+  if (cfg_.cov_type == kMaternGeneral)
+    Fatal("standard errors of the covariance parameters are not supported for cov_fct 'matern' with cov_fct_shape = %g "
+          "by gpboost_amd (supported shapes: 0.5, 1.5, 2.5)", cfg_.shape);
   // CalcFisherInformation, dense branch (re_model_template.h:9179-9230), transf_scale = false,
   // include_error_var = true: with Sigma^-1 = Psi^-1 / sigma^2 and dSigma_k on the original scale
   // (sigma^2: I; sigma1^2: the correlation matrix; rho: sigma1^2 dcorr/drho)

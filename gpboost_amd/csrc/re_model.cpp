@@ -45,7 +45,10 @@ int parse_cov(const std::string& name, double shape) {
     if (eq(shape, 0.5)) return kMatern05;
     if (eq(shape, 1.5)) return kMatern15;
     if (eq(shape, 2.5)) return kMatern25;
-    Fatal("cov_fct 'matern' with shape %g is not supported by gpboost_amd (supported: 0.5, 1.5, 2.5)", shape);
+    // any other smoothness: CovarianceMaternGeneralShape (cov_fcts.h:1701-1715), cov.h matern_general
+    if (!(shape > 0.) || shape > kMaternGeneralMaxShape)
+      Fatal("cov_fct 'matern' needs 0 < cov_fct_shape <= %g, got %g", kMaternGeneralMaxShape, shape);
+    return kMaternGeneral;
   }
   if (name == "gaussian" || name == "Gaussian") return kGaussian;
   Fatal("cov_fct '%s' is not supported by gpboost_amd (supported: exponential, matern, gaussian)", name.c_str());
@@ -58,8 +61,14 @@ bool check_convergence_criterion(const std::string& name) {
   return false;
 }
 
-double range_trafo(int cov_type, double rho) {
+static double general_shape(double nu) {
+  if (!(nu > 0.)) Fatal("the range transform of cov_fct 'matern' with a general cov_fct_shape needs the shape");
+  return nu;
+}
+
+double range_trafo(int cov_type, double rho, double nu) {
   switch (cov_type) {
+    case kMaternGeneral: return std::sqrt(2. * general_shape(nu)) / rho;   // cov_fcts.h:454-456
     case kMatern05: return 1. / rho;
     case kMatern15: return std::sqrt(3.) / rho;
     case kMatern25: return std::sqrt(5.) / rho;
@@ -67,8 +76,9 @@ double range_trafo(int cov_type, double rho) {
   }
 }
 
-double range_back(int cov_type, double phi) {
+double range_back(int cov_type, double phi, double nu) {
   switch (cov_type) {
+    case kMaternGeneral: return std::sqrt(2. * general_shape(nu)) / phi;
     case kMatern05: return 1. / phi;
     case kMatern15: return std::sqrt(3.) / phi;
     case kMatern25: return std::sqrt(5.) / phi;
@@ -89,6 +99,20 @@ REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor, co
   // likelihood and approximation (re_model_template.h:207-211, 563; likelihoods.h:240-257)
   cfg_.lik = parse_likelihood(cfg_.likelihood);
   refuse_grouped_only_likelihood(cfg_.lik, cfg_.likelihood);
+  if (cfg_.cov_type == kMaternGeneral) {
+    // served: the exact Gaussian Vecchia path (the wave-per-row and the wide row kernel) and the exact dense path
+    if (cfg_.lik != kLikGaussian || cfg_.gp_approx == "vecchia_latent")
+      Fatal("cov_fct 'matern' with cov_fct_shape = %g is supported for likelihood 'gaussian' with gp_approx 'vecchia' or "
+            "'none' only (likelihood '%s', gp_approx '%s'); the shapes 0.5, 1.5 and 2.5 serve every model",
+            cfg_.shape, cfg_.likelihood.c_str(), cfg_.gp_approx.c_str());
+    if (cfg_.gp_approx != "vecchia" && cfg_.gp_approx != "none")
+      Fatal("cov_fct 'matern' with cov_fct_shape = %g is not supported for gp_approx = '%s' by gpboost_amd (supported: "
+            "vecchia, none; the shapes 0.5, 1.5 and 2.5 serve every approximation)", cfg_.shape, cfg_.gp_approx.c_str());
+    if (several)
+      Fatal("cov_fct 'matern' with cov_fct_shape = %g is not supported with several clusters (cluster_ids) by "
+            "gpboost_amd (supported shapes there: 0.5, 1.5, 2.5)", cfg_.shape);
+    cfg_.mg = matern_general_pars(cfg_.shape);
+  }
   if (cfg_.gp_approx == "vecchia_latent") {
     vecchia_ = true;
     cfg_.latent = true;
@@ -288,6 +312,7 @@ REModelAMD::REModelAMD(const ModelConfig& cfg, const double* coords_colmajor, co
       std::iota(perm_.begin(), perm_.end(), 0);
     } else {
       dense_.reset(new DenseSolver(n, d, d_X_.get(), stream_));
+      dense_->SetMaternGeneral(cfg_.mg);   // kMaternGeneral: the shape, for every call that builds Psi
     }
   }
   d_sums_.alloc(16);
@@ -443,7 +468,7 @@ void REModelAMD::TransformCovPars(const double* orig, double* trafo) const {
   if (!(orig[0] > 0. && orig[1] > 0. && orig[2] > 0.)) Fatal("covariance parameters must be > 0");
   trafo[0] = orig[0];
   trafo[1] = orig[1] / orig[0];
-  trafo[2] = range_trafo(cfg_.cov_type, orig[2]);
+  trafo[2] = range_trafo(cfg_.cov_type, orig[2], cfg_.shape);
 }
 
 void REModelAMD::SetY(const double* y) {
@@ -557,6 +582,7 @@ void REModelAMD::LaunchVecchiaRows(const double* trafo, int r0, int r1, double* 
   a.diag_mult = 1.;   // Gaussian likelihood: nugget 1 on the transformed scale (Vecchia_utils.cpp:1540)
   a.diag_add = 1.;
   a.d_nugget = 1.;
+  a.mg = cfg_.mg;
   if (d_block_sums_.size() == 0)   // built as a latent model and switched to the Gaussian likelihood
     d_block_sums_.alloc((size_t)std::max(vecchia_rows_blocks(row_end_ - row_begin_, a.m), 1) * kVecchiaSums);
   a.block_sums = d_block_sums_.get();
@@ -670,7 +696,7 @@ void REModelAMD::EvalDense(const double* trafo, bool want_grad, double* sums) {
 EvalResult REModelAMD::EvalLatent(const double* cov_pars_orig, bool want_grad) {
   if (!(cov_pars_orig[0] > 0. && cov_pars_orig[1] > 0.)) Fatal("covariance parameters must be > 0");
   // TransformCovPars for non-Gaussian likelihoods: no division by a nugget (cov_fcts.h:438-460)
-  const double trafo[2] = {cov_pars_orig[0], range_trafo(cfg_.cov_type, cov_pars_orig[1])};
+  const double trafo[2] = {cov_pars_orig[0], range_trafo(cfg_.cov_type, cov_pars_orig[1], cfg_.shape)};
   EvalResult res = EvalLatentTrafo(trafo, want_grad);
   last_cov_pars_.assign(cov_pars_orig, cov_pars_orig + 2);
   return res;
@@ -790,7 +816,7 @@ void REModelAMD::GetLatentVecchiaFactor(const double* cov_pars_orig, double* Din
   LatentFactorArgs fa{};
   fa.X = d_X_.get(); fa.nbr = d_nbr_.get(); fa.n = n; fa.d = cfg_.d; fa.m = m;
   fa.var = cov_pars_orig[0];
-  fa.phi = range_trafo(cfg_.cov_type, cov_pars_orig[1]);
+  fa.phi = range_trafo(cfg_.cov_type, cov_pars_orig[1], cfg_.shape);
   fa.jitter = 1. + 1e-10;
   fa.Bv = b.get(); fa.dBv = e.get(); fa.Dinv = a.get(); fa.dD = c.get();
   launch_latent_factor(cfg_.cov_type, fa, stream_);
@@ -822,6 +848,7 @@ void REModelAMD::GetVecchiaFactor(const double* cov_pars_orig, double* Dinv, dou
   a.Dinv_out = dD.get();
   a.B_out = dB.get();
   a.R = RowsDist();
+  a.mg = cfg_.mg;
   launch_vecchia_rows(cfg_.cov_type, a, stream_);
   HIP_CHECK(hipMemcpyAsync(Dinv, dD.get(), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipMemcpyAsync(Bvals, dB.get(), sizeof(double) * n * m, hipMemcpyDeviceToHost, stream_));

@@ -52,6 +52,7 @@ struct ModelConfig {
   double cover_tree_radius = 1.;
   std::string ind_points_selection = "kmeans++";
   // derived
+  MaternGeneralPars mg{};  // cov_type kMaternGeneral: the constants of the shape (matern_general.h)
   bool latent = false;     // latent GP + Laplace approximation (non-Gaussian or "vecchia_latent")
   int lik = 0;             // LatentLik code when latent
 };
@@ -64,18 +65,20 @@ void refuse_grouped_only_likelihood(int lik, const std::string& name);
 void response_transform(int lik, double aux_shape, double aux_gauss, double delta_conv, hipStream_t stream, int n_pred,
                         double* mean, double* var, double* cov);
 // cov_fcts.h:438-460: range rho -> phi on the transformed scale
-// cov_fcts.h:2753-2770 ParseCovFunctionAlias (+ shape) -> kMatern05 / kMatern15 / kMatern25 / kGaussian
+// cov_fcts.h:2753-2770 ParseCovFunctionAlias (+ shape) -> kMatern05 / kMatern15 / kMatern25 / kGaussian, or
+// kMaternGeneral for any other shape in (0, kMaternGeneralMaxShape]
 int parse_cov(const std::string& name, double shape);
 // FindInitCovPar's initial transformed range (cov_fcts.h:1275-1450): median distance among the points X
 // (host row-major n x d), at most 1000 of them drawn uniformly with rng (which continues the caller's
 // generator) when n > 1000
-double init_range_trafo(const std::vector<double>& X, int d, int cov_type, std::mt19937& rng);
-double range_trafo(int cov_type, double rho);
+double init_range_trafo(const std::vector<double>& X, int d, int cov_type, std::mt19937& rng, double nu = 0.);
+// nu: the shape, needed by kMaternGeneral only (phi = sqrt(2 nu) / rho, cov_fcts.h:454-456)
+double range_trafo(int cov_type, double rho, double nu = 0.);
 // SUPPORTED_CONV_CRIT_ (re_model_template.h:756-760): true for "relative_change_in_parameters", false for
 // "relative_change_in_log_likelihood"; anything else fails
 bool check_convergence_criterion(const std::string& name);
 // cov_fcts.h TransformBackCovPars: range transform phi -> range rho
-double range_back(int cov_type, double phi);
+double range_back(int cov_type, double phi, double nu = 0.);
 
 struct EvalResult {
   double nll = 0.;
@@ -341,7 +344,8 @@ class REModelAMD {
                     double shift, bool scale_first);
   std::vector<int> FitcMatch(const std::vector<double>& xp_rowmajor, int n_pred) const;
   void ResponseTransform(int n_pred, double* mean, double* var, double* cov);
-  double range_trafo_of(double rho) const { return range_trafo(cfg_.cov_type, rho); }
+  void RefuseGeneralShapeFisher() const;   // Fisher scoring has no general-shape Matern kernels
+  double range_trafo_of(double rho) const { return range_trafo(cfg_.cov_type, rho, cfg_.shape); }
   void FindInitCovPar(const double* y, double* trafo) const;
   double InitialRangeTrafo() const;
   void BuildVecchiaStructure();

@@ -74,7 +74,7 @@ void REModelAMD::CalcGradientF(double* y, const double* fixed_effects, bool calc
     SetLatentOffset(fixed_effects);
     if (!y_set_) Fatal("Response variable data has not been set");
     EnsureStructure();
-    const double trafo[2] = {cov_pars_orig_[0], range_trafo(cfg_.cov_type, cov_pars_orig_[1])};
+    const double trafo[2] = {cov_pars_orig_[0], range_trafo(cfg_.cov_type, cov_pars_orig_[1], cfg_.shape)};
     const double aux = aux_pars_.empty() ? 1. : aux_pars_[0];
     std::vector<double> gvo(n);
     const auto start = (!calc_cov_factor && latent_evaluated_) ? LatentVecchia::ModeStart::kKeep
@@ -180,6 +180,7 @@ std::vector<double> REModelAMD::Gram(const double* trafo, bool next_eval_grad) {
   a.diag_mult = 1.; a.diag_add = 1.; a.d_nugget = 1.;
   a.Dinv_out = d_Df_.get();
   a.B_out = d_Bf_.get();
+  a.mg = cfg_.mg;
   launch_vecchia_rows(cfg_.cov_type, a, stream_);
   const int npairs = c * (c + 1) / 2;
   d_gram_part_.alloc((size_t)vecchia_gram_blocks(n) * npairs);
@@ -331,6 +332,7 @@ void REModelAMD::PsiInvVecchia(const double* trafo, double* yaux, double* diag) 
   a.diag_mult = 1.; a.diag_add = 1.; a.d_nugget = 1.;
   a.Dinv_out = d_Df_.get();
   a.B_out = d_Bf_.get();
+  a.mg = cfg_.mg;
   launch_vecchia_rows(cfg_.cov_type, a, stream_);
   DevBuf<double> u(n), ya(n), dd(n);
   launch_vecchia_psi_inv_diag(n, m, d_nbr_.get(), d_tptr_.get(), d_trow_.get(), d_tslot_.get(), d_Bf_.get(),
@@ -351,6 +353,9 @@ void REModelAMD::SetLikelihood(const std::string& likelihood) {
   c.likelihood = likelihood;
   const int lik = parse_likelihood(likelihood);
   refuse_grouped_only_likelihood(lik, likelihood);
+  if (cfg_.cov_type == kMaternGeneral && lik != kLikGaussian)
+    Fatal("cov_fct 'matern' with cov_fct_shape = %g is supported for likelihood 'gaussian' only (likelihood '%s'); the "
+          "shapes 0.5, 1.5 and 2.5 serve every likelihood", cfg_.shape, likelihood.c_str());
   const bool dense = c.gp_approx == "none";
   const bool latent = c.gp_approx == "vecchia_latent" || ((vecchia_ || fitc_ || vif_ || dense) && lik != kLikGaussian);
   if (vif_) {   // full-scale Vecchia: the Laplace solver on the same inducing points and neighbours (Cholesky)
@@ -376,7 +381,10 @@ void REModelAMD::SetLikelihood(const std::string& likelihood) {
       std::iota(perm_.begin(), perm_.end(), 0);
     } else if (!latent) {
       dense_lap_.reset();
-      if (!dense_) dense_.reset(new DenseSolver(cfg_.n, cfg_.d, d_X_.get(), stream_));
+      if (!dense_) {
+        dense_.reset(new DenseSolver(cfg_.n, cfg_.d, d_X_.get(), stream_));
+        dense_->SetMaternGeneral(cfg_.mg);
+      }
     }
     c.matrix_inversion_method = "cholesky";
   } else if (fitc_) {   // FITC: the Laplace solver on the same inducing points (Cholesky either way)

@@ -141,7 +141,7 @@ PredictPars REModelAMD::PredictPrologue(const double* y, const double* cov_pars,
   EvalLatent(p.cp, false);
   p.sigma2 = 1.;
   p.var = p.cp[0];
-  p.phi = range_trafo(cfg_.cov_type, p.cp[1]);
+  p.phi = range_trafo(cfg_.cov_type, p.cp[1], cfg_.shape);
   return p;
 }
 
@@ -201,6 +201,7 @@ void REModelAMD::PredFactorRows(const std::vector<double>& xa, int na, const std
   a.B_out = f.B.get();
   a.Dinv_out = f.Dinv.get();
   a.row_base = r0;
+  a.mg = cfg_.mg;
   launch_vecchia_rows(cfg_.cov_type, a, stream_);
 }
 
@@ -393,6 +394,9 @@ void REModelAMD::PredictLatentSim(const PredictCall& c, int n, int mp, const std
 // With a Laplace likelihood (CalcPred, re_model_template.h:10026- -> PredictLaplaceApproxStable,
 // likelihoods.h:5610-5676): latent means Sigma_po d1 and (co)variances from the factor of I + W^1/2 Sigma W^1/2.
 void REModelAMD::PredictDense(const PredictCall& c, const PredictPars& p) {
+  if (cfg_.cov_type == kMaternGeneral)
+    Fatal("predictions with gp_approx = 'none' are not supported for cov_fct 'matern' with cov_fct_shape = %g by "
+          "gpboost_amd (use gp_approx = 'vecchia'; supported shapes: 0.5, 1.5, 2.5)", cfg_.shape);
   const int n_pred = c.n_pred;
   const std::vector<double> xp = PredCoords(c);
   const bool want_var = c.var || (cfg_.latent && c.response);

@@ -1131,6 +1131,11 @@ bool vecchia_rows16_selected(int m) {   // launch_k<32>'s choice
 int launch_vecchia_rows(int cov_type, const VecchiaRowsArgs& a, hipStream_t s) {
   if (a.d < 1 || a.d > kDMax) Fatal("GPU Vecchia kernel supports 1 <= dim_gp_coords <= %d, got %d", kDMax, a.d);
   if (a.r1 <= a.r0) return 0;
+  if (cov_type == kMaternGeneral) {   // one Bessel evaluation per pair: the kernels that evaluate each pair once
+    if (a.m > kRowsWideMaxM)
+      Fatal("num_neighbors = %d > %d is not supported by the GPU Vecchia kernel", a.m, kRowsWideMaxM);
+    return a.m <= 64 ? launch_vecchia_rows_bessel(a, s) : launch_vecchia_rows_wide(cov_type, a, s);
+  }
   switch (lanes_for_m(a.m)) {
     case 16: return launch_cov<16>(cov_type, a, s);
     case 32: return launch_cov<32>(cov_type, a, s);

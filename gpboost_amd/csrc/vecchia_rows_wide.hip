@@ -44,6 +44,10 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_rows_wide_kernel(Vecchia
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int d = a.d;
   const double var = a.var, phi = a.phi;
+  const CovShape<COV> sh = [&] {
+    if constexpr (COV == kMaternGeneral) return a.mg;
+    else return NoShape{};
+  }();
   const double cdiag = var * a.diag_mult + a.diag_add;
   const double delta = cdiag - var;   // C - C_nonugget on the diagonal
   const bool want_like = a.Y != nullptr;
@@ -67,7 +71,7 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_rows_wide_kernel(Vecchia
         s += (xi - x) * (xi - x);
       }
       double c, dc;
-      cov_dcov_sq<COV>(s, var, phi, c, dc);
+      cov_dcov_sq_s<COV>(s, var, phi, sh, c, dc);
       cv[tid] = rv ? c : 0.;
       dcv[tid] = rv ? dc : 0.;
       yv[tid] = (rv && want_like) ? a.Y[nb] : 0.;
@@ -75,7 +79,7 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_rows_wide_kernel(Vecchia
     }
     __syncthreads();
 
-    wide_pairs<COV>(A, S, nbx, KP, k, var, phi, tid);   // ---- 2.
+    wide_pairs<COV>(A, S, nbx, KP, k, var, phi, tid, sh);   // ---- 2.
     __syncthreads();
     wide_chol<false, false>(A, S, KP, rd, nullptr, tid, lane, wave);   // ---- 3.
 
@@ -162,6 +166,10 @@ int launch_vecchia_rows_wide(int cov_type, const VecchiaRowsArgs& a, hipStream_t
     Fatal("num_neighbors = %d > %d is not supported by the GPU Vecchia kernel", a.m, kRowsWideMaxM);
   if (a.r1 <= a.r0) return 0;
   int blocks = 0;
+  if (cov_type == kMaternGeneral) {   // not one of dispatch_cov's: this kernel and the wave-per-row one serve it
+    if (!(a.mg.nu > 0.)) Fatal("the Matern shape (cov_fct_shape) has not been set for the general-shape row kernel");
+    return wide_launch(vecchia_rows_wide_kernel<kMaternGeneral>, a, a.m, a.r1 - a.r0, "rows wide", "", s);
+  }
   dispatch_cov(cov_type, [&](auto cov) {
     blocks = wide_launch(vecchia_rows_wide_kernel<decltype(cov)::value>, a, a.m, a.r1 - a.r0, "rows wide", "", s);
   });

@@ -66,12 +66,27 @@ __device__ __forceinline__ double wide_unscale(double x, double pv) {
   else return x * pv;
 }
 
-// pairs: e -> (h, q); q < h: (row h, column q), else (row KP - 1 - h, column q - h)
-template <int COV>
+// The barrier between the stages of a row: of the workgroup that owns it (NW waves), or, where ONE wave owns the row
+// (NW = 1, vecchia_rows_bessel.hip), of that wave alone: its LDS accesses complete in program order, so all that
+// is needed is that the compiler keeps them there.
+template <int NW>
+__device__ __forceinline__ void wide_sync() {
+  if constexpr (NW == 1) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();
+  }
+}
+
+// pairs: e -> (h, q); q < h: (row h, column q), else (row KP - 1 - h, column q - h). NT threads share them (tid is
+// the thread's index among them); sh is the covariance's shape (empty for the closed forms)
+template <int COV, int NT = kWideThreads>
 __device__ __forceinline__ void wide_pairs(double* A, int S, const double* nbx, int KP, int k, double var, double phi,
-                                           int tid) {
+                                           int tid, const CovShape<COV>& sh = {}) {
   const int npairs = (KP / 2) * (KP - 1);
-  for (int e0 = 0; e0 < npairs; e0 += kWideThreads) {   // workgroup-uniform trip count; the last trip is partial
+  for (int e0 = 0; e0 < npairs; e0 += NT) {   // workgroup-uniform trip count; the last trip is partial
     const int e = min(e0 + tid, npairs - 1);
     const int h = e / (KP - 1), q = e - h * (KP - 1);
     const int r = q < h ? h : KP - 1 - h;
@@ -83,7 +98,7 @@ __device__ __forceinline__ void wide_pairs(double* A, int S, const double* nbx, 
       s += t * t;
     }
     double cc, dc;
-    cov_dcov_sq<COV>(s, var, phi, cc, dc);
+    cov_dcov_sq_s<COV>(s, var, phi, sh, cc, dc);
     const bool valid = r < k;   // c < r
     if (e0 + tid < npairs) {
       A[r * S + c] = valid ? cc : 0.;
@@ -92,8 +107,9 @@ __device__ __forceinline__ void wide_pairs(double* A, int S, const double* nbx, 
   }
 }
 
-// Called by the whole workgroup after a barrier; ends with one. diag_out[j] = L_jj (DIV) or 1 / L_jj.
-template <bool DIV, bool BORDER>
+// Called by the whole workgroup after a barrier; ends with one. diag_out[j] = L_jj (DIV) or 1 / L_jj. NW: the waves
+// that share the row (tid over all of them; NW = 1: the row's wave takes every trailing tile itself).
+template <bool DIV, bool BORDER, int NW = kWideThreads / 64>
 __device__ __forceinline__ void wide_chol(double* A, int S, int KP, double* diag_out, double* zb, int tid, int lane,
                                           int wave) {
   const int lr = lane & 15, lq = lane >> 4;
@@ -132,7 +148,7 @@ __device__ __forceinline__ void wide_chol(double* A, int S, int KP, double* diag
 #pragma unroll
       for (int c = 0; c < kPanel; ++c) px[c] = x[c];
     }
-    __syncthreads();   // the panel is final; every wave has read the diagonal block
+    wide_sync<NW>();   // the panel is final; every wave has read the diagonal block
     if (tid < kPanel) {
 #pragma unroll
       for (int c = 0; c < kPanel; ++c) {
@@ -153,7 +169,7 @@ __device__ __forceinline__ void wide_chol(double* A, int S, int KP, double* diag
     int cnt = 0;
     for (int I = p + 1; I < NB; ++I) {
       for (int J = p + 1; J <= I; ++J, ++cnt) {
-        if ((cnt & 3) != wave) continue;
+        if ((cnt & (NW - 1)) != wave) continue;
         const double* pa = A + (I * kPanel + lr) * S + j0 + lq;
         const double* pb = A + (J * kPanel + lr) * S + j0 + lq;
         double4_t u = {0., 0., 0., 0.};
@@ -166,7 +182,7 @@ __device__ __forceinline__ void wide_chol(double* A, int S, int KP, double* diag
         }
       }
     }
-    __syncthreads();
+    wide_sync<NW>();
   }
 }
 

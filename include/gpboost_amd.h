@@ -18,7 +18,9 @@
  *
  * All 29 GPB_* functions of the reference (include/LightGBM/c_api.h:1358-1786) are exported with
  * their signatures. Scope of this build: one GP component (num_gp = 1) with
- * cov_fct in {exponential, matern (shape 0.5/1.5/2.5), gaussian}; gp_approx "none" (dense
+ * cov_fct in {exponential, matern (cov_fct_shape 0.5/1.5/2.5 everywhere; any other shape in (0, 100] for the Gaussian
+ * likelihood with gp_approx "vecchia" (likelihood, gradient, fit, factor, predictions) and "none" (likelihood,
+ * gradient, fit), every other use of such a shape fails with a message naming cov_fct_shape), gaussian}; gp_approx "none" (dense
  * Cholesky) and "vecchia" with likelihood "gaussian" (exact), "vecchia" with "bernoulli_logit" and
  * "vecchia_latent" with "gaussian" (Laplace approximation, iterative methods); linear regression
  * covariates for the Gaussian likelihood (GLS, optimizer_coef "wls"); OR grouped random effects
@@ -699,6 +701,11 @@ GPBOOST_AMD_EXPORT int GPB_TestFitcStages(int stage, int n, int m, int d, int co
                                           double var2, double phi2, const double* X, const double* Z, const double* y,
                                           int np, const double* Xp, const int32_t* match, double* const* outs,
                                           const int64_t* out_lens, int n_outs);
+/* The Matern covariance with a general shape as the device evaluates it (csrc/cov.h matern_general). No reference
+ * counterpart (tests). 0 < nu <= 100; x (n): the scaled distances sqrt(2 nu) r / rho; c (n) and dc (n): the
+ * correlation 2^(1-nu) / Gamma(nu) x^nu K_nu(x) and its derivative -2^(1-nu) / Gamma(nu) x^(nu+1) K_{nu-1}(x) with
+ * respect to the logarithm of the range transform (x <= 0: 1 and 0). */
+GPBOOST_AMD_EXPORT int GPB_TestMaternGeneral(double nu, int n, const double* x, double* c, double* dc);
 /* The batched dense kernel of models with several clusters (csrc/dense_batch.hip) on caller-given clusters. No
  * reference counterpart (tests). C clusters, cluster c holding the rows ptr[c] .. ptr[c + 1] - 1 (ptr: C + 1 entries
  * from 0, 1 .. 64 rows per cluster) of X (N x d row-major, d in 1..3) and y (N); cov_type 0..3, var and phi > 0 on
