@@ -1032,10 +1032,11 @@ class GPModel:
                                                       self._host_reduce, None))
 
 
-def vecchia_fisher_rows(X, nbr, cov_type: int, var: float, phi: float):
+def vecchia_fisher_rows(X, nbr, cov_type: int, var: float, phi: float, shape=None):
     """GPB_TestVecchiaFisherRows: the row factor of the Vecchia Fisher information (transformed scale, nugget 1) for
     the points X (n x d, Vecchia order) and the neighbour table nbr (n x m). Returns (Bv, dBv_var, dBv, Dinv,
-    dD_var, dD)."""
+    dD_var, dD). With a shape: GPB_TestVecchiaFisherRowsMatern, the Matern covariance of that smoothness (cov_type is
+    then not used)."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     nbr = np.ascontiguousarray(nbr, dtype=np.int32)
     (n, d), m = X.shape, nbr.shape[1]
@@ -1043,10 +1044,12 @@ def vecchia_fisher_rows(X, nbr, cov_type: int, var: float, phi: float):
         raise ValueError("nbr must have one row per point")
     big = [np.empty((n, m)) for _ in range(3)]
     small = [np.empty(n) for _ in range(3)]
-    fn = lib().GPB_TestVecchiaFisherRows
+    fn = lib().GPB_TestVecchiaFisherRows if shape is None else lib().GPB_TestVecchiaFisherRowsMatern
     D, c = ctypes.POINTER(ctypes.c_double), ctypes
-    fn.argtypes = [D, c.POINTER(c.c_int32), c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double] + [D] * 6
-    _safe_call(fn(_dp(X), _ip(nbr), n, d, m, int(cov_type), float(var), float(phi), *map(_dp, big + small)))
+    which = c.c_int if shape is None else c.c_double
+    fn.argtypes = [D, c.POINTER(c.c_int32), c.c_int, c.c_int, c.c_int, which, c.c_double, c.c_double] + [D] * 6
+    _safe_call(fn(_dp(X), _ip(nbr), n, d, m, int(cov_type) if shape is None else float(shape), float(var), float(phi),
+                  *map(_dp, big + small)))
     return (*big, *small)
 
 

@@ -37,7 +37,7 @@ LDFLAGS = ["-shared", "-fopenmp", f"--offload-arch={ARCH}", f"-L{ROCM}/lib", f"-
 # the flag keeps the compiler from forming v_pk_*_f32 in any helper code)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"vecchia_rows_wide.hip": _NO_PK_F32, "vecchia_fisher_rows_wide.hip": _NO_PK_F32,
-               "vecchia_rows_bessel.hip": _NO_PK_F32}
+               "vecchia_rows_bessel.hip": _NO_PK_F32, "vecchia_fisher_rows_bessel.hip": _NO_PK_F32}
 
 
 def sources():

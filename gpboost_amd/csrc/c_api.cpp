@@ -1099,6 +1099,14 @@ int GPB_TestVecchiaFisherRows(const double* X, const int32_t* nbr, int n, int d,
   API_END();
 }
 
+int GPB_TestVecchiaFisherRowsMatern(const double* X, const int32_t* nbr, int n, int d, int m, double shape, double var,
+                                    double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                                    double* dD) {
+  API_BEGIN();
+  gpb_amd::test_vecchia_fisher_rows_matern(X, nbr, n, d, m, shape, var, phi, Bv, dBv_var, dBv, Dinv, dD_var, dD);
+  API_END();
+}
+
 int GPB_TestVecchiaNeighbors(const double* x, int n, int d, int m, int row_begin, int row_end, int end_search_at,
                              int use_gpu, int32_t* out, int64_t out_len) {
   API_BEGIN();

@@ -36,7 +36,7 @@ class DenseSolver {
   // components): Psi gains sum_k tau_k [lev_k(i) == lev_k(j)] (d_lev: device K x n level indices, K <= 8)
   // in every build; K = 0 switches it off. Predictions then take the prediction points' levels (SetGroupedPred:
   // device K x np, -1 - id for a label not in the training data, equal ids for equal new labels).
-  // cov_type kMaternGeneral (Eval, Factor and what builds on them; Fisher and Predict do not serve it): the shape
+  // cov_type kMaternGeneral (Eval, Factor, Fisher and what builds on them; Predict does not serve it): the shape
   void SetMaternGeneral(const MaternGeneralPars& mg) { mg_ = mg; }
   void SetGrouped(int K, const int* d_lev, const double* tau);
   void SetGroupedPred(int np, const int* d_plev);

@@ -723,7 +723,7 @@ __global__ void __launch_bounds__(256) dense_grad_kernel(const double* __restric
 template <int COV>
 __global__ void __launch_bounds__(256) build_dsigma_kernel(const double* __restrict__ X, int n, int d, int ld,
                                                            double phi, double dscale, double* __restrict__ D1,
-                                                           double* __restrict__ D2) {
+                                                           double* __restrict__ D2, CovShape<COV> sh = {}) {
   const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
   const int ti = threadIdx.x & 63;
   for (int jj = threadIdx.x >> 6; jj < 64; jj += 4) {
@@ -733,7 +733,7 @@ __global__ void __launch_bounds__(256) build_dsigma_kernel(const double* __restr
     if (i != j) {
       double s = 0.;
       for (int q = 0; q < d; ++q) { const double t = X[(size_t)i * d + q] - X[(size_t)j * d + q]; s += t * t; }
-      cov_dcov<COV>(sqrt(s), 1., phi, c, dc);
+      cov_dcov_s<COV>(sqrt(s), 1., phi, sh, c, dc);
     }
     D1[(size_t)i + (size_t)j * ld] = c;
     D2[(size_t)i + (size_t)j * ld] = dscale * dc;
@@ -1358,21 +1358,22 @@ void DenseSolver::Fisher(int cov_type, double var, double phi, double dscale, do
   double* W = W_.get();
   HIP_CHECK(hipMemsetAsync(info_.get(), 0, sizeof(int), stream_));
   const int nt = (n + 63) / 64;
-  dispatch_cov(cov_type, [&](auto c) {
-    hipLaunchKernelGGL((build_psi_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld, var,
-                       phi, A, NoShape{});
-  });
-  HIP_CHECK(hipGetLastError());
+  BuildPsi(cov_type, var, phi);
   AddGrouped();
   PotrfLookahead();
   Trtri(0, n);
   gemm(stream_, n, n, n, 1., W, ld, 1, W, ld, 0, 0., A, ld, 1, 0, 1, 1);   // P = W^T W (lower)
   hipLaunchKernelGGL(mirror_lower_kernel, dim3(nt, nt), dim3(256), 0, stream_, A, n, ld);
   DevBuf<double> D2((size_t)ld * ld), G1((size_t)ld * ld), G2((size_t)ld * ld), part((size_t)nt * nt * 6);
-  dispatch_cov(cov_type, [&](auto c) {
-    hipLaunchKernelGGL((build_dsigma_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld,
-                       phi, dscale, W, D2.get());   // D1 into W (L^-1 is no longer needed)
-  });
+  if (cov_type == kMaternGeneral) {   // D1 into W (L^-1 is no longer needed)
+    hipLaunchKernelGGL((build_dsigma_kernel<kMaternGeneral>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld, phi,
+                       dscale, W, D2.get(), MgShape());
+  } else {
+    dispatch_cov(cov_type, [&](auto c) {
+      hipLaunchKernelGGL((build_dsigma_kernel<decltype(c)::value>), dim3(nt, nt), dim3(256), 0, stream_, d_X_, n, d, ld,
+                         phi, dscale, W, D2.get(), NoShape{});
+    });
+  }
   HIP_CHECK(hipGetLastError());
   gemm(stream_, n, n, n, 1., A, ld, 0, W, ld, 0, 0., G1.get(), ld);
   gemm(stream_, n, n, n, 1., A, ld, 0, D2.get(), ld, 0, 0., G2.get(), ld);

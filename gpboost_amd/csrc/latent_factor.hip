@@ -397,6 +397,16 @@ void launch_cov(int cov, const LatentFactorArgs& a, hipStream_t s) {
 void launch_latent_factor(int cov_type, const LatentFactorArgs& a, hipStream_t s) {
   if (a.d < 1 || a.d > kDMax) Fatal("GPU Vecchia kernel supports 1 <= dim_gp_coords <= %d, got %d", kDMax, a.d);
   if (a.n <= 0) return;
+  if (cov_type == kMaternGeneral) {   // not one of dispatch_cov's: the kernels that evaluate each pair once serve it
+    if (a.dBv_var == nullptr)
+      Fatal("the latent Vecchia factor (no nugget) is not available for the Matern covariance with a general shape");
+    if (a.m > kRowsWideMaxM)
+      Fatal("num_neighbors = %d > %d is not supported for the Vecchia Fisher information", a.m, kRowsWideMaxM);
+    if (!(a.mg.nu > 0.)) Fatal("the Matern shape (cov_fct_shape) has not been set for the general-shape Fisher row kernel");
+    if (a.m <= 64) launch_vecchia_fisher_rows_bessel(a, s);
+    else launch_vecchia_fisher_rows_wide(cov_type, a, s);
+    return;
+  }
   switch (lanes_for_m(a.m)) {
     case 16: launch_cov<16>(cov_type, a, s); break;
     case 32: launch_cov<32>(cov_type, a, s); break;

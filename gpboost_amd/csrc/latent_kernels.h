@@ -17,6 +17,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "matern_general.h"
+
 namespace gpb_amd {
 
 struct LatentFactorArgs {
@@ -36,12 +38,17 @@ struct LatentFactorArgs {
   // Vecchia_utils.cpp:1512, 1573-1580: dA = C^-1 a, dD = var - a.c - a.a)
   double* dBv_var;
   double* dD_var;
+  MaternGeneralPars mg;  // kMaternGeneral only (the nugget form: the wave-per-row and the wide Fisher kernel)
 };
 void launch_latent_factor(int cov_type, const LatentFactorArgs& a, hipStream_t s);
 // The nugget form (dBv_var != nullptr) for 64 < m <= kRowsWideMaxM (vecchia_fisher_rows_wide.hip: one workgroup per
 // row, blocked Cholesky in LDS with c as a border row, t = dC a on the whole workgroup, the two dependent solves in
 // one sweep). launch_latent_factor routes to it; dBv / dD stay nullable.
 void launch_vecchia_fisher_rows_wide(int cov_type, const LatentFactorArgs& a, hipStream_t s);
+// The nugget form for the Matern covariance with a general shape (kMaternGeneral, a.mg) and m <= 64
+// (vecchia_fisher_rows_bessel.hip: one wave per row, every pair covariance evaluated once, the wide kernel's stages on
+// that wave). launch_latent_factor routes to it; dBv / dD stay nullable.
+void launch_vecchia_fisher_rows_bessel(const LatentFactorArgs& a, hipStream_t s);
 
 struct SparseB {
   int n, m;

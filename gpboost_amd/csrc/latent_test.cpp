@@ -351,13 +351,13 @@ void test_latent_vector(int op, int n, int t, int np, int ia, int ib, double alp
   *guard = touched;
 }
 
-void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int m, int cov_type, double var,
-                              double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
-                              double* dD) {
-  const char* fn = "GPB_TestVecchiaFisherRows";
+namespace {
+// the body of the two Fisher row hooks: the host-side checks, NaN-initialised outputs between guard bands, the launch
+void fisher_rows_hook(const char* fn, const double* X, const int* nbr, int n, int d, int m, int cov_type,
+                      const MaternGeneralPars& mg, double var, double phi, double* Bv, double* dBv_var, double* dBv,
+                      double* Dinv, double* dD_var, double* dD) {
   test_latent_check_graph(fn, n, m, nbr, (int64_t)n * m, d, X, (int64_t)n * d);
   if (d > 3) Fatal("%s: d = %d", fn, d);
-  if (cov_type < kMatern05 || cov_type > kGaussian) Fatal("%s: cov_type = %d", fn, cov_type);
   if (!(var > 0.) || !(phi > 0.) || !std::isfinite(var) || !std::isfinite(phi))
     Fatal("%s: var = %g, phi = %g", fn, var, phi);
   if (Bv == nullptr || Dinv == nullptr) Fatal("%s: Bv or Dinv is NULL", fn);
@@ -388,6 +388,7 @@ void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int
   fa.nugget = 1.;
   fa.Bv = p[0]; fa.dBv_var = p[1]; fa.dBv = p[2];
   fa.Dinv = p[3]; fa.dD_var = p[4]; fa.dD = p[5];
+  fa.mg = mg;
   launch_latent_factor(cov_type, fa, nullptr);
   HIP_CHECK(hipDeviceSynchronize());
   for (int q = 0; q < 6; ++q) {
@@ -399,6 +400,25 @@ void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int
       if (!std::isnan(h[g]) || !std::isnan(h[kGuard + len + g])) Fatal("%s: output %d was written out of range", fn, q);
     std::memcpy(host[q], h.data() + kGuard, sizeof(double) * len);
   }
+}
+}  // namespace
+
+void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int m, int cov_type, double var,
+                              double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                              double* dD) {
+  const char* fn = "GPB_TestVecchiaFisherRows";
+  if (cov_type < kMatern05 || cov_type > kGaussian) Fatal("%s: cov_type = %d", fn, cov_type);
+  fisher_rows_hook(fn, X, nbr, n, d, m, cov_type, MaternGeneralPars{}, var, phi, Bv, dBv_var, dBv, Dinv, dD_var, dD);
+}
+
+void test_vecchia_fisher_rows_matern(const double* X, const int* nbr, int n, int d, int m, double shape, double var,
+                                     double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                                     double* dD) {
+  const char* fn = "GPB_TestVecchiaFisherRowsMatern";
+  if (!(shape > 0.) || shape > kMaternGeneralMaxShape)
+    Fatal("%s: shape = %g outside (0, %g]", fn, shape, kMaternGeneralMaxShape);
+  fisher_rows_hook(fn, X, nbr, n, d, m, kMaternGeneral, matern_general_pars(shape), var, phi, Bv, dBv_var, dBv, Dinv,
+                   dD_var, dD);
 }
 
 // ---------------------------------------------------------------- the C ABI's object

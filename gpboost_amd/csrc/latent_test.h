@@ -70,6 +70,11 @@ void test_latent_check_graph(const char* fn, int n, int m, const int* nbr, int64
 void test_vecchia_fisher_rows(const double* X, const int* nbr, int n, int d, int m, int cov_type, double var,
                               double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
                               double* dD);
+// GPB_TestVecchiaFisherRowsMatern: the same for the Matern covariance with the smoothness shape (kMaternGeneral; m <= 64:
+// vecchia_fisher_rows_bessel.hip, 65 to 128: the wide kernel's general-shape instance)
+void test_vecchia_fisher_rows_matern(const double* X, const int* nbr, int n, int d, int m, double shape, double var,
+                                     double phi, double* Bv, double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                                     double* dD);
 // opts (nullable, 9 entries): {relabel, dense_rows, head_rows, tail_merge, seg_form, tail_order, tail_form, tail_w,
 // no_graph}, an entry < 0 = the environment's / the default
 LatentOptions test_latent_options(const char* fn, const int64_t* opts, int n);

@@ -772,7 +772,6 @@ void REModelAMD::OptimCovPar(const double* y, const double* fixed_effects, bool 
   // (re_model_template.h:846-1700) -> OptimExternal "lbfgs" (optim_utils.h:561-706)
   if (called_in_boosting) RefuseClusters("the GPBoost-algorithm covariance update (GPB_OptimCovParBoosting)");
   if (isettings_.optimizer == "fisher_scoring") RefuseClusters("optimizer_cov = 'fisher_scoring'");
-  RefuseGeneralShapeFisher();
   UseDevice();
   const int n = cfg_.n;
   if (reuse_lr && !called_in_boosting)
@@ -1010,14 +1009,7 @@ void REModelAMD::InitializeOptimizerNames() {
   if (optimizer_coef_.empty()) optimizer_coef_ = cfg_.latent ? "lbfgs" : "wls";
 }
 
-void REModelAMD::RefuseGeneralShapeFisher() const {
-  if (isettings_.optimizer == "fisher_scoring" && cfg_.cov_type == kMaternGeneral)
-    Fatal("optimizer_cov = 'fisher_scoring' is not supported for cov_fct 'matern' with cov_fct_shape = %g by gpboost_amd "
-          "(use 'lbfgs' or 'gradient_descent'; supported shapes: 0.5, 1.5, 2.5)", cfg_.shape);
-}
-
 void REModelAMD::OptimLinRegrCoefCovPar(const double* y, const double* X, int p, const double* fixed_effects) {
-  RefuseGeneralShapeFisher();
   if (X != nullptr && p > 0) RefuseClusters("linear regression covariates (X)");
   if (!est_idx_.empty() && X != nullptr && p > 0)
     Fatal("estimate_cov_par_index (fixing covariance parameters) with linear regression covariates is not supported by "
@@ -1160,9 +1152,11 @@ void REModelAMD::GetInitCovPar(double* out) const {
 }
 
 void REModelAMD::StdDevCovPars(const double* orig, double* sd) {
-  if (cfg_.cov_type == kMaternGeneral)
+  // the general-shape Matern: the Vecchia row kernels and the dense engine serve it, the FITC Fisher kernels do not
+  if (cfg_.cov_type == kMaternGeneral && (fitc_ || vif_))
     Fatal("standard errors of the covariance parameters are not supported for cov_fct 'matern' with cov_fct_shape = %g "
-          "by gpboost_amd (supported shapes: 0.5, 1.5, 2.5)", cfg_.shape);
+          "and gp_approx = '%s' by gpboost_amd (supported there: the shapes 0.5, 1.5, 2.5)", cfg_.shape,
+          cfg_.gp_approx.c_str());
   // CalcFisherInformation, dense branch (re_model_template.h:9179-9230), transf_scale = false,
   // include_error_var = true: with Sigma^-1 = Psi^-1 / sigma^2 and dSigma_k on the original scale
   // (sigma^2: I; sigma1^2: the correlation matrix; rho: sigma1^2 dcorr/drho)
@@ -1182,7 +1176,8 @@ void REModelAMD::StdDevCovPars(const double* orig, double* sd) {
     if (world_ > 1) Fatal("standard deviations of covariance parameters are only available on single-rank models");
     if (!vfisher_)
       vfisher_.reset(new VecchiaFisher(cfg_.n, cfg_.d, cfg_.num_neighbors, d_X_.get(), d_nbr_.get(), nbr_, stream_));
-    vfisher_->Fisher(cfg_.cov_type, orig, trafo, iter.num_rand_vec_trace, iter.seed_rand_vec_trace, 0, &F[0][0]);
+    vfisher_->Fisher(cfg_.cov_type, orig, trafo, iter.num_rand_vec_trace, iter.seed_rand_vec_trace, 0, &F[0][0],
+                     cfg_.mg);
   } else if (fitc_) {
     // CalcFisherInformation_FITC_FSA (re_model_template.h:9363-9548), the same probes
     fitc_->Fisher(cfg_.cov_type, orig, trafo, iter.num_rand_vec_trace, iter.seed_rand_vec_trace, 0, &F[0][0]);

@@ -344,7 +344,6 @@ class REModelAMD {
                     double shift, bool scale_first);
   std::vector<int> FitcMatch(const std::vector<double>& xp_rowmajor, int n_pred) const;
   void ResponseTransform(int n_pred, double* mean, double* var, double* cov);
-  void RefuseGeneralShapeFisher() const;   // Fisher scoring has no general-shape Matern kernels
   double range_trafo_of(double rho) const { return range_trafo(cfg_.cov_type, rho, cfg_.shape); }
   void FindInitCovPar(const double* y, double* trafo) const;
   double InitialRangeTrafo() const;

@@ -71,7 +71,7 @@ VecchiaFisher::VecchiaFisher(int n, int d, int m, const double* d_X, const int* 
 VecchiaFisher::~VecchiaFisher() { pre_.reset(); }
 
 void VecchiaFisher::Fisher(int cov_type, const double* orig, const double* trafo, int t, int seed, uint64_t run_id,
-                           double* FI) {
+                           double* FI, const MaternGeneralPars& mg) {
   const int n = n_, m = m_;
   if (t < 1) Fatal("num_rand_vec_trace must be > 0");
   if (!(orig[0] > 0. && orig[1] > 0. && orig[2] > 0.)) Fatal("covariance parameters must be > 0");
@@ -90,6 +90,7 @@ void VecchiaFisher::Fisher(int cov_type, const double* orig, const double* trafo
   fa.Bv = Bv_.get(); fa.Dinv = Dinv_.get();
   fa.dBv = dBv1_.get(); fa.dD = dD1_.get();
   fa.dBv_var = dBv0_.get(); fa.dD_var = dD0_.get();
+  fa.mg = mg;
   launch_latent_factor(cov_type, fa, s_);
   // 2. Sigma_t z = B^-1 D B^-T z (P) and B^-T z (W) by one VADU application with dw = D^-1
   std::vector<double> Zh((size_t)n * t);

@@ -14,7 +14,8 @@
 //
 // This build: the factor and its two derivatives from one row kernel on the transformed scale (the
 // latent factor kernel in its nugget form, latent_factor.hip; 65 to 128 neighbours: the workgroup-per-row
-// kernel of vecchia_fisher_rows_wide.hip), rescaled to the original scale on the
+// kernel of vecchia_fisher_rows_wide.hip; general-shape Matern, up to 64: the wave-per-row kernel of
+// vecchia_fisher_rows_bessel.hip), rescaled to the original scale on the
 // device (B is scale-free; D_o = sigma^2 D, dB_o / dsigma1^2 = dB / dlog(var) / sigma1^2, dD_o / dsigma1^2 =
 // dD / dlog(var) sigma^2 / sigma1^2, d / drho = dlog(phi) / drho d / dlog(phi), dD also times sigma^2);
 // Sigma z from ONE application of the VADU plan (vadu_precond.h: B^-1 diag(1/dw) B^-T with dw = D^-1 —
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "common.h"
+#include "matern_general.h"
 #include "vadu_precond.h"
 
 namespace gpb_amd {
@@ -46,8 +48,10 @@ class VecchiaFisher {
                 hipStream_t stream);
   ~VecchiaFisher();
   // FI (3 x 3, row-major, [sigma^2, sigma1^2, rho]) at the original-scale parameters orig; trafo: the same
-  // on the transformed scale (TransformCovPars); t probes from (seed, run_id).
-  void Fisher(int cov_type, const double* orig, const double* trafo, int t, int seed, uint64_t run_id, double* FI);
+  // on the transformed scale (TransformCovPars); t probes from (seed, run_id). mg: the shape constants of cov_type
+  // kMaternGeneral (the row kernel is all that depends on the covariance).
+  void Fisher(int cov_type, const double* orig, const double* trafo, int t, int seed, uint64_t run_id, double* FI,
+              const MaternGeneralPars& mg = {});
 
  private:
   int n_, d_, m_;

@@ -57,6 +57,10 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_fisher_rows_wide_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int d = a.d;
   const double var = a.var, phi = a.phi;
+  const CovShape<COV> sh = [&] {
+    if constexpr (COV == kMaternGeneral) return a.mg;
+    else return NoShape{};
+  }();
   const double cdiag = var * a.jitter + a.nugget;
 
   for (int i = blockIdx.x; i < a.n; i += gridDim.x) {
@@ -77,7 +81,7 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_fisher_rows_wide_kernel(
         const double xi = q < d ? a.X[(size_t)i * d + q] : 0.;
         s += (xi - gx[q]) * (xi - gx[q]);
       }
-      cov_dcov_sq<COV>(s, var, phi, gc, gdc);
+      cov_dcov_sq_s<COV>(s, var, phi, sh, gc, gdc);
       tp[tid] = rv ? gc : -1.;   // covariances are >= 0
     }
     __syncthreads();
@@ -96,7 +100,7 @@ __global__ void __launch_bounds__(kWideThreads) vecchia_fisher_rows_wide_kernel(
     }
     __syncthreads();
 
-    wide_pairs<COV>(A, S, nbx, KP, k, var, phi, tid);   // ---- 2.
+    wide_pairs<COV>(A, S, nbx, KP, k, var, phi, tid, sh);   // ---- 2.
     __syncthreads();
     wide_chol<true, true>(A, S, KP, dg, zb, tid, lane, wave);   // ---- 3., the border row zb riding along
 
@@ -179,6 +183,12 @@ void launch_vecchia_fisher_rows_wide(int cov_type, const LatentFactorArgs& a, hi
   if (a.Bv == nullptr || a.Dinv == nullptr || a.dBv_var == nullptr || a.dD_var == nullptr)
     Fatal("the wide Vecchia Fisher row kernel needs Bv, Dinv, dBv_var and dD_var");
   if (a.n <= 0) return;
+  if (cov_type == kMaternGeneral) {   // not one of dispatch_cov's: this kernel and the wave-per-row one serve it
+    if (!(a.mg.nu > 0.)) Fatal("the Matern shape (cov_fct_shape) has not been set for the general-shape Fisher row kernel");
+    wide_launch(vecchia_fisher_rows_wide_kernel<kMaternGeneral>, a, a.m, a.n, "fisher rows wide",
+                " for the Vecchia Fisher information", s);
+    return;
+  }
   dispatch_cov(cov_type, [&](auto cov) {
     wide_launch(vecchia_fisher_rows_wide_kernel<decltype(cov)::value>, a, a.m, a.n, "fisher rows wide",
                 " for the Vecchia Fisher information", s);

@@ -172,25 +172,6 @@ __global__ void __launch_bounds__(64) matern_general_test_kernel(MaternGeneralPa
   if (i < n) matern_general(x[i], 1., p, c[i], dc[i]);
 }
 
-template <int NW>
-int launch_nw(const VecchiaRowsArgs& a, size_t bytes, int cus, hipStream_t s) {
-  auto kern = vecchia_rows_bessel_kernel<kMaternGeneral, NW>;
-  if (bytes > 64 * 1024)   // above the default dynamic-LDS limit
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)bytes));
-  int per_cu = 0;
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * NW, bytes));
-  const int rows = a.r1 - a.r0;
-  const int blocks = std::min({(rows + NW - 1) / NW, std::max(per_cu, 1) * std::max(cus, 1), kRowsWideMaxBlocks});
-  static const bool info = std::getenv("GPBOOST_AMD_ROWS_PROF") != nullptr;
-  if (info)
-    std::fprintf(stderr, "[rows bessel] m=%d grid=%d waves/workgroup=%d workgroups/CU=%d LDS bytes/workgroup=%zu\n", a.m,
-                 blocks, NW, per_cu, bytes);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NW), bytes, s, a);
-  HIP_CHECK(hipGetLastError());
-  return blocks;
-}
-
 }  // namespace
 
 void test_matern_general(double nu, int n, const double* x, double* c, double* dc) {
@@ -213,16 +194,8 @@ int launch_vecchia_rows_bessel(const VecchiaRowsArgs& a, hipStream_t s) {
   if (a.m < 1 || a.m > 64) Fatal("the wave-per-row Vecchia kernel serves num_neighbors <= 64, got %d", a.m);
   if (!(a.mg.nu > 0.)) Fatal("the Matern shape (cov_fct_shape) has not been set for the general-shape row kernel");
   if (a.r1 <= a.r0) return 0;
-  int dev = 0, cus = 0, lds_max = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-  const size_t wave_bytes = wide_lds_doubles(a.m) * sizeof(double);
-  if (4 * wave_bytes <= (size_t)lds_max) return launch_nw<4>(a, 4 * wave_bytes, cus, s);
-  if (2 * wave_bytes <= (size_t)lds_max) return launch_nw<2>(a, 2 * wave_bytes, cus, s);
-  if (wave_bytes > (size_t)lds_max)
-    Fatal("num_neighbors = %d needs %zu bytes of LDS per wave, this device has %d", a.m, wave_bytes, lds_max);
-  return launch_nw<1>(a, wave_bytes, cus, s);
+  return wave_rows_launch(vecchia_rows_bessel_kernel<kMaternGeneral, 4>, vecchia_rows_bessel_kernel<kMaternGeneral, 2>,
+                          vecchia_rows_bessel_kernel<kMaternGeneral, 1>, a, a.m, a.r1 - a.r0, "rows bessel", s);
 }
 
 }  // namespace gpb_amd

@@ -1,6 +1,8 @@
 // The core of the two wide Vecchia row kernels (64 < num_neighbors <= kRowsWideMaxM, gfx950, wave64):
-// vecchia_rows_wide.hip (likelihood and gradient rows) and vecchia_fisher_rows_wide.hip (Fisher rows). Included by
-// these two files only. One 256-thread workgroup (four waves) owns a Vecchia row with k = min(i, m) neighbours; with
+// vecchia_rows_wide.hip (likelihood and gradient rows) and vecchia_fisher_rows_wide.hip (Fisher rows), and of their
+// wave-per-row forms for the general-shape Matern covariance and m <= 64 (vecchia_rows_bessel.hip,
+// vecchia_fisher_rows_bessel.hip: NW = 1 and NT = 64 below, one LDS slice per wave). Included by these four files
+// only. One 256-thread workgroup (four waves) owns a Vecchia row with k = min(i, m) neighbours; with
 // KP = k rounded up to a multiple of 16 (rows >= k are identity padding with zero right-hand sides, which leaves
 // every solution unchanged) the between-neighbour matrix lives in ONE square LDS array A (KP x KP, odd row stride
 // S = MP + 1, MP = m rounded up to 16): C_rc in the lower triangle (r > c), dC_rc / dlog(phi) in the upper one
@@ -25,7 +27,7 @@
 //  - wide_forward / wide_backward: L z = rhs and L^T x = z for NR right-hand sides together on ONE wave: lane l
 //    holds entries l and l + 64 of each, column sweeps with one wave shuffle per column and right-hand side, one
 //    load of L and of the pivot per column for all of them, no barrier inside;
-//  - wide_launch: the host side (LDS check, grid = resident capacity, launch).
+//  - wide_launch, wave_rows_launch: the host side (LDS check, grid = resident capacity, launch).
 // Every loop's trip count is uniform over the workgroup or the wave; where the work per lane differs, the lanes are
 // predicated instead. Every sum has a fixed order and there is no atomic. A failed pivot has no path of its own:
 // sqrt of a negative pivot is NaN, which spreads to everything after it.
@@ -270,6 +272,37 @@ int wide_launch(void (*kern)(Args), const Args& a, int m, int rows, const char* 
   if (info)
     std::fprintf(stderr, "[%s] m=%d grid=%d workgroups/CU=%d LDS bytes/workgroup=%zu\n", tag, m, blocks, per_cu, bytes);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWideThreads), bytes, s, a);
+  HIP_CHECK(hipGetLastError());
+  return blocks;
+}
+
+// Host side of the wave-per-row kernels (m <= 64, one wave's LDS slice is wide_lds_doubles(m)): kern4 / kern2 / kern1
+// are the instances with four, two and one independent waves per workgroup; four are taken where the device's
+// per-workgroup LDS limit allows, else two or one. The grid is the resident capacity; returns it.
+template <typename Args>
+int wave_rows_launch(void (*kern4)(Args), void (*kern2)(Args), void (*kern1)(Args), const Args& a, int m, int rows,
+                     const char* tag, hipStream_t s) {
+  int dev = 0, cus = 0, lds_max = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  const size_t wave_bytes = wide_lds_doubles(m) * sizeof(double);
+  if (wave_bytes > (size_t)lds_max)
+    Fatal("num_neighbors = %d needs %zu bytes of LDS per wave, this device has %d", m, wave_bytes, lds_max);
+  const int nw = 4 * wave_bytes <= (size_t)lds_max ? 4 : (2 * wave_bytes <= (size_t)lds_max ? 2 : 1);
+  void (*kern)(Args) = nw == 4 ? kern4 : (nw == 2 ? kern2 : kern1);
+  const size_t bytes = nw * wave_bytes;
+  if (bytes > 64 * 1024)   // above the default dynamic-LDS limit
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)bytes));
+  int per_cu = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * nw, bytes));
+  const int blocks = std::min({(rows + nw - 1) / nw, std::max(per_cu, 1) * std::max(cus, 1), kRowsWideMaxBlocks});
+  static const bool info = std::getenv("GPBOOST_AMD_ROWS_PROF") != nullptr;
+  if (info)
+    std::fprintf(stderr, "[%s] m=%d grid=%d waves/workgroup=%d workgroups/CU=%d LDS bytes/workgroup=%zu\n", tag, m,
+                 blocks, nw, per_cu, bytes);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * nw), bytes, s, a);
   HIP_CHECK(hipGetLastError());
   return blocks;
 }

@@ -609,6 +609,14 @@ GPBOOST_AMD_EXPORT int GPB_TestLatentOpsPcg(void* handle, int t, int n_single, d
 GPBOOST_AMD_EXPORT int GPB_TestVecchiaFisherRows(const double* X, const int32_t* nbr, int n, int d, int m,
                                                  int cov_type, double var, double phi, double* Bv, double* dBv_var,
                                                  double* dBv, double* Dinv, double* dD_var, double* dD);
+/* The same rows for the Matern covariance with a general smoothness: shape in (0, 100] takes the place of cov_type
+ * (phi = sqrt(2 shape) / rho), every other argument and every check as above; dBv_var with dD_var is required here
+ * (without them: an error return). m <= 64 is served by the wave-per-row kernel, 65 to 128 by the workgroup-per-row
+ * kernel's general-shape instance. */
+GPBOOST_AMD_EXPORT int GPB_TestVecchiaFisherRowsMatern(const double* X, const int32_t* nbr, int n, int d, int m,
+                                                       double shape, double var, double phi, double* Bv,
+                                                       double* dBv_var, double* dBv, double* Dinv, double* dD_var,
+                                                       double* dD);
 /* The Vecchia neighbour search on host arrays: the lists of the rows [row_begin, row_end) of the points x (n x d
  * row-major, finite) among the earlier points j <= end_search_at (-1: n - 2, the likelihood's setting; prediction
  * rows after n_obs observed points pass n_obs - 1). use_gpu != 0: vecchia_neighbors_gpu (d in 1..3; m <= 64 one
